@@ -10,14 +10,21 @@ registration_generalized_icp(L1, 1e-6/1e-6/100) for voxels 0.4/0.2/0.1 m), exact
 (2_MGICP...py:190-199).  value = pairs registered / wall time of the K steps.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--variant gicp|fgr] [--radius-rule script|af] [--config5]
-                    [--pairs-per-step 48] [--inflight 4] [--group 0=by size] [--points 200000] [--no-cpu-baseline] [--no-extras]
+                    [--pairs-per-step 48] [--inflight 4] [--group 0=by size] [--points 200000] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, config).  --full adds
+everything else the line can carry: the library's launch profile of the timed region, the solo roofline pass, the tracked
+profile figures, `extras` and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned (poses, fitness,
+RMSE, per-scale records and a fixed sample of the correspondence sets) as DIR/<name>.npy; the inputs are seeded, so two builds
+given the same arguments can be compared output for output.
 
 --gpus N > 1: when no launcher has set RANK, this process starts N ranks itself (python -m torch.distributed.run, one fresh
 process per GPU) BEFORE anything touches HIP, forwards rank 0's JSON line and exits with the launcher's code.  Every rank
 registers its own batches (weak scaling, no data-path collective); one all-gather of the fixed-size pose records closes the
 timed region (RCCL; gloo under PCR_BENCH_REHEARSE=1 / PCR_BENCH_DRYRUN=1).
 
-The default line is the GICP path with the script-2 radii (1.2/0.4/0.1 m).  `extras` in the same line holds short measurements
+The default line is the GICP path with the script-2 radii (1.2/0.4/0.1 m).  With --full, `extras` in the same line holds short measurements
 of the other forms SURVEY §8(d) names: the ALL_FUNCTIONS radius rule (radius_from_cloud_pair * 2^-i), the FGR variant of config 2
 (registro_FGR voxel 0.1 + the same 3-scale GICP, both inside the pair time) and config 5 (2M points, 5 scales, 64-NN normals).
 """
@@ -69,14 +76,20 @@ def parse_args(argv=None):
                     "--config3-tiles times, cost-partitioned over the ranks (sharding.partition(costs=points)), every rank runs ONE fgr+gicp plan (what drivers.stage12 runs), "
                     "one all-gather of the pose records; the line carries per-rank wall, upload time and pairs/s")
     ap.add_argument("--config3-tiles", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: launch profile of the timed region, solo roofline "
+                    "pass, tracked profile figures, extras and the CPU baseline (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float64; "
+                    "correspondences as a fixed, seeded float32 sample)")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("PCR_BENCH_INFLIGHT", "4")),
                     help="independent pairs (or lockstep groups, see --group) in flight per GPU (one library worker thread + context + streams each)")
     ap.add_argument("--group", type=int, default=int(os.environ.get("PCR_BENCH_GROUP", "0")),
                     help="pairs per lockstep group (pcr_pairs_plan.group): that many consecutive pairs of a batch go through the same launches; "
                          "0 = by cloud size as registration.register_pairs_plan(group=None) does (registration.default_group: 6 at 200k points)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.group <= 0:
         args.group = -1          # resolved by registration.default_group once the package is imported (main)
     return args
@@ -121,6 +134,92 @@ def tables_identical(gathered, world, device=None) -> bool:
     out = torch.empty((world, 16), dtype=torch.int64, device=mine.device)
     dist.all_gather_into_tensor(out, mine.reshape(1, 16))
     return bool((out == out[0]).all().item())
+
+
+# ------------------------------------------------------------------------------------------------ inputs and outputs
+def _base_pair_file(n_points, index):
+    """Cache file of synthetic.make_pair(n_points, index=index) (the same rule make_pair applies: $PCR_SYNTH_CACHE, else
+    <repo>/.synth_cache if that directory exists, else the system temp dir)."""
+    import tempfile
+    syn = importlib.import_module(PKG + ".synthetic")
+    repo_cache = os.path.join(ROOT, ".synth_cache")
+    d = os.environ.get("PCR_SYNTH_CACHE") or (repo_cache if os.path.isdir(repo_cache) else os.path.join(tempfile.gettempdir(), "pcr_synth_cache"))
+    return os.path.join(d, f"pair_v1_{n_points}_{syn.SEED}_{index}.npz")
+
+
+def base_pair_indices(args):
+    """(n_points, indices) of the generated pairs a run's workload is derived from (main: base_pair / workload)."""
+    n_distinct = args.pairs if args.pairs > 0 else max(1, args.pairs_per_step)
+    return max(args.points, 200_000), list(range(max(1, min(args.base_pairs, n_distinct))))
+
+
+def prepare_inputs(n_points=200_000, indices=range(8)):
+    """Generate the synthetic base pairs that are not cached yet, in parallel (the generator takes ~20 s per 200k-point pair on
+    one core).  Each pair is made by a fresh `python -c` process that imports only the generator: nothing of the caller's
+    process (its __main__, threads, HIP state) is carried into the children, so build() and bench.py can call this from any
+    script.  The cached pairs are exactly what make_pair returns, so this changes no input; a run that finds them cached
+    starts at once."""
+    missing = [i for i in indices if not os.path.exists(_base_pair_file(n_points, i))]
+    if not missing:
+        return
+    try:
+        avail = len(os.sched_getaffinity(0))
+    except AttributeError:
+        avail = os.cpu_count() or 1
+    workers = max(1, min(len(missing), avail, 16))
+    code = ("import importlib, sys; sys.path.insert(0, sys.argv[1]); "
+            "importlib.import_module(sys.argv[2] + '.synthetic').make_pair(int(sys.argv[3]), index=int(sys.argv[4]))")
+    running = []
+
+    def wait(p):
+        if p.wait() != 0:
+            raise RuntimeError(f"generating synthetic pair {p.args[-1]} ({n_points} points) failed with exit code {p.returncode}")
+    try:
+        for i in missing:
+            if len(running) == workers:
+                wait(running.pop(0))
+            running.append(subprocess.Popen([sys.executable, "-c", code, ROOT, PKG, str(n_points), str(i)]))
+        while running:
+            wait(running.pop(0))
+    finally:
+        for p in running:                   # only after a failure: stop the others
+            p.kill()
+            p.wait()
+
+
+CORR_SAMPLE_ROWS = 1 << 21          # correspondence rows written by --dump-outputs over all pairs (3 x 4 B each: at most 24 MB)
+
+
+def dump_outputs(out_dir, results):
+    """What the last timed step returned, as float64 arrays (one row per pair of the batch), plus a fixed sample of every pair's
+    correspondence set: the set sorted by (source, target) index, rows picked by a generator seeded with the pair's position."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"transformation": np.stack([r.transformation for r in results]).astype(np.float64),
+           "fitness": np.array([r.fitness for r in results], np.float64),
+           "inlier_rmse": np.array([r.inlier_rmse for r in results], np.float64)}
+    if results and results[0].scales:
+        sc = [r.scales for r in results]
+        out["scale_transformation"] = np.array([[s["T"] for s in x] for x in sc], np.float64)
+        for k in ("fitness", "inlier_rmse", "iterations", "n_corr", "converged", "n_voxel", "n_clean"):
+            out[f"scale_{k}"] = np.array([[s[k] for s in x] for x in sc], np.float64)
+    if results and hasattr(results[0], "fgr"):
+        out["fgr_transformation"] = np.stack([r.fgr.transformation for r in results]).astype(np.float64)
+        out["fgr_fitness"] = np.array([r.fgr.fitness for r in results], np.float64)
+        out["fgr_inlier_rmse"] = np.array([r.fgr.inlier_rmse for r in results], np.float64)
+    per_pair = max(1, CORR_SAMPLE_ROWS // max(1, len(results)))
+    counts, rows = [], []
+    for k, r in enumerate(results):
+        c = np.asarray(r.correspondence_set, dtype=np.int64).reshape(-1, 2)
+        counts.append(len(c))
+        c = c[np.lexsort((c[:, 1], c[:, 0]))]
+        if len(c) > per_pair:
+            c = c[np.sort(np.random.default_rng([20241008, k]).choice(len(c), per_pair, replace=False))]
+        rows.append(np.concatenate([np.full((len(c), 1), k, np.int64), c], axis=1))
+    out["n_correspondences"] = np.array(counts, np.float64)
+    out["correspondences_sample"] = (np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)).astype(np.float32)      # (pair, source, target): exact below 2^24
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ dry run (launcher / gather plumbing on CPU)
@@ -234,6 +333,8 @@ def config3_run(args, rank, world, local_rank) -> int:
         res = run(batch, mine[0] if mine else 0)
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
         recs = np.stack([shard.pack_record(i, r) for i, r in zip(mine, res)]) if mine else np.zeros((0, shard.RECORD_DOUBLES))
         # every pose against the reference's shipped GICP pose: the six tight golden pairs within SURVEY 8(c)(2)'s 3e-4 rad / 3e-3 m, s1 -> s0 and the loop closure
         # (noisy for the oracle itself) within 2e-3 rad / 2 cm
@@ -289,6 +390,8 @@ def main(argv=None) -> int:
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.config3 and os.environ.get("PCR_BENCH_DRYRUN") != "1" and os.environ.get("PCR_BENCH_LAUNCHED_BY") != "bench.py":
+        prepare_inputs(*base_pair_indices(args))        # before any rank touches HIP (ranks started by this process find them cached)
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args)
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -379,7 +482,8 @@ def main(argv=None) -> int:
     torch.cuda.synchronize()
     for _ in range(max(args.warmup, 1)):                                        # W untimed warm-up steps (every worker context at least once)
         run_batch(max(B, args.inflight))
-    pool_prof(enable=1, reset=True)
+    if args.full:
+        pool_prof(enable=1, reset=True)                                         # launch profile of the timed region (roofline.us_per_launch_in_flight, ...)
     barrier()
     t0 = time.perf_counter()
     results, rec_rows = [], []
@@ -396,13 +500,44 @@ def main(argv=None) -> int:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearse else "cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    prof = pool_prof(enable=0, reset=True)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results)
 
     def pose_err(res, p):
         dR = res.transformation[:3, :3].T @ p.T_true[:3, :3]
         return {"rad": float(np.arccos(np.clip((np.trace(dR) - 1) / 2, -1, 1))), "m": float(np.linalg.norm(res.transformation[:3, 3] - p.T_true[:3, 3]))}
 
-    line = None
+    res = results[-1]
+    rule_txt = "radius_from_cloud_pair * 2^-i per pair (ALL_FUNCTIONS.py:277-278)" if args.radius_rule == "af" else "radii " + "/".join(f"{d:g}" for d in pairs[0].max_distances_script) + " m"
+    workload_txt = (f"step = batch of {B} independent pairs ({n_distinct} distinct), each {len(pairs[0].source)}-pt synthetic NCLT-shaped clouds, "
+                    + ("registro_FGR (voxel 0.1) + " if args.variant == "fgr" else "") + f"{n_scales}-scale GICP (voxels " + "/".join(f"{v:g}" for v in pairs[0].voxel_sizes)
+                    + f" m, {rule_txt}, SOR(30,1.0), KNN-{normal_k} normals, {args.loss.upper()}, 1e-6/1e-6/100)")
+    it_per_pair = [sum(s["iterations"] for s in r.scales) for r in results]
+    line = {
+        "metric": METRIC,
+        "value": world * n_done / dt, "unit": "pairs/s", "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 points+search, f64 normal equations (SURVEY 8a fp column)", "data": "synthetic", "full": args.full,
+        "config": {"workload": workload_txt, "variant": args.variant, "radius_rule": args.radius_rule,
+                   "points_per_cloud": int(len(pairs[0].source)), "pairs_per_step": B, "distinct_pairs": n_distinct,
+                   "distinct_how": f"{min(args.base_pairs, n_distinct)} independently sampled scene pairs, each re-posed by a rigid motion of both clouds and re-ordered (synthetic.derive_pair); every pair has its own buffers",
+                   "parallelism": f"pairs x{world}", "pairs_in_flight_per_gpu": args.inflight * max(1, args.group), "lockstep_group": args.group, "groups_in_flight_per_gpu": args.inflight,
+                   "in_flight_by": "pcr_register_pairs_plan (library worker threads)",
+                   "scales": [dict(voxel=s["voxel"], max_dist=s["max_dist"], n_voxel=s["n_voxel"], n_clean=s["n_clean"],
+                                   iterations=s["iterations"]) for s in res.scales],
+                   "iterations_per_pair_mean": float(np.mean(it_per_pair)),
+                   "iterations_per_pair_min_median_max": [int(np.min(it_per_pair)), float(np.median(it_per_pair)), int(np.max(it_per_pair))],
+                   "err_vs_planted": pose_err(res, pairs[(B - 1) % len(pairs)]),
+                   "err_vs_planted_max_over_last_step": {k: float(max(pose_err(r, pairs[i % len(pairs)])[k] for i, r in enumerate(results))) for k in ("rad", "m")},
+                   "gathered_records": int(len(gathered)), "tables_identical": same_tables}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return 0 if same_tables else 4
+    prof = pool_prof(enable=0, reset=True)
+
     if rank == 0:
         # ---- roofline pass: the hot loop's launch period WITHOUT the other pairs' kernels in the way.  In the timed region the
         # pairs in flight share the GPU, so HIP events around a chunk of launches also count the time its kernels wait for
@@ -413,7 +548,6 @@ def main(argv=None) -> int:
         run_batch(min(4, n_distinct), inflight=1, group=1)
         torch.cuda.synchronize()
         solo = pool_prof(enable=0, reset=True)
-        res = results[-1]
         ev_ms_f, ev_launches_f, ik_us_f, live_f, _, issued = (prof[i] for i in range(6))
         us_in_flight = 1e3 * ev_ms_f / ev_launches_f if ev_launches_f else None
         ev_ms, ev_launches, ik_us, live, alg_bytes, _ = (solo[i] for i in range(6))
@@ -499,34 +633,13 @@ def main(argv=None) -> int:
                                     "bytes from THIS run's counts (launch = one lockstep group)"}
             except Exception:       # noqa: BLE001 -- a tracked file must never cost the line
                 dominant = None
-        rule_txt = "radius_from_cloud_pair * 2^-i per pair (ALL_FUNCTIONS.py:277-278)" if args.radius_rule == "af" else "radii " + "/".join(f"{d:g}" for d in pairs[0].max_distances_script) + " m"
-        workload_txt = (f"step = batch of {B} independent pairs ({n_distinct} distinct), each {len(pairs[0].source)}-pt synthetic NCLT-shaped clouds, "
-                        + ("registro_FGR (voxel 0.1) + " if args.variant == "fgr" else "") + f"{n_scales}-scale GICP (voxels " + "/".join(f"{v:g}" for v in pairs[0].voxel_sizes)
-                        + f" m, {rule_txt}, SOR(30,1.0), KNN-{normal_k} normals, {args.loss.upper()}, 1e-6/1e-6/100)")
-        it_per_pair = [sum(s["iterations"] for s in r.scales) for r in results]
         # SURVEY 8d's algorithmic bytes of the WHOLE path per pair, from this run's own counts (last step): per cloud and scale 12 N0 + 44 D + 36 C
         # (voxel grid, outlier filter, compaction, normals), per scale 48 C_source (I + 1) for the GICP loop
         n0 = [len(pairs[i % len(pairs)].source) + len(pairs[i % len(pairs)].target) for i in range(len(results))]
         path_bytes = float(np.mean([sum(12.0 * n0[i] + 44.0 * sum(s["n_voxel"]) + 36.0 * sum(s["n_clean"]) + 48.0 * s["n_clean"][0] * (s["iterations"] + 1) for s in r.scales)
                                     for i, r in enumerate(results)]))
         path_gbs = path_bytes * (n_done / dt) / 1e9
-        line = {
-            "metric": METRIC,
-            "value": world * n_done / dt, "unit": "pairs/s", "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 points+search, f64 normal equations (SURVEY 8a fp column)", "data": "synthetic",
-            "config": {"workload": workload_txt, "variant": args.variant, "radius_rule": args.radius_rule,
-                       "points_per_cloud": int(len(pairs[0].source)), "pairs_per_step": B, "distinct_pairs": n_distinct,
-                       "distinct_how": f"{min(args.base_pairs, n_distinct)} independently sampled scene pairs, each re-posed by a rigid motion of both clouds and re-ordered (synthetic.derive_pair); every pair has its own buffers",
-                       "parallelism": f"pairs x{world}", "pairs_in_flight_per_gpu": args.inflight * max(1, args.group), "lockstep_group": args.group, "groups_in_flight_per_gpu": args.inflight,
-                       "in_flight_by": "pcr_register_pairs_plan (library worker threads)",
-                       "scales": [dict(voxel=s["voxel"], max_dist=s["max_dist"], n_voxel=s["n_voxel"], n_clean=s["n_clean"],
-                                       iterations=s["iterations"]) for s in res.scales],
-                       "iterations_per_pair_mean": float(np.mean(it_per_pair)),
-                       "iterations_per_pair_min_median_max": [int(np.min(it_per_pair)), float(np.median(it_per_pair)), int(np.max(it_per_pair))],
-                       "err_vs_planted": pose_err(res, pairs[(B - 1) % len(pairs)]),
-                       "err_vs_planted_max_over_last_step": {k: float(max(pose_err(r, pairs[i % len(pairs)])[k] for i, r in enumerate(results))) for k in ("rad", "m")},
-                       "gathered_records": int(len(gathered)), "tables_identical": same_tables},
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "traffic_from_profiles": traffic_file, "valu_from_profiles": valu_file,
                          "kernel": "k_icp_fused (one GICP iteration); the first launch of a scale is k_icp_nn + k_icp_lin",
@@ -542,7 +655,7 @@ def main(argv=None) -> int:
                          "path": {"algorithmic_bytes_per_pair": path_bytes, "achieved": path_gbs, "unit": "GB/s", "frac": path_gbs / HBM_PEAK_GBS,
                                   "what": "SURVEY 8d's byte model of the whole pair (sum over clouds and scales of 12 N0 + 44 D + 36 C, plus 48 C_source (I + 1) per scale) x this run's pairs/s per GPU, "
                                           "over the HBM peak: the kernel figure above is one launch of the hot loop alone"}},
-        }
+        })
         if args.variant == "fgr" and solo[10] > 0:
             line["roofline_fgr"] = fgr_roofline(solo)
         if not args.no_extras and world == 1 and not args.config5 and args.variant == "gicp" and args.radius_rule == "script":

@@ -20,7 +20,7 @@ def _run(args, env=None):
 
 
 def test_bench_json_contract():
-    d = _run(["--steps", "1", "--warmup", "1", "--pairs-per-step", "8"])
+    d = _run(["--steps", "1", "--warmup", "1", "--pairs-per-step", "8", "--full"])
     assert d["n_ranks_seen"] == 1 and d["config"]["distinct_pairs"] == 8 and d["roofline"]["traffic"] is None
     ex = d["extras"]
     for k in ("gicp_af_radius_rule", "fgr_plus_gicp", "config5_2M_points_5_scales_64nn"):
@@ -41,6 +41,30 @@ def test_bench_json_contract():
     assert c["kind"] == "port" and c["unit"] == "pairs/s" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     assert d["value"] > 20 * c["value"]                                                  # north star: >= 20x the CPU path at 1 GPU
     assert d["config"]["err_vs_planted"]["rad"] < 2e-3 and d["config"]["err_vs_planted"]["m"] < 2e-2
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times --steps steps and prints the headline keys only; --dump-outputs writes what its last step returned."""
+    import numpy as np
+    out = tmp_path / "out"
+    d = _run(["--steps", "2", "--warmup", "1", "--pairs-per-step", "8", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in d, k
+    for k in ("roofline", "extras", "cpu_baseline"):
+        assert k not in d, k
+    assert d["steps"] == 2 and d["full"] is False and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 8 / (2 * d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    T = files["transformation.npy"]
+    assert T.shape == (8, 4, 4) and np.allclose(T[:, 3], [0, 0, 0, 1])
+    assert files["scale_transformation.npy"].shape == (8, 3, 4, 4) and np.array_equal(files["scale_transformation.npy"][:, -1], T)
+    assert files["fitness.npy"].shape == (8,) and ((files["fitness.npy"] > 0) & (files["fitness.npy"] <= 1)).all()
+    assert float(files["scale_iterations.npy"].sum(1).mean()) == d["config"]["iterations_per_pair_mean"]
+    c = files["correspondences_sample.npy"]
+    assert c.shape[1] == 3 and len(c) > 0 and set(np.unique(c[:, 0]).astype(int)) <= set(range(8))
+    assert (files["n_correspondences.npy"] > 0).all()
 
 
 def test_bench_two_rank_rehearsal_on_one_gpu():

@@ -11,13 +11,13 @@ export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/profiles_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT" "$ROOT/profiles" "$ROOT/gpurun_out/profiles_export"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 2 --warmup 1 > "$OUT/bench_stats.log" 2> "$OUT/bench_stats.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 2 --warmup 1 > "$OUT/bench_stats.log" 2> "$OUT/bench_stats.err" || exit 1
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${TAG}_bench_kernel_stats.csv"
 python3 "$ROOT/tools/icp_gap_hist.py" "$OUT/stats" "$ROOT/profiles/${TAG}_icp_gaps_inflight.txt" > /dev/null
 python3 "$ROOT/tools/trace_overview.py" "$OUT/stats" 0.4 > "$ROOT/profiles/${TAG}_trace_overview_inflight.txt"
 python3 "$ROOT/tools/trace_bins.py" "$OUT/stats" > "$ROOT/profiles/${TAG}_timeline_bins.txt"
 # config 2's FGR variant (registro_FGR + the same GICP): kernel summary of the same command the bench line of that variant comes from
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/fgr" -o run -- python3 "$ROOT/bench.py" --variant fgr --no-cpu-baseline --steps 1 --warmup 1 --pairs-per-step 16 > "$OUT/bench_fgr.log" 2> "$OUT/bench_fgr.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/fgr" -o run -- python3 "$ROOT/bench.py" --full --variant fgr --no-cpu-baseline --steps 1 --warmup 1 --pairs-per-step 16 > "$OUT/bench_fgr.log" 2> "$OUT/bench_fgr.err" || exit 1
 cp "$(find "$OUT/fgr" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${TAG}_fgr_kernel_stats.csv"
 grep '^{"metric' "$OUT/bench_fgr.log" | tail -1 > "$ROOT/profiles/${TAG}_bench_line_fgr_under_rocprof.json"
 # the script-1 FGR stage on the shipped-size golden NCLT clouds in lockstep FGR groups (24 pairs per group, 4 groups in flight: the default rule)
@@ -30,26 +30,26 @@ cp "$(find "$OUT/gicpn" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${
 grep '^gicp group' "$OUT/gicp_nclt.log" | tail -1 > "$ROOT/profiles/${TAG}_gicp_nclt_groups_line.txt"
 python3 "$ROOT/tools/trace_bins.py" "$OUT/gicpn" > "$ROOT/profiles/${TAG}_gicp_nclt_timeline_bins.txt"
 # one pair at a time: gaps of the iteration chain without other pairs
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/solo" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 8 --inflight 1 --group 1 > "$OUT/bench_solo.log" 2> "$OUT/bench_solo.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/solo" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 8 --inflight 1 --group 1 > "$OUT/bench_solo.log" 2> "$OUT/bench_solo.err" || exit 1
 python3 "$ROOT/tools/icp_gap_hist.py" "$OUT/solo" "$ROOT/profiles/${TAG}_icp_gaps_solo.txt" > /dev/null
 cp "$(find "$OUT/solo" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${TAG}_solo_kernel_stats.csv"
 # config 5 (2M-point clouds, 5 scales, 64-NN normals) and NCLT-size pairs (20k points, the default group rule): kernel summaries of the commands
 # whose bench lines are stored next to them
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5" -o run -- python3 "$ROOT/bench.py" --config5 --pairs-per-step 8 --base-pairs 2 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/bench_c5.log" 2> "$OUT/bench_c5.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5" -o run -- python3 "$ROOT/bench.py" --full --config5 --pairs-per-step 8 --base-pairs 2 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/bench_c5.log" 2> "$OUT/bench_c5.err" || exit 1
 cp "$(find "$OUT/c5" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${TAG}_config5_kernel_stats.csv"
 grep '^{"metric' "$OUT/bench_c5.log" | tail -1 > "$ROOT/profiles/${TAG}_bench_line_config5_under_rocprof.json"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/nclt" -o run -- python3 "$ROOT/bench.py" --points 20000 --pairs-per-step 192 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/bench_nclt.log" 2> "$OUT/bench_nclt.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/nclt" -o run -- python3 "$ROOT/bench.py" --full --points 20000 --pairs-per-step 192 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/bench_nclt.log" 2> "$OUT/bench_nclt.err" || exit 1
 cp "$(find "$OUT/nclt" -name '*kernel_stats.csv' | head -1)" "$ROOT/profiles/${TAG}_nclt_kernel_stats.csv"
 grep '^{"metric' "$OUT/bench_nclt.log" | tail -1 > "$ROOT/profiles/${TAG}_bench_line_nclt_under_rocprof.json"
 for pass in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   d=$OUT/pmc_$(echo $pass | tr ' ' '_')
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 4 --inflight 1 --group 1 > "$d.log" 2> "$d.err" || exit 1
+  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 4 --inflight 1 --group 1 > "$d.log" 2> "$d.err" || exit 1
   echo "pmc pass [$pass] done"
 done
 # the same three passes on the DEFAULT path (lockstep groups of six: k_knn_wave_batchp, k_icp_fused_b<1024>), 12 pairs per step
 for pass in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   d=$OUT/pmcg_$(echo $pass | tr ' ' '_')
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 12 --inflight 2 > "$d.log" 2> "$d.err" || exit 1
+  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 12 --inflight 2 > "$d.log" 2> "$d.err" || exit 1
   echo "pmc pass (groups) [$pass] done"
 done
 python3 - "$OUT" "$ROOT/profiles/${TAG}" <<'PY'
@@ -100,7 +100,7 @@ for r in rows: print(r)
 PY
 # VALU issue per kernel and pair (one pair at a time, kernels serialised by the counter collection): which kernels the chip's VALU time goes to
 d=$OUT/pmc_valu
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 4 --inflight 1 --group 1 > "$d.log" 2> "$d.err" || exit 1
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 4 --inflight 1 --group 1 > "$d.log" 2> "$d.err" || exit 1
 python3 - "$OUT" "$ROOT/profiles/${TAG}" <<'PY'
 import csv, glob, sys, collections
 out, dst = sys.argv[1], sys.argv[2]
@@ -122,7 +122,7 @@ with open(dst + "_pmc_valu_per_pair.csv", "w", newline="") as fo:
 PY
 # the same table for the DEFAULT bench (lockstep groups: wavefront k-NN kernel, by-value fused kernel) -- what the headline number runs
 d=$OUT/pmc_valu_groups
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 1 --warmup 1 > "$d.log" 2> "$d.err" || exit 1
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 > "$d.log" 2> "$d.err" || exit 1
 python3 - "$OUT" "$ROOT/profiles/${TAG}" <<'PY'
 import csv, glob, sys, collections, json
 out, dst = sys.argv[1], sys.argv[2]
