@@ -264,6 +264,12 @@ int pcr_profile_read(pcr_context *ctx, double *out16, int reset);
  * pipeline uses. idx: n x k int32, d2: n x k float32 (device), rows sorted ascending.              */
 int pcr_debug_knn(pcr_context *ctx, const float *xyz, int64_t n, int k, double radius, int32_t *idx, float *d2,
                   int32_t *counts);
+/* the Hybrid(radius, k) neighbour lists of FPFH (k in 1..200, radius > 0) of `count` clouds (xyz[c]: n[c] x 3 float32, device).  count = 1
+ * takes the path of pcr_compute_fpfh_feature, count > 1 (at most 64) the one of the lockstep registro_FGR groups.  idx[c]: n[c] x k int32
+ * (device), row i = caller point i, entries caller indices, -1 = none; cnt[c]: n[c] int32 (device), the entries of the row, or -1 for a row
+ * in the k-best kernel's slot layout (scan all k slots).  A ball of more than k points lists its k nearest by (float64 d^2, caller index). */
+int pcr_debug_radius_lists(pcr_context *ctx, int count, const float *const *xyz, const int64_t *n, int k, double radius,
+                           int32_t *const *idx, int32_t *const *cnt);
 /* one GICP linearisation at pose T: search + A.6 sums. JTJ36, JTr6, stats3 = {count, sum d^2, sum r^2} (host) */
 int pcr_debug_gicp_linearize(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src,
                              const float *tgt_xyz, const float *tgt_normals, int64_t n_tgt, double max_dist,

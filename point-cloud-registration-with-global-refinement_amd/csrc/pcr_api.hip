@@ -380,6 +380,50 @@ extern "C" int pcr_debug_knn(pcr_context *ctx, const float *xyz, int64_t n, int 
     });
 }
 
+// rows of the sorted cloud -> caller order; entries past cnt (an append row) become -1
+__global__ void k_radius_lists_unpermute(const int32_t *si, const int32_t *sc, const uint32_t *perm, int n, int k, int32_t *idx, int32_t *counts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = perm[i];
+    const int c = sc[i];
+    for (int t = 0; t < k; t++) {
+        const int32_t v = (c < 0 || t < c) ? si[(size_t)i * k + t] : -1;
+        idx[(size_t)o * k + t] = v >= 0 ? (int32_t)perm[v] : -1;
+    }
+    counts[o] = c;
+}
+
+extern "C" int pcr_debug_radius_lists(pcr_context *ctx, int count, const float *const *xyz, const int64_t *n, int k, double radius,
+                                      int32_t *const *idx, int32_t *const *cnt) {
+    return pcr_api_call(ctx, [&]() -> int {
+    if (count < 1 || count > 64 || !xyz || !n || !idx || !cnt) return PCR_EINVAL;
+    size_t bytes = 1 << 20;
+    for (int c = 0; c < count; c++) {
+        if (n[c] <= 0 || !xyz[c] || !idx[c] || !cnt[c]) return PCR_EINVAL;
+        bytes += pcr_scratch_bytes_for(n[c]) + (size_t)n[c] * (size_t)(k > 0 ? k : 1) * 4 + (size_t)n[c] * 64;
+    }
+    PCR_TRY(pcr_arena_reserve(ctx, bytes));
+    std::vector<DevCloud> cs((size_t)count); std::vector<uint32_t *> perm((size_t)count, nullptr);
+    if (count == 1) {                                   // the compute_fpfh_feature path
+        PCR_TRY(pcr_import_cloud(ctx, xyz[0], nullptr, n[0], &cs[0], &perm[0], false));
+    } else {                                            // the lockstep FGR groups' path
+        for (int c = 0; c < count; c++) PCR_TRY(pcr_alloc_cloud(ctx, &cs[c], (int)n[c], false, true));
+        PCR_TRY(pcr_import_clouds_batch(ctx, count, xyz, nullptr, n, cs.data(), perm.data()));
+    }
+    std::vector<const DevCloud *> cp((size_t)count); std::vector<const uint32_t *> pp((size_t)count);
+    std::vector<int32_t *> si((size_t)count), sc((size_t)count);
+    for (int c = 0; c < count; c++) {
+        cp[c] = &cs[c]; pp[c] = perm[c];
+        si[c] = arena<int32_t>(ctx, (size_t)n[c] * (size_t)(k > 0 ? k : 1)); sc[c] = arena<int32_t>(ctx, n[c]);
+        if (!si[c] || !sc[c]) return PCR_ENOMEM;
+    }
+    PCR_TRY(pcr_dev_radius_lists_batch(ctx, cp.data(), pp.data(), count, k, radius, si.data(), sc.data()));
+    for (int c = 0; c < count; c++)
+        PCR_LAUNCH(ctx, k_radius_lists_unpermute, dim3((unsigned)((n[c] + 255) / 256)), dim3(256), 0, ctx->stream, si[c], sc[c], perm[c], (int)n[c], k, idx[c], cnt[c]);
+    return PCR_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------------- registration API
 static int check_T(pcr_context *ctx, const double *T) {
     if (!T) return PCR_EINVAL;

@@ -1565,15 +1565,18 @@ struct RadListArgs {
     int32_t *idx; int32_t *cnt;                  // rows of k int32 per query; entries per row (-1: row in the k-best kernel's slot layout, scan all k)
     int *over_list, *over_count;                 // first queries of the 8-query pieces left to the k-best kernel
     int select;                                  // 1: overfull balls are finished here (threshold selection); 0: every overfull piece goes to the k-best kernel
+    const uint32_t *perm;                        // sorted -> caller index: the second key of the order at the k-th place
 };
 // Round 5: an OVERFULL ball (23 % of the balls of a 175k-point cloud at r = 1 m, max_nn = 200) no longer goes through the k-best kernel's
 // 25-slot sorted insertion.  FPFH needs the SET of the k nearest, not their order: the first walk also counts the in-ball points of each
 // query in RL_BINS bins of d^2 (LDS), the bin B in which the count passes k is read off, and a second walk -- bounded by that bin's upper edge --
 // appends every point of the bins below B and collects the points of bin B (a dozen) into LDS, of which the k - below smallest complete the
 // row -- smallest by (float64 d^2, caller index), the order of the reference's k-d tree (oracle/kdtree.c cmp_item), so that a tie at the k-th
-// place falls as it does there (the k-best kernel keeps the first one its walk meets).  Both walks test the same float32 expressions, so they see the same points.  A boundary bin of more than RL_EDGE points
-// (many equal distances) sends the piece to the k-best kernel as before.
-#define RL_BINS 128            // (two 16-bit counters per LDS word: a ball holds far fewer than 65 536 points)
+// place falls as it does there; the caller index comes from RadListArgs::perm (the points' w is 0).  Both walks test the same float32
+// expressions, so they see the same points.  A boundary bin of more than RL_EDGE points (many equal distances), or a ball of more than 65 535
+// points (a 16-bit bin counter may have wrapped into its neighbour), sends the piece to the k-best kernel, and k_radius_fix below then decides
+// the k-th place of its rows by the same (float64 d^2, caller index) rule: the lists are the same set on every path.
+#define RL_BINS 128            // (two 16-bit counters per LDS word; a ball of more than 0xffff points is the k-best kernel's)
 #define RL_EDGE 20
 // squared distance as the reference's k-d tree forms it (float64 differences of the float32 coordinates, products and sums rounded one by one)
 __device__ static inline double pcr_d2_f64_unfused(const float4 q, const float4 p) {
@@ -1632,16 +1635,17 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
     if (over && select) {
         // the bin in which the count passes k (octet-uniform: every lane reads the octet's 64 counters)
         int B = 0, below = 0;
-        if (mine) {
+        const bool wide = mine && cnt > 0xffff;                            // a 16-bit bin counter may have wrapped: the piece is the k-best kernel's
+        if (mine && !wide) {
             for (int b = 0; b < RL_BINS; b++) { const int h = (int)((hist[ob][b >> 1] >> (16 * (b & 1))) & 0xffffu); if (below + h >= a.k) { B = b; break; } below += h; }
         }
-        const float bound2 = mine ? fminf(a.r2f, (float)(B + 1) / bin_scale * 1.0001f) : -1.0f;
+        const float bound2 = (mine && !wide) ? fminf(a.r2f, (float)(B + 1) / bin_scale * 1.0001f) : -1.0f;
         int cnt2 = 0;
         auto visit2 = [&](int first, int count) {
             for (int base = first; base < first + count; base += OCT) {
                 const int idx = base + ol;
                 bool lo = false, eq = false; float d2 = 0.0f;
-                if (mine && idx < first + count) {
+                if (mine && !wide && idx < first + count) {
                     const float4 p = a.t.pts[idx];
                     d2 = pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z);
                     if (d2 < a.r2f) { int b = (int)(d2 * bin_scale); b = b < RL_BINS ? b : RL_BINS - 1; lo = b < B; eq = b == B; }
@@ -1654,15 +1658,15 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
                     const int e = atomicAdd(&nedge[ob], 1);
                     if (e < RL_EDGE) {
                         const float4 p = a.t.pts[idx];
-                        edge_d2[ob][e] = pcr_d2_f64_unfused(q, p); edge_id[ob][e] = make_int2(__float_as_int(p.w), idx);
+                        edge_d2[ob][e] = pcr_d2_f64_unfused(q, p); edge_id[ob][e] = make_int2((int)a.perm[idx], idx);
                     }
                 }
             }
         };
-        oct_search_group(a.t, m, gstk[threadIdx.x >> 6], mine, leaf0, q.x, q.y, q.z, [&]() { return bound2; }, visit2,
+        oct_search_group(a.t, m, gstk[threadIdx.x >> 6], mine && !wide, leaf0, q.x, q.y, q.z, [&]() { return bound2; }, visit2,
                          [](int, int) { return false; }, ol, nullptr);
         const int ne = mine ? nedge[ob] : 0;
-        const bool spill = ne > RL_EDGE;
+        const bool spill = wide || ne > RL_EDGE;
         over = __ballot(spill) != 0ull;                                    // such a piece is the k-best kernel's
         if (!over && mine) {
             const int need = a.k - below;                                  // 1 <= need <= ne
@@ -1683,9 +1687,162 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
 }
 __global__ void __launch_bounds__(KNN_BS) k_radius_list(RadListArgs a) { d_radius_list(a); }
 __global__ void __launch_bounds__(KNN_BS) k_radius_list_g(const RadListArgs *a) { d_radius_list(a[blockIdx.y]); }
-// `count` clouds in one launch pair: the append kernel, then the k-best list form over the listed pieces.  Rows idx[c]: cap x k int32,
-// cnt[c]: cap int32.  (Hybrid search only: radius > 0.)
-int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, int count, int k, double radius, int32_t *const *idx, int32_t *const *cnt) {
+
+// The k-th place of the pieces the k-best kernel listed (spilled boundary bins, the 16-bit counter guard, every overfull piece under select = 0).
+// That kernel keeps the first of equal float32 distances its walk meets: right for SOR and normals, which never look at which one, but FPFH's
+// rows must be the reference's set, ranked by (float64 d^2, caller index).  For a row it filled (k entries), D = its largest float32 d^2:
+// every point below the band [D (1 - 2^-18), D (1 + 2^-18)] belongs to the reference's k nearest and every in-ball point above it does not
+// (the float32 and float64 d^2 of a point differ by far less than 2^-20 relative), so only the band's points need ranking.  The band can be
+// any size (300 copies of one point, a lattice shell), so it is not buffered: the rank is found digit by digit, eight bits of the key
+// (float64 d^2 bits, then caller index) per walk, from counts in LDS; a last walk writes the row.  Rows with fewer than k entries (balls of
+// at most k points in such a piece) are complete already.  Off the hot path: spilled pieces are rare on the scans.
+#define RL_FIX_BAND (1.0f / 262144.0f)
+__device__ static inline unsigned long long rl_octet_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < OCT; o <<= 1) { const unsigned long long w = __shfl_xor(v, o, OCT); v = w < v ? w : v; }
+    return v;
+}
+__device__ static inline unsigned long long rl_octet_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < OCT; o <<= 1) { const unsigned long long w = __shfl_xor(v, o, OCT); v = w > v ? w : v; }
+    return v;
+}
+__device__ static inline void d_radius_fix(const RadListArgs &a) {
+    constexpr int OPB = KNN_BS / OCT;
+    __shared__ OctMeta m;
+    __shared__ OctGroupStack gstk[KNN_BS / 64];
+    __shared__ unsigned dig[OPB][256];
+    const int n_items = *a.over_count;
+    if ((int)blockIdx.x * (KNN_BS / 64) >= n_items) return;
+    if (threadIdx.x == 0) m = *a.t.meta;
+    __syncthreads();
+    const int n = m.n;
+    const int lane = threadIdx.x & 63, oct = lane >> 3, ol = lane & 7, ob = threadIdx.x >> 3;
+    for (int it = blockIdx.x * (KNN_BS / 64) + (threadIdx.x >> 6); it < n_items; it += gridDim.x * (KNN_BS / 64)) {
+        const int g0 = a.over_list[it];
+        const int qi = g0 + oct;
+        const bool live = qi < n;
+        const float4 q = a.t.pts[live ? qi : 0];
+        int32_t *const row = a.idx + (size_t)(live ? qi : 0) * a.k;
+        // the row as the k-best kernel left it: entries and the largest float32 distance
+        float dmax = 0.0f; int filled = 0;
+        for (int s = ol; s < a.k; s += OCT) {
+            const int j = live ? row[s] : -1;
+            if (j >= 0) { const float4 p = a.t.pts[j]; dmax = fmaxf(dmax, pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z)); filled++; }
+        }
+        dmax = pcr_octet_max(dmax); filled = pcr_octet_sum_i(filled);
+        bool fix = live && filled == a.k;                                   // octet-uniform
+        if (__ballot(fix) == 0ull) continue;
+        const float lo = dmax * (1.0f - RL_FIX_BAND), hi = fminf(dmax * (1.0f + RL_FIX_BAND), a.r2f);
+        const float wb = fix ? hi * 1.0001f : -1.0f;
+        const int leaf0 = a.t.leaf_of[g0 < n ? g0 : 0];
+        // scan(fn): fn(d2, morton index) for every point of this query's walk inside the band's bound (all lanes of the octet, any order)
+        auto scan = [&](bool act, auto fn) {
+            auto visit = [&](int first, int count) {
+                for (int base = first; base < first + count; base += OCT) {
+                    const int idx = base + ol;
+                    if (act && idx < first + count) {
+                        const float4 p = a.t.pts[idx];
+                        const float d2 = pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z);
+                        if (d2 < a.r2f && d2 <= hi) fn(d2, idx, p);
+                    }
+                }
+            };
+            oct_search_group(a.t, m, gstk[threadIdx.x >> 6], act, leaf0, q.x, q.y, q.z, [&]() { return act ? wb : -1.0f; }, visit,
+                             [](int, int) { return false; }, ol, nullptr);
+        };
+        auto key_of = [&](const float4 &p) { return (unsigned long long)__double_as_longlong(pcr_d2_f64_unfused(q, p)); };
+        // walk 1: points below the band, points in it, and the range of their float64 keys
+        int below = 0, nb = 0;
+        unsigned long long kmin = ~0ull, kmax = 0ull;
+        scan(fix, [&](float d2, int, const float4 &p) {
+            if (d2 < lo) { below++; return; }
+            nb++; const unsigned long long kk = key_of(p); kmin = kk < kmin ? kk : kmin; kmax = kk > kmax ? kk : kmax;
+        });
+        below = pcr_octet_sum_i(below); nb = pcr_octet_sum_i(nb); kmin = rl_octet_min_u64(kmin); kmax = rl_octet_max_u64(kmax);
+        int need = a.k - below;                                             // 1 <= need <= nb (D is the k-th smallest float32 d^2)
+        fix = fix && need >= 1 && need <= nb;
+        // the need-th smallest (float64 key, caller index) of the band, 8 bits per walk: first the key, then the index among its equals
+        const bool all_band = fix && need == nb;
+        unsigned long long kpre = kmin; int r = need, ties = nb;          // key prefix found so far; rank left inside it; points with that prefix
+        const int ktop = (kmin == kmax) ? 0 : 64 - __builtin_clzll(kmin ^ kmax);
+        if (fix && !all_band && ktop > 0) kpre = (ktop >= 64) ? 0ull : (kmin >> ktop) << ktop;
+        for (int sh = 56; sh >= 0; sh -= 8) {
+            const bool act = fix && !all_band && sh < ktop;
+            if (__ballot(act) == 0ull) continue;
+            for (int b = ol; b < 256; b += OCT) dig[ob][b] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            const unsigned long long hm = (sh + 8 >= 64) ? 0ull : ~0ull << (sh + 8);
+            scan(act, [&](float d2, int, const float4 &p) {
+                if (d2 < lo) return;
+                const unsigned long long kk = key_of(p);
+                if ((kk & hm) == (kpre & hm)) atomicAdd(&dig[ob][(kk >> sh) & 255u], 1u);
+            });
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (act) {
+                int cum = 0, b = 0;
+                for (; b < 255; b++) { const int h = (int)dig[ob][b]; if (cum + h >= r) break; cum += h; }
+                r -= cum; ties = (int)dig[ob][b];
+                kpre = (kpre & hm) | ((unsigned long long)b << sh);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // kpre is now the key of the need-th point; r of the `ties` band points with that key are taken, lowest caller index first
+        const bool all_ties = all_band || r >= ties;
+        unsigned long long ipre = 0ull; int r2 = r;
+        const int itop = 64 - __builtin_clzll((unsigned long long)(n > 1 ? n - 1 : 1));
+        for (int sh = 24; sh >= 0; sh -= 8) {
+            const bool act = fix && !all_ties && sh < itop;
+            if (__ballot(act) == 0ull) continue;
+            for (int b = ol; b < 256; b += OCT) dig[ob][b] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            const unsigned long long hm = ~0ull << (sh + 8);
+            scan(act, [&](float d2, int idx, const float4 &p) {
+                if (d2 < lo || key_of(p) != kpre) return;
+                const unsigned long long ci = a.perm[idx];
+                if ((ci & hm) == (ipre & hm)) atomicAdd(&dig[ob][(ci >> sh) & 255u], 1u);
+            });
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (act) {
+                int cum = 0, b = 0;
+                for (; b < 255; b++) { const int h = (int)dig[ob][b]; if (cum + h >= r2) break; cum += h; }
+                r2 -= cum;
+                ipre = (ipre & hm) | ((unsigned long long)b << sh);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // last walk: the row, in walk order (k entries: the readers' slot scan sees the same set)
+        int cnt = 0;
+        auto write = [&](int first, int count) {
+            for (int base = first; base < first + count; base += OCT) {
+                const int idx = base + ol;
+                bool take = false;
+                if (fix && idx < first + count) {
+                    const float4 p = a.t.pts[idx];
+                    const float d2 = pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z);
+                    if (d2 < a.r2f && d2 <= hi) {
+                        if (d2 < lo || all_band) take = true;
+                        else {
+                            const unsigned long long kk = key_of(p);
+                            take = kk < kpre || (kk == kpre && (all_ties || (unsigned long long)a.perm[idx] <= ipre));
+                        }
+                    }
+                }
+                const unsigned mask = (unsigned)(__ballot(take) >> (oct * 8)) & 0xffu;
+                const int pos = cnt + __builtin_popcount(mask & ((1u << ol) - 1u));
+                if (take && pos < a.k) row[pos] = idx;
+                cnt += __builtin_popcount(mask);
+            }
+        };
+        oct_search_group(a.t, m, gstk[threadIdx.x >> 6], fix, leaf0, q.x, q.y, q.z, [&]() { return wb; }, write,
+                         [](int, int) { return false; }, ol, nullptr);
+    }
+}
+__global__ void __launch_bounds__(KNN_BS) k_radius_fix(RadListArgs a) { d_radius_fix(a); }
+__global__ void __launch_bounds__(KNN_BS) k_radius_fix_g(const RadListArgs *a) { d_radius_fix(a[blockIdx.y]); }
+// `count` clouds in one launch triple: the append kernel, the k-best list form over the listed pieces, the k-th place of those pieces.  Rows
+// idx[c]: cap x k int32, cnt[c]: cap int32; perms[c]: sorted -> caller index.  (Hybrid search only: radius > 0.)
+int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, const uint32_t *const *perms, int count, int k, double radius, int32_t *const *idx, int32_t *const *cnt) {
     if (count < 1) return PCR_OK;
     if (count > PCR_MAX_GROUP_BATCH) { ctx->err = "radius list batch size"; return PCR_EINVAL; }
     if (!(radius > 0) || k < 1 || k > 200) { ctx->err = "radius lists: radius <= 0 or k outside 1..200"; return PCR_EINVAL; }
@@ -1699,7 +1856,7 @@ int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, int 
         RadListArgs r;
         r.t = oct_view(cs[c]); r.n_ptr = cs[c]->n; r.r2f = (float)(radius * radius); r.k = k; r.idx = idx[c]; r.cnt = cnt[c];
         r.over_list = arena<int>(ctx, (size_t)cs[c]->cap / OCT + 1); r.over_count = counts + c;
-        r.select = pcr_options().radius_list_select.load(std::memory_order_relaxed);
+        r.select = pcr_options().radius_list_select.load(std::memory_order_relaxed); r.perm = perms[c];
         if (!r.over_list) return PCR_ENOMEM;
         ra.push_back(r);
         KnnArgs a; std::memset(&a, 0, sizeof a);                        // the k-best search of pcr_dev_knn_debug, over the listed pieces only
@@ -1713,19 +1870,24 @@ int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, int 
     }
     const int m = (int)ra.size();
     if (m == 0) return PCR_OK;
+    const RadListArgs *d = nullptr;
     if (m == 1) {
         PCR_LAUNCH(ctx, k_radius_list, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS)), dim3(KNN_BS), 0, ctx->stream, ra[0]);
     } else {
-        const RadListArgs *d = pcr_desc_upload(ctx, ra.data(), m);
+        d = pcr_desc_upload(ctx, ra.data(), m);
         if (!d) return PCR_ENOMEM;
         PCR_LAUNCH(ctx, k_radius_list_g, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS), m), dim3(KNN_BS), 0, ctx->stream, d);
     }
     // the overfull pieces: as many wavefronts as a dense cloud may list (every piece), striding
     int lg = mc / (OCT * (KNN_BS / 64) * 4); lg = lg < 8 ? 8 : (lg > 2048 ? 2048 : lg);
     const dim3 grid(lg, m), block(KNN_BS);
-    if (k <= 32) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 4>), (k_knn_list_batchp<KNN_MODE_DEBUG, 4>), ka.data(), m, grid, block);
-    if (k <= 64) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 8>), (k_knn_list_batchp<KNN_MODE_DEBUG, 8>), ka.data(), m, grid, block);
-    return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 25>), (k_knn_list_batchp<KNN_MODE_DEBUG, 25>), ka.data(), m, grid, block);
+    if (k <= 32) PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 4>), (k_knn_list_batchp<KNN_MODE_DEBUG, 4>), ka.data(), m, grid, block));
+    else if (k <= 64) PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 8>), (k_knn_list_batchp<KNN_MODE_DEBUG, 8>), ka.data(), m, grid, block));
+    else PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 25>), (k_knn_list_batchp<KNN_MODE_DEBUG, 25>), ka.data(), m, grid, block));
+    // ... and their k-th place by (float64 d^2, caller index)
+    if (m == 1) PCR_LAUNCH(ctx, k_radius_fix, grid, block, 0, ctx->stream, ra[0]);
+    else PCR_LAUNCH(ctx, k_radius_fix_g, grid, block, 0, ctx->stream, d);
+    return PCR_OK;
 }
 
 // ============================================= normals of the CLEANED cloud from the SOR pass's k-best lists (K5')

@@ -316,7 +316,7 @@ static int fpfh_of_cloud(pcr_context *ctx, const DevCloud &c, const uint32_t *pe
         ncnt = arena<int32_t>(ctx, n);
         if (!ncnt) return PCR_ENOMEM;
         const DevCloud *cp = &c;
-        PCR_TRY(pcr_dev_radius_lists_batch(ctx, &cp, 1, knn, radius, &nbr, &ncnt));
+        PCR_TRY(pcr_dev_radius_lists_batch(ctx, &cp, &perm, 1, knn, radius, &nbr, &ncnt));
     } else {
         float *nd2 = arena<float>(ctx, (size_t)n * knn);
         if (!nd2) return PCR_ENOMEM;
@@ -1481,7 +1481,8 @@ int pcr_registro_fgr_group(pcr_context *ctx, pcr_fgr_group_pair *q, int G) {
             }
             nmax = n[k] > nmax ? n[k] : nmax;
         }
-        PCR_TRY(pcr_dev_radius_lists_batch(ctx, cp.data(), C, p0.feature_max_nn, p0.feature_radius, nbr.data(), ncnt.data()));
+        std::vector<const uint32_t *> cperm(perm.begin(), perm.end());
+        PCR_TRY(pcr_dev_radius_lists_batch(ctx, cp.data(), cperm.data(), C, p0.feature_max_nn, p0.feature_radius, nbr.data(), ncnt.data()));
         const FpfhArgs *dfa = pcr_desc_upload(ctx, fa.data(), C);
         if (!dfa) return PCR_ENOMEM;
         const dim3 grid((unsigned)(((size_t)nmax * OCT + FB - 1) / FB), C);
