@@ -287,15 +287,13 @@ int pcr_debug_feature_nn(pcr_context *ctx, const float *f0, int64_t n0, const fl
  * 1 the one-query-per-lane kernel for every search that fits it; "knnw_budget": candidate batches a wavefront of that kernel takes before
  * it hands its queries over; "fence_prep": measurement only -- with profiling on, every scale's GICP loop of the pipelined multiscale path
  * (clouds the batched preprocessing declines: config 5) starts after ALL preprocessing enqueued so far has finished, so that HIP-event times
- * per launch are the iteration kernels' own; "icp_phase", "icp_verify", "debug_stamps", "debug_visits": diagnostics of the GICP loop and the searches
- * (phase stamps of the fused iteration kernel, re-search of certified queries, per-call stamp print-outs, visit counts instead of results).
+ * per launch are the iteration kernels' own; "icp_verify": diagnostics of the GICP loop (re-search of certified queries).
  * Switches between two forms of the FGR half that give the same bits (tests compare them): "spfh_float64" (0: pair features of FPFH decided in
  * float where float can and in float64 otherwise, for clouds from 60 000 points; 1: all in float64; 2: both, a disagreement is an error; 4: the
  * float pass whatever the size; 3: as 4 with a 16-entry queue, the overflow path), "radius_list_select" (1: overfull Hybrid(r, max_nn) balls finished by threshold selection; 0: by the k-best kernel),
  * "featnn_mutual" (1: the second direction of the feature search inside FGR runs only for the rows the first direction points at, under the
  * bound it found; 0: both directions in full), "icp_scales" (1: in lockstep groups of small clouds every pair goes through its scales by itself;
- * 0: one lockstep loop per scale).  "plan_stagger_us", "plan_prefetch": measurement only (delayed worker starts; twice the workers
- * behind a gate in front of a group's chip-filling part) -- both cost throughput, README.md quotes the numbers.  "arena_poison": the scratch arena is filled with this byte before every call (a read of
+ * 0: one lockstep loop per scale).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
  * scratch nobody wrote then follows the pattern).  Returns PCR_EINVAL for an unknown name. */
 int pcr_set_option(const char *name, long long value);
 /* Process-wide event counters (value, or -1 for an unknown name; reset != 0 clears it): how often a lockstep registro_FGR group fell back to

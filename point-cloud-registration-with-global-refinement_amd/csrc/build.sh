@@ -14,7 +14,7 @@ for f in pcr_sort pcr_cloud pcr_gicp pcr_featnn pcr_fgr pcr_api; do
     echo "hipcc $f.hip"
     # pcr_fgr: no SLP vectorisation = no packed-FP32 instructions.  On MI355X a v_pk_mul_f32 that reads the result of a v_rsq_f32 issued ten
     # instructions earlier took a STALE value in one of its halves when other kernels kept the transcendental pipe busy (measured:
-    # tools/lab/fpfh_race.py); tools/pk_trans_scan.py (a CPU test) checks that no unit holds such a pair.
+    # DESIGN.md section 7); tools/pk_trans_scan.py (a CPU test) checks that no unit holds such a pair.
     extra=""; [ $f = pcr_fgr ] && extra="-fno-slp-vectorize"
     hipcc $FLAGS $extra -c $f.hip -o $f.o
   fi

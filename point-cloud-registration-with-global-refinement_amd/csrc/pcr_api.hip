@@ -7,7 +7,6 @@
 #include <atomic>
 #include <mutex>
 #include <thread>
-#include <chrono>
 #include <vector>
 #include "pcr_octree.h"
 
@@ -21,15 +20,10 @@ PcrOptions &pcr_options() {
         if (const char *e = getenv("PCR_KNN_WAVE")) o.knn_wave = atoi(e);
         if (const char *e = getenv("PCR_KNNW_BUDGET")) o.knnw_budget = atoi(e);
         if (const char *e = getenv("PCR_FENCE_PREP")) o.fence_prep = atoi(e);
-        if (const char *e = getenv("PCR_ICP_PHASE")) o.icp_phase = atoi(e);
         if (getenv("PCR_ICP_VERIFY")) o.icp_verify = 1;
-        if (getenv("PCR_DEBUG_STAMPS")) o.debug_stamps = 1;
-        if (const char *e = getenv("PCR_DEBUG_VISITS")) o.debug_visits = atoi(e) ? atoi(e) : 1;
         if (const char *e = getenv("PCR_SPFH_FLOAT64")) o.spfh_float64 = atoi(e);
         if (const char *e = getenv("PCR_RADIUS_LIST_SELECT")) o.radius_list_select = atoi(e);
         if (const char *e = getenv("PCR_FEATNN_MUTUAL")) o.featnn_mutual = atoi(e);
-        if (const char *e = getenv("PCR_PLAN_STAGGER_US")) o.plan_stagger_us = atoi(e);
-        if (const char *e = getenv("PCR_PLAN_PREFETCH")) o.plan_prefetch = atoi(e);
         if (const char *e = getenv("PCR_ICP_SCALES")) o.icp_scales = atoi(e);
     });
     return o;
@@ -49,16 +43,11 @@ extern "C" int pcr_set_option(const char *name, long long value) {
     if (!strcmp(name, "knn_wave")) { o.knn_wave = (int)value; return PCR_OK; }
     if (!strcmp(name, "knnw_budget")) { o.knnw_budget = (int)value; return PCR_OK; }
     if (!strcmp(name, "fence_prep")) { o.fence_prep = (int)value; return PCR_OK; }
-    if (!strcmp(name, "icp_phase")) { o.icp_phase = (int)value; return PCR_OK; }
     if (!strcmp(name, "icp_verify")) { o.icp_verify = (int)value; return PCR_OK; }
-    if (!strcmp(name, "debug_stamps")) { o.debug_stamps = (int)value; return PCR_OK; }
-    if (!strcmp(name, "debug_visits")) { o.debug_visits = (int)value; return PCR_OK; }
     if (!strcmp(name, "spfh_float64")) { o.spfh_float64 = (int)value; return PCR_OK; }
     if (!strcmp(name, "radius_list_select")) { o.radius_list_select = (int)value; return PCR_OK; }
     if (!strcmp(name, "arena_poison")) { o.arena_poison = (int)value; return PCR_OK; }
     if (!strcmp(name, "featnn_mutual")) { o.featnn_mutual = (int)value; return PCR_OK; }
-    if (!strcmp(name, "plan_stagger_us")) { o.plan_stagger_us = (int)value; return PCR_OK; }
-    if (!strcmp(name, "plan_prefetch")) { o.plan_prefetch = (int)value; return PCR_OK; }
     if (!strcmp(name, "icp_scales")) { o.icp_scales = (int)value; return PCR_OK; }
     return PCR_EINVAL;
 }
@@ -358,9 +347,9 @@ __global__ void k_knn_unpermute(const int32_t *si, const float *sd, const int32_
     }
     if (counts) counts[o] = sc[i];
 }
-__global__ void k_match_unpermute(const int32_t *m, const uint32_t *sp, const uint32_t *tp, int n, int32_t *out, int raw) {
+__global__ void k_match_unpermute(const int32_t *m, const uint32_t *sp, const uint32_t *tp, int n, int32_t *out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[sp[i]] = raw ? m[i] : (m[i] >= 0 ? (int32_t)tp[m[i]] : -1);
+    if (i < n) out[sp[i]] = m[i] >= 0 ? (int32_t)tp[m[i]] : -1;
 }
 
 extern "C" int pcr_debug_knn(pcr_context *ctx, const float *xyz, int64_t n, int k, double radius, int32_t *idx, float *d2, int32_t *counts) {
@@ -505,7 +494,7 @@ extern "C" int pcr_debug_gicp_linearize(pcr_context *ctx, const float *src_xyz, 
     if (!match) return PCR_ENOMEM;
     PCR_TRY(pcr_dev_linearize_once(ctx, &s, &t, max_dist, T, params, JTJ36, JTr6, stats3, match));
     if (match_out) {
-        PCR_LAUNCH(ctx, k_match_unpermute, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, ctx->stream, match, sperm, tperm, (int)n_src, match_out, pcr_options().debug_visits.load(std::memory_order_relaxed) ? 1 : 0);
+        PCR_LAUNCH(ctx, k_match_unpermute, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, ctx->stream, match, sperm, tperm, (int)n_src, match_out);
         PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
     return PCR_OK;
@@ -555,7 +544,6 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
                               int64_t n_tgt, const double *voxels, const double *dists, int n_scales, int sor_k, double sor_std, int normal_k, const double *init_T,
                               const pcr_gicp_params *params, pcr_scale_record *records, int32_t *correspondences, const double *bs, const double *bt) {
     if (n_scales < 2 || n_scales > 8 || sor_k > 32 || normal_k > 32 || n_src <= 0 || n_tgt <= 0) return 1;
-    const double t_entry = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     auto lane_bytes = [&](int64_t n) { return (size_t)n_scales * ((size_t)n + 512) * 1100 + pcr_sort_temp_bytes((size_t)n * n_scales) + (size_t)n * n_scales * 40 + (32u << 20); };
     const size_t blk_s = lane_bytes(n_src), blk_t = lane_bytes(n_tgt);
     PCR_TRY(pcr_arena_reserve(ctx, blk_s + blk_t + pcr_scratch_bytes_for(n_src) + (1u << 20)));
@@ -615,14 +603,6 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
     if (declined) { ctx->err = "voxel pass accepted one cloud and declined the other"; return PCR_EINVAL; }      // same scales, same key width: cannot happen
     PCR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane_ev[0], 0));
     PCR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane_ev[1], 0));
-    // diagnostics (PCR_PAIR_TIMELINE=1, with profiling on): host-clock breakdown of a pair: enqueue of the preprocessing, wait for it,
-    // the GICP loops of the scales (out16[11..14], seconds; [15] pairs).  The extra synchronisation serialises prep and loop.
-    static const bool timeline = getenv("PCR_PAIR_TIMELINE") != nullptr;
-    const bool tl = timeline && ctx->profiling;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_enq = now();
-    if (tl) { PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); }
-    const double t_prep = now();
     double T[16];
     memcpy(T, init_T, sizeof T);
     int32_t *match = arena<int32_t>(ctx, n_src);
@@ -631,7 +611,6 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
         PCR_TRY(pcr_dev_gicp(ctx, &clean[0][s], &clean[1][s], dists[s], T, params, &records[s].icp, match));
         memcpy(T, records[s].icp.transformation, sizeof T);
     }
-    if (tl) { ctx->prof[11] += t_enq - t_entry; ctx->prof[12] += t_prep - t_enq; ctx->prof[13] += now() - t_prep; ctx->prof[15] += 1.0; }
     if (correspondences) {
         PCR_TRY(pcr_dev_compact_matches(ctx, match, clean[0][n_scales - 1].n, clean[0][n_scales - 1].cap, nullptr, nullptr, correspondences, nullptr));      // (the count is the result's n_correspondences: no read-back)
     }
@@ -703,7 +682,6 @@ static int multiscale_group(pcr_context *ctx, pcr_pair_ex *const *px, int G, con
         for (size_t k = 0; k < vp.size(); k++) vp[k] = &vox[k];
         PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp.data(), (int)vp.size()));
     }
-    PcrGateToken heavy_token(ctx->heavy_gate);         // (held to the end of the group: the function returns after its last read-back)
     {   // the filter chains of ALL clouds and scales of the group as one batch (round 5: sources and targets were two batches -- twice the launches, and
         // twice the tails of the list-driven searches); incomplete normal lists are searched over the voxel trees (piece lists of the filter pass)
         std::vector<const DevCloud *> ins; std::vector<DevCloud *> outs; std::vector<const float4 *> pr; std::vector<uint8_t *> td; std::vector<int *> tc, ci, ck;
@@ -1008,27 +986,19 @@ extern "C" int pcr_register_pairs_plan(int device, pcr_pair_ex *pairs, int n_pai
     const int group = plan->stage == PCR_STAGE_FGR ? fgr_group
                     : (((plan->stage == PCR_STAGE_GICP || plan->stage == PCR_STAGE_FGR_GICP) && plan->group > 1) ? (plan->group > 24 ? 24 : plan->group)      /* (32 in lockstep were measured at 310 pairs/s against 1150 with 24 on NCLT-size pairs: capped) */ : 1);
     const int units = (n_pairs + group - 1) / group;
-    int workers = inflight < 1 ? 1 : (inflight > units ? units : (inflight > 16 ? 16 : inflight));
-    // (option "plan_prefetch": twice the workers, of which `workers` at a time are past the gate of multiscale_group)
-    PcrGate gate;
-    const bool prefetch = pcr_options().plan_prefetch.load(std::memory_order_relaxed) != 0 && plan->stage == PCR_STAGE_GICP && group > 1 && units > workers;
-    if (prefetch) { gate.free_slots = workers; workers = 2 * workers > units ? units : 2 * workers; if (workers > 16) workers = 16; }
+    const int workers = inflight < 1 ? 1 : (inflight > units ? units : (inflight > 16 ? 16 : inflight));
     // the workers wait for everything already enqueued on `after_stream` (NULL = the legacy default stream, which is what torch's
     // default stream is): the producers of the clouds, normals and initial poses
     hipEvent_t ready = nullptr;
     if (hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess) return PCR_EHIP;
     if (hipEventRecord(ready, (hipStream_t)after_stream) != hipSuccess) { (void)hipEventDestroy(ready); return PCR_EHIP; }
     for (int i = 0; i < n_pairs; i++) { pairs[i].base.status = PCR_EHIP; snprintf(pairs[i].base.error, sizeof pairs[i].base.error, "not processed (no worker context)"); }
-    std::atomic<int> next(0), failed(0), started(0);
-    const int stagger_us = pcr_options().plan_stagger_us.load(std::memory_order_relaxed);      // measurement only: worker w starts w x this later
+    std::atomic<int> next(0), failed(0);
     auto work = [&]() {
-        const int wid = started.fetch_add(1);
-        if (stagger_us > 0 && wid > 0) std::this_thread::sleep_for(std::chrono::microseconds((long long)wid * stagger_us));
         (void)hipSetDevice(device);
         pcr_context *ctx = pool_take(device);
         if (!ctx) { failed++; return; }
         use_private_stream(ctx);
-        ctx->heavy_gate = prefetch ? &gate : nullptr;
         if (ensure_stream(ctx) == PCR_OK) (void)hipStreamWaitEvent(ctx->stream, ready, 0);
         const bool gicp_stage = plan->stage == PCR_STAGE_GICP || plan->stage == PCR_STAGE_FGR_GICP;
         auto group_unit = [&](int i, int cnt) -> int {
@@ -1190,7 +1160,6 @@ extern "C" int pcr_register_pairs_plan(int device, pcr_pair_ex *pairs, int n_pai
         }
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
         ctx->group_forms = false;
-        ctx->heavy_gate = nullptr;
         pool_give(device, ctx);
     };
     std::vector<std::thread> threads;

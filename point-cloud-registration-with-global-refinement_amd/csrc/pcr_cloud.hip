@@ -501,7 +501,7 @@ int pcr_dev_sort_cloud(pcr_context *ctx, const float *xyz, int64_t n, const doub
     if (!k0 || !k1 || !v0 || !temp) return PCR_ENOMEM;
     // ONE lattice unit for the three axes (the largest extent over 2^16 cells): cubic Morton cells.  A unit per axis (round 1-2) made
     // the cells of an NCLT-shaped cloud (235 x 235 x 12 m) 20 x flatter than wide, and the curve then cuts a ground patch into contour
-    // strips: 64 consecutive points had 408 distinct 30-NN neighbours instead of 209 (tools/knnw_stats.py).
+    // strips: 64 consecutive points had 408 distinct 30-NN neighbours instead of 209 (measured with per-wavefront counters of the k-NN kernel).
     float s[3];
     double emax = 0.0;
     for (int d = 0; d < 3; d++) emax = b6[3 + d] - b6[d] > emax ? b6[3 + d] - b6[d] : emax;
@@ -1088,11 +1088,9 @@ struct KnnArgs {
     double *avg;                       // SOR
     const float4 *prior; float4 *normals; float *cov6;   // normals
     int32_t *dbg_idx; float *dbg_d2; int32_t *dbg_cnt;   // debug (rows unsorted)
-    int dbg_visits;                                      // debug: dbg_cnt <- traversal counters
     int32_t *list_idx; int list_pitch;                   // k-best lists: rows of list_pitch int32 per query (-1: empty slot).  SOR: optional output (32);
                                                          //   wavefront kernel (pcr_knn_wave.h): required, its working rows (scratch in the other modes)
     const uint8_t *todo;                                 // optional: only queries with todo[q] != 0 are processed
-    unsigned long long *stamps;                          // diagnostics (PCR_KNN_STAMPS): 24 words per wavefront
     int seed_span;                                       // Morton-index half-width of the seed range (-1: k)
     int *zero_a, *zero_b;                                // optional counters of LATER kernels, zeroed here (saves two memset launches)
     uint8_t *hard; int wave_budget;                      // wavefront kernel: optional, queries it gave up after wave_budget batches (1) or served (0)
@@ -1125,11 +1123,9 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
     if (threadIdx.x == 0) m = *a.t.meta;
     if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { if (a.zero_a) *a.zero_a = 0; if (a.zero_b) *a.zero_b = 0; }
     __syncthreads();
-    auto item = [&](const int g0, const size_t stamp_slot) {
+    auto item = [&](const int g0) {
     const int n = m.n;
     const int lane = threadIdx.x & 63, oct = lane >> 3, ol = lane & 7;
-    const unsigned long long t_begin = wall_clock64();
-    const unsigned long long c_begin = a.stamps ? __builtin_readcyclecounter() : 0ull;
     const int qi = g0 + oct;
     const int oq = (a.keep && qi < n) ? a.pos[qi] : qi;                 // output / todo index of this query
     const bool live = qi < n && (!a.keep || a.keep[qi]) && (!a.todo || a.todo[oq]);
@@ -1146,7 +1142,6 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
     const int sp = span > half ? span : half;
     const int plo = g0 - sp < 0 ? 0 : g0 - sp, phi = glast + sp > n - 1 ? n - 1 : glast + sp;
     bool seeding = true;
-    int st_scan = 0, st_rounds = 0;      // diagnostics: 8-point scan steps and insertion rounds of this wavefront
 
     // ---- scan `count` consecutive points from `first` for all 8 queries, 8 candidates at a time; survivors enter the k-best
     auto visit = [&](int first, int count) {
@@ -1160,9 +1155,7 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
             }
             unsigned long long bal = __ballot(pass);
             uint32_t surv = (uint32_t)(bal >> (oct * 8)) & 0xffu;
-            st_scan++;
             while (bal != 0ull) {                      // one candidate per octet and round, no divergence inside
-                st_rounds++;
                 const int sl = __builtin_ctz(surv | 0x100u) & 7;
                 const float cd = __shfl(d2, sl, OCT);
                 tk.insert(surv ? cd : __builtin_inff(), base + sl);
@@ -1191,26 +1184,9 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
     if (c0 + filled <= phi) visit(c0 + filled, phi - (c0 + filled) + 1);
     seeding = false;
 
-    const float seed_worst = tk.worst;
-    int nvis = 0;
     const int first_live = g0 + (__builtin_ctzll(__ballot(live)) >> 3);
     oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[first_live], q.x, q.y, q.z, [&]() { return tk.worst; }, visit,
-                     [&](int f, int c) { return f >= plo && f + c - 1 <= phi; }, ol,
-                     ((MODE == KNN_MODE_DEBUG && a.dbg_visits) || a.stamps) ? &nvis : nullptr);
-    if (a.stamps && ol == 0) {
-        unsigned long long *w = a.stamps + 24 * stamp_slot;
-        w[8 + oct] = ((unsigned long long)__float_as_uint(seed_worst) << 32) | __float_as_uint(tk.worst);
-        w[16 + oct] = ((unsigned long long)__float_as_uint(q.x) << 32) | __float_as_uint(q.y);
-    }
-    if (a.stamps && lane == 0) {
-        unsigned long long *w = a.stamps + 24 * stamp_slot;
-        w[4] = ((unsigned long long)(unsigned)st_scan << 32) | (unsigned)st_rounds;
-        w[5] = ((unsigned long long)__float_as_uint(q.x) << 32) | __float_as_uint(q.y);
-        w[6] = ((unsigned long long)__float_as_uint(q.z) << 32) | __float_as_uint(tk.worst);
-        w[7] = (unsigned long long)nvis;
-        w[0] = t_begin; w[1] = wall_clock64(); w[2] = __builtin_readcyclecounter() - c_begin;
-        w[3] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-    }
+                     [&](int f, int c) { return f >= plo && f + c - 1 <= phi; }, ol);
     if (!live) return;
 
     // ---- epilogue in float64 on the selected neighbours (inputs are exact float32 -> same values as the oracle)
@@ -1282,21 +1258,23 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
         }
 #pragma unroll
         for (int o = 1; o < OCT; o <<= 1) c += __shfl_xor(c, o, OCT);
-        if (ol == 0 && a.dbg_cnt) a.dbg_cnt[qi] = a.dbg_visits == 2 ? (int)(wall_clock64() - t_begin) : (a.dbg_visits ? nvis : c);
+        if (ol == 0 && a.dbg_cnt) a.dbg_cnt[qi] = c;
     }
     };
     const int wv = threadIdx.x >> 6;
-    if (!LIST) item((int)blockIdx.x * OPB + wv * OCT, (size_t)blockIdx.x * (KNN_BS / 64) + wv);
-    else for (int it = blockIdx.x * (KNN_BS / 64) + wv; it < n_items; it += gridDim.x * (KNN_BS / 64)) item(a.hard_piece ? a.hard_list[it] : a.hard_list[it >> 3] + (it & 7) * OCT, 0);
+    if (!LIST) item((int)blockIdx.x * OPB + wv * OCT);
+    else for (int it = blockIdx.x * (KNN_BS / 64) + wv; it < n_items; it += gridDim.x * (KNN_BS / 64)) item(a.hard_piece ? a.hard_list[it] : a.hard_list[it >> 3] + (it & 7) * OCT);
 }
 template <int MODE, int SLOTS> __device__ static inline void d_knn(const KnnArgs &a) { d_knn_<MODE, SLOTS, false>(a); }
 template <int MODE, int SLOTS> __device__ static inline void d_knn_list(const KnnArgs &a) { d_knn_<MODE, SLOTS, true>(a); }
 template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn(KnnArgs a) { d_knn<MODE, SLOTS>(a); }
 template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list(KnnArgs a) { d_knn_list<MODE, SLOTS>(a); }
 template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list_batch(KnnBatch b) { d_knn_list<MODE, SLOTS>(b.a[blockIdx.y]); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list_batchp(const KnnArgs *a) { d_knn_list<MODE, SLOTS>(a[blockIdx.y]); }
+// (the device-pointer forms inline the body by force: left to the inliner, whether it was inlined there depended on the order in which the
+// templates were instantiated, and a call out of line costs a stack frame and up to 100 VGPRs)
+template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn_list<MODE, SLOTS>(a[blockIdx.y]); }
 template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_batch(KnnBatch b) { d_knn<MODE, SLOTS>(b.a[blockIdx.y]); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_batchp(const KnnArgs *a) { d_knn<MODE, SLOTS>(a[blockIdx.y]); }
+template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn<MODE, SLOTS>(a[blockIdx.y]); }
 
 #include "pcr_knn_wave.h"
 
@@ -1315,7 +1293,7 @@ static bool knn_wave_enabled(const pcr_context *ctx, int batch, long long points
     const int forced = pcr_options().knn_wave.load(std::memory_order_relaxed);
     return forced >= 0 ? forced != 0 : (!ctx->octet_only && (ctx->group_forms || batch >= KNN_WAVE_MIN_BATCH || points >= KNN_WAVE_MIN_POINTS));
 }
-static bool knn_wave_fits(const KnnArgs &a) { return a.k >= 1 && a.k <= 64 && !a.todo && !a.stamps && !a.dbg_visits; }
+static bool knn_wave_fits(const KnnArgs &a) { return a.k >= 1 && a.k <= 64 && !a.todo; }
 // the wavefront kernel appends every query's k-best to a row in global memory: the caller's list (SOR) or scratch from the arena
 template <int MODE>
 static int knn_wave_rows(pcr_context *ctx, KnnArgs &a, int cap) {
@@ -1364,22 +1342,6 @@ template <int MODE>
 static int launch_knn_wave(pcr_context *ctx, int cap, KnnArgs a) {
     PCR_TRY(knn_wave_rows<MODE>(ctx, a, cap));
     const dim3 grid((unsigned)(((size_t)cap + KW_BS - 1) / KW_BS)), block(KW_BS);
-    if (const char *path = MODE == KNN_MODE_DEBUG ? getenv("PCR_KNNW_STATS") : nullptr) {      // diagnostics: per-wavefront counters of the two passes, appended to a file
-        const size_t words = (size_t)grid.x * (KW_BS / 64) * 24;
-        unsigned long long *dev = nullptr;
-        if (hipMalloc(&dev, words * 8) != hipSuccess) return PCR_ENOMEM;
-        (void)hipMemsetAsync(dev, 0, words * 8, ctx->stream);
-        a.stamps = dev;
-        if (a.k <= 20) PCR_LAUNCH(ctx, (k_knn_wave_stats<MODE, 20>), grid, block, 0, ctx->stream, a);
-        else if (a.k <= 30) PCR_LAUNCH(ctx, (k_knn_wave_stats<MODE, 30>), grid, block, 0, ctx->stream, a);
-        else PCR_LAUNCH(ctx, (k_knn_wave_stats<MODE, 64>), grid, block, 0, ctx->stream, a);
-        (void)hipStreamSynchronize(ctx->stream);
-        std::vector<unsigned long long> h(words);
-        (void)hipMemcpy(h.data(), dev, words * 8, hipMemcpyDeviceToHost);
-        if (FILE *f = fopen(path, "ab")) { const unsigned long long hdr[4] = {0x4b57535441ull, (unsigned long long)a.k, (unsigned long long)cap, words / 24}; fwrite(hdr, 8, 4, f); fwrite(h.data(), 8, words, f); fclose(f); }
-        (void)hipFree(dev);
-        return PCR_OK;
-    }
     const int budget = knn_wave_budget();
     const bool handover = MODE != KNN_MODE_DEBUG && budget > 0;
     if (handover) {
@@ -1402,13 +1364,8 @@ static int launch_knn_wave(pcr_context *ctx, int cap, KnnArgs a) {
 }
 
 // `count` searches in ONE launch (blockIdx.y picks the problem; k <= 32): the SOR / normals searches of all scales of a cloud
-template <int MODE> static int launch_knn_cap(pcr_context *ctx, int cap, KnnArgs a);
 template <int MODE>
 static int launch_knn_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count) {
-    if (getenv("PCR_KNN_STAMPS")) {                          // diagnostics: one stamped launch per problem
-        for (int k = 0; k < count; k++) PCR_TRY(launch_knn_cap<MODE>(ctx, caps[k], a[k]));
-        return PCR_OK;
-    }
     long long total_pts = 0;
     for (int k = 0; k < count; k++) total_pts += caps[k];
     if (knn_wave_enabled(ctx, count, total_pts)) {
@@ -1439,32 +1396,10 @@ static int launch_knn_octet_batch(pcr_context *ctx, KnnArgs *a, const int *caps,
 }
 
 template <int MODE>
-static int launch_knn(pcr_context *ctx, const DevCloud *c, KnnArgs a) { return launch_knn_cap<MODE>(ctx, c->cap, a); }
-template <int MODE>
 static int launch_knn_cap(pcr_context *ctx, int cap, KnnArgs a) {
     if (cap <= 0) return PCR_OK;
     if (a.k < 1 || a.k > 200) { ctx->err = "k out of range for the octet k-NN kernel (1..200)"; return PCR_EINVAL; }
     const dim3 grid((unsigned)(((size_t)cap * OCT + KNN_BS - 1) / KNN_BS)), block(KNN_BS);
-    const char *stamp_path = getenv("PCR_KNN_STAMPS");      // diagnostics only: per-wavefront begin/end clocks and hardware ids
-    const size_t stamp_words = (size_t)grid.x * (KNN_BS / 64) * 24;
-    if (stamp_path) {
-        if (hipMalloc(&a.stamps, stamp_words * 8) != hipSuccess) return PCR_ENOMEM;
-        (void)hipMemsetAsync(a.stamps, 0, stamp_words * 8, ctx->stream);
-    }
-    struct StampDump {
-        pcr_context *ctx; const char *path; unsigned long long *dev; size_t words; int mode, k;
-        ~StampDump() {
-            if (!path) return;
-            (void)hipStreamSynchronize(ctx->stream);
-            unsigned long long *h = (unsigned long long *)malloc(words * 8);
-            (void)hipMemcpy(h, dev, words * 8, hipMemcpyDeviceToHost);
-            if (FILE *f = fopen(path, "ab")) {
-                const unsigned long long hdr[4] = {0x5354414d50ull, (unsigned long long)mode, (unsigned long long)k, words / 24};
-                fwrite(hdr, 8, 4, f); fwrite(h, 8, words, f); fclose(f);
-            }
-            free(h); (void)hipFree(dev);
-        }
-    } dump{ctx, stamp_path, a.stamps, stamp_words, MODE, a.k};
     a.seed_span = -1;
     if (knn_wave_enabled(ctx, 1, cap) && knn_wave_fits(a)) { a.seed_span = -1; return launch_knn_wave<MODE>(ctx, cap, a); }
     if (a.k <= 32) PCR_LAUNCH(ctx, k_knn<MODE, 4>, grid, block, 0, ctx->stream, a);
@@ -1472,6 +1407,8 @@ static int launch_knn_cap(pcr_context *ctx, int cap, KnnArgs a) {
     else PCR_LAUNCH(ctx, k_knn<MODE, 25>, grid, block, 0, ctx->stream, a);
     return PCR_OK;
 }
+template <int MODE>
+static int launch_knn(pcr_context *ctx, const DevCloud *c, KnnArgs a) { return launch_knn_cap<MODE>(ctx, c->cap, a); }
 
 static void knn_radius(KnnArgs &a, int search_kind, double radius) {
     if (search_kind == PCR_SEARCH_HYBRID && radius > 0) {
@@ -1485,7 +1422,7 @@ int pcr_dev_knn_debug(pcr_context *ctx, const DevCloud *c, int k, double radius,
     a.t = oct_view(c); a.n_ptr = c->n; a.k = k;
     knn_radius(a, radius > 0 ? PCR_SEARCH_HYBRID : PCR_SEARCH_KNN, radius);
     if (radius > 0) a.r2cap_f = (float)(radius * radius);
-    a.dbg_idx = idx; a.dbg_d2 = d2; a.dbg_cnt = counts; a.dbg_visits = pcr_options().debug_visits.load(std::memory_order_relaxed);
+    a.dbg_idx = idx; a.dbg_d2 = d2; a.dbg_cnt = counts;
     return launch_knn<KNN_MODE_DEBUG>(ctx, c, a);
 }
 
@@ -1528,7 +1465,7 @@ __global__ void __launch_bounds__(KNN_BS) k_radius_moments(RadArgs a) {
     };
     const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
     oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return a.r2f; }, visit,
-                     [](int, int) { return false; }, ol, nullptr);
+                     [](int, int) { return false; }, ol);
 #pragma unroll
     for (int t = 0; t < 9; t++) cu[t] = octet_sum(cu[t]);
     c = octet_sum(c);
@@ -1629,7 +1566,7 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
     const int leaf0 = a.t.leaf_of[g0 < n ? g0 : 0];
     // (without the selection a ball that is overfull already needs nothing more from the walk: its bound drops to nothing)
     oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, leaf0, q.x, q.y, q.z, [&]() { return (!select && cnt > a.k) ? -1.0f : a.r2f; }, visit,
-                     [](int, int) { return false; }, ol, nullptr);
+                     [](int, int) { return false; }, ol);
     const bool mine = live && cnt > a.k;                                   // octet-uniform
     bool over = __ballot(mine) != 0ull;                                    // (a wavefront = one piece of 8 queries)
     if (over && select) {
@@ -1664,7 +1601,7 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
             }
         };
         oct_search_group(a.t, m, gstk[threadIdx.x >> 6], mine && !wide, leaf0, q.x, q.y, q.z, [&]() { return bound2; }, visit2,
-                         [](int, int) { return false; }, ol, nullptr);
+                         [](int, int) { return false; }, ol);
         const int ne = mine ? nedge[ob] : 0;
         const bool spill = wide || ne > RL_EDGE;
         over = __ballot(spill) != 0ull;                                    // such a piece is the k-best kernel's
@@ -1749,7 +1686,7 @@ __device__ static inline void d_radius_fix(const RadListArgs &a) {
                 }
             };
             oct_search_group(a.t, m, gstk[threadIdx.x >> 6], act, leaf0, q.x, q.y, q.z, [&]() { return act ? wb : -1.0f; }, visit,
-                             [](int, int) { return false; }, ol, nullptr);
+                             [](int, int) { return false; }, ol);
         };
         auto key_of = [&](const float4 &p) { return (unsigned long long)__double_as_longlong(pcr_d2_f64_unfused(q, p)); };
         // walk 1: points below the band, points in it, and the range of their float64 keys
@@ -1835,7 +1772,7 @@ __device__ static inline void d_radius_fix(const RadListArgs &a) {
             }
         };
         oct_search_group(a.t, m, gstk[threadIdx.x >> 6], fix, leaf0, q.x, q.y, q.z, [&]() { return wb; }, write,
-                         [](int, int) { return false; }, ol, nullptr);
+                         [](int, int) { return false; }, ol);
     }
 }
 __global__ void __launch_bounds__(KNN_BS) k_radius_fix(RadListArgs a) { d_radius_fix(a); }
@@ -2225,7 +2162,7 @@ int pcr_dev_knn_lists_batch(pcr_context *ctx, const DevCloud *const *cs, int cou
         a.t = oct_view(cs[c]); a.n_ptr = cs[c]->n; a.k = k;
         knn_radius(a, radius > 0 ? PCR_SEARCH_HYBRID : PCR_SEARCH_KNN, radius);
         if (radius > 0) a.r2cap_f = (float)(radius * radius);
-        a.dbg_idx = idx[c]; a.dbg_d2 = d2[c]; a.dbg_cnt = nullptr; a.dbg_visits = 0;
+        a.dbg_idx = idx[c]; a.dbg_d2 = d2[c]; a.dbg_cnt = nullptr;
         caps[m++] = cs[c]->cap;
     }
     if (m == 0) return PCR_OK;

@@ -669,7 +669,7 @@ __device__ static inline void d_feature_nn_screen(const FnnArgs &a) {
     // The database does not fit the L2s (51 MB at 200k rows): a row block comes from the Infinity Cache or HBM, 1-2 us away.  Steps are
     // staged FN_GRP at a time with ONE workgroup barrier per group: the LDS image is double buffered by group, the global loads of group
     // g + 2 are issued once group g + 1 has been written to LDS and land while group g + 1 is computed on.  Round 4 measured where a
-    // wavefront's cycles go in this loop (tools/build_variant.sh stamps pcr_featnn -DFN_STAMPS, 200k x 200k rows, per direction): barrier
+    // wavefront's cycles go in this loop (a stamped diagnostics build, since removed, 200k x 200k rows, per direction): barrier
     // waits 37 %, MFMA path 36 %, candidate path 10 %, LDS stash 10 %, load issue 7 % -- and then that the barriers are NOT the lever: groups
     // of 2 / 4 tiles per barrier (13.0 / 12.9 ms against 12.6 for both directions) and workgroups of 4 / 2 wavefronts (12.1 / 12.0 against
     // 13.0 before the other changes of the round) leave the time where it is.  A wavefront computes in 62 % of the staged steps of its
@@ -694,18 +694,11 @@ __device__ static inline void d_feature_nn_screen(const FnnArgs &a) {
 #pragma unroll
     for (int t = 0; t < FN_GRP; t++) { const int i = 2 * FN_GRP + t; pf_step[t] = i < n_list ? slist[i] : 0; pf_lw[t] = i < n_list ? list_lw(i) : 0.0f; }
     unsigned long long n_comp = 0;
-#ifdef FN_STAMPS          // diagnostics build (tools/build_variant.sh ... -DFN_STAMPS): shader cycles of a wavefront per phase of the step loop
-    unsigned long long tc_bar = 0, tc_fast = 0, tc_cand = 0, tc_stash = 0, tc_fetch = 0, n_hitblk = 0;
-#define FN_T(...) __VA_ARGS__
-#else
-#define FN_T(...)
-#endif
     const unsigned a_off = (unsigned)(g * FN_GROUP + col * FN_PITCH);
     int chunk_base = -1, chunk_fill = FN_CHUNK;            // wave-uniform: current chunk of the record pool (none yet)
     bool dead = false;                                      // the pool overflowed: flags[0] is set and the caller falls back
     // one staged tile: LDS buffer `buf`, database step `step`, box distance `lw` of the tile from this wavefront's queries
     auto tile = [&](const int buf, const int step, const float lw) {
-        FN_T(const unsigned long long t2 = __builtin_amdgcn_s_memtime();)
         const bool wave_on = !(lw > Dw);                  // wave-uniform
         if (wave_on) {
         n_comp++;
@@ -734,11 +727,9 @@ __device__ static inline void d_feature_nn_screen(const FnnArgs &a) {
                 }
             }
         }
-        FN_T(const unsigned long long t3 = __builtin_amdgcn_s_memtime(); tc_fast += t3 - t2;)
         // ---- candidate path: blocks in which some lane saw a value under its threshold are recomputed from the LDS image
         if (!BOUND_ONLY && wave_hits != 0u && !dead) {
             while (wave_hits != 0u) {
-                FN_T(n_hitblk++;)
                 const int blk = __builtin_ctz(wave_hits);
                 wave_hits &= wave_hits - 1u;
                 const int sub = blk / FN_QB, b = blk % FN_QB;
@@ -793,35 +784,28 @@ __device__ static inline void d_feature_nn_screen(const FnnArgs &a) {
             }
             if (prune) Dw = wave_D();
         }
-        FN_T(tc_cand += __builtin_amdgcn_s_memtime() - t3;)
         }
     };
     for (int gi = 0; gi < n_groups; gi++) {
         const int half = (gi & 1) * FN_GRP;
-        FN_T(const unsigned long long t1 = __builtin_amdgcn_s_memtime();)
         __syncthreads();                                  // the buffers of this group are complete; the other group's are no longer read by anyone
-        FN_T(tc_bar += __builtin_amdgcn_s_memtime() - t1;)
 #pragma unroll
         for (int t = 0; t < FN_GRP; t++) if (gi * FN_GRP + t < n_list) tile(half + t, slist[gi * FN_GRP + t], lw_now[t]);
-        FN_T(const unsigned long long t4 = __builtin_amdgcn_s_memtime();)
         if (gi + 1 < n_groups) {
 #pragma unroll
             for (int t = 0; t < FN_GRP; t++) if ((gi + 1) * FN_GRP + t < n_list) { stash((FN_GRP - half) + t, slot[t]); lw_next[t] = slot[t].lw; }
         }
-        FN_T(const unsigned long long t5 = __builtin_amdgcn_s_memtime(); tc_stash += t5 - t4;)
         if (gi + 2 < n_groups) {
 #pragma unroll
             for (int t = 0; t < FN_GRP; t++) if ((gi + 2) * FN_GRP + t < n_list) fetch(pf_step[t], pf_lw[t], slot[t]);
         }
 #pragma unroll
         for (int t = 0; t < FN_GRP; t++) { const int i = (gi + 3) * FN_GRP + t; pf_step[t] = i < n_list ? slist[i] : 0; pf_lw[t] = i < n_list ? list_lw(i) : 0.0f; }
-        FN_T(tc_fetch += __builtin_amdgcn_s_memtime() - t5;)
 #pragma unroll
         for (int t = 0; t < FN_GRP; t++) lw_now[t] = lw_next[t];
     }
     if (lane == 0 && chunk_base >= 0) a.chunk_fill[chunk_base / FN_CHUNK] = chunk_fill;
     if (a.stats && lane == 0) { atomicAdd(&a.stats[1], n_comp); atomicAdd(&a.stats[2], (unsigned long long)n_list); }
-    FN_T(if (a.stats && lane == 0) { atomicAdd(&a.stats[4], tc_fetch); atomicAdd(&a.stats[5], tc_bar); atomicAdd(&a.stats[6], tc_fast); atomicAdd(&a.stats[7], tc_cand); atomicAdd(&a.stats[8], tc_stash); atomicAdd(&a.stats[9], n_hitblk); })
     if (BOUND_ONLY)
 #pragma unroll
         for (int b = 0; b < FN_QB; b++) U[b] = pcr_xrow_min(U[b]);
@@ -1244,7 +1228,7 @@ int pcr_feature_nn_mutual(pcr_context *ctx, const float *f0, int n0, const float
         a.L = nullptr; a.L_stride = 0; a.n_qt = 0; a.prelist = nullptr; a.pre_mode = 0; a.n_bound = 0; a.xcd_chunk = 0; a.stats = nullptr;
         a.seeded = seeded ? 1 : 0;
         unsigned long long *stats = nullptr;
-        if (check || ctx->profiling) { stats = arena<unsigned long long>(ctx, 16); if (!stats) return PCR_ENOMEM; PCR_HIP_CHECK(ctx, hipMemsetAsync(stats, 0, 128, ctx->stream)); a.stats = stats; }
+        if (check || ctx->profiling) { stats = arena<unsigned long long>(ctx, 4); if (!stats) return PCR_ENOMEM; PCR_HIP_CHECK(ctx, hipMemsetAsync(stats, 0, 32, ctx->stream)); a.stats = stats; }
         if (prune && seeded) {      // the bounds are final already: one pass over the tiles within them
             const int nqt = (nq + 63) / 64, nbt = steps;
             float *L = arena<float>(ctx, (size_t)nqt * nbt);
@@ -1272,12 +1256,10 @@ int pcr_feature_nn_mutual(pcr_context *ctx, const float *f0, int n0, const float
             if (a.n_bound > 0) PCR_LAUNCH(ctx, k_feature_nn_screen<true>, dim3(groups, FN_PRE_SPLIT_B), dim3(FN_WG), 0, ctx->stream, a);
             PCR_LAUNCH(ctx, k_feature_nn_screen<false>, dim3(groups, FN_PRE_SPLIT), dim3(FN_WG), 0, ctx->stream, a);
             if (check) {    // the pre-pass by itself (diagnostics: a wait and a read-back in the middle of the direction)
-                unsigned long long hs[16] = {0}; int used = 0;
-                PCR_HIP_CHECK(ctx, hipMemcpyAsync(hs, stats, 128, hipMemcpyDeviceToHost, ctx->stream));
+                int used = 0;
                 PCR_HIP_CHECK(ctx, hipMemcpyAsync(&used, pool_used, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
                 PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-                fprintf(stderr, "featnn dir %d pre-pass (%d nearest tiles per workgroup): %d records allocated (%.1f per query); stamps (M ticks): fetch %.1f, barrier %.1f, fast path %.1f, candidate path %.1f (%llu hit blocks), stash %.1f\n",
-                        dir, FN_NPRE, used, (double)used / nq, hs[4] * 1e-6, hs[5] * 1e-6, hs[6] * 1e-6, hs[7] * 1e-6, hs[9], hs[8] * 1e-6);
+                fprintf(stderr, "featnn dir %d pre-pass (%d nearest tiles per workgroup): %d records allocated (%.1f per query)\n", dir, FN_NPRE, used, (double)used / nq);
             }
             a.pre_mode = 0; a.step0 = 0; a.steps_per_split = sps; a.step_end = steps;
             a.xcd_chunk = FN_XCD_ORDER ? (groups + 7) / 8 : 0;
@@ -1316,11 +1298,9 @@ int pcr_feature_nn_mutual(pcr_context *ctx, const float *f0, int n0, const float
             PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h[0], pool_used, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h[1], flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             PCR_HIP_CHECK(ctx, hipMemcpyAsync(hd, dbg, 8, hipMemcpyDeviceToHost, ctx->stream));
-            unsigned long long hs[16] = {0};
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(hs, stats, 128, hipMemcpyDeviceToHost, ctx->stream));
+            unsigned long long hs[4] = {0, 0, 0, 0};
+            PCR_HIP_CHECK(ctx, hipMemcpyAsync(hs, stats, 32, hipMemcpyDeviceToHost, ctx->stream));
             PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            if (hs[4] + hs[5] + hs[6]) fprintf(stderr, "featnn dir %d: wavefront cycles per phase of the step loop (FN_STAMPS, summed over wavefronts, M cycles): fetch issue %.1f, barrier wait %.1f, fast path %.1f, "
-                                                       "candidate path %.1f (%llu hit blocks), stash %.1f\n", dir, hs[4] * 1e-6, hs[5] * 1e-6, hs[6] * 1e-6, hs[7] * 1e-6, hs[9], hs[8] * 1e-6);
             fprintf(stderr, "featnn dir %d: tile pruning %s: %llu steps staged of %lld (workgroup x step), %llu (wavefront, step) pairs computed of %lld\n", dir, prune ? "on" : "off",
                     hs[0], (long long)groups * steps, hs[1], (long long)groups * (FN_WG / 64) * steps);
             fprintf(stderr, "featnn dir %d: %d queries x %d rows, pre %d + %d splits x %d steps of %d rows; pool %d of %d records allocated (%.1f per query)%s, %.0f survived the final bound (%.2f per query); "

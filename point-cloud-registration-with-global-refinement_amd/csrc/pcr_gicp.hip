@@ -63,16 +63,12 @@ struct IcpArgs {
     int loss; double loss_k; double a;          // a = 1 - epsilon
     double rel_fit, rel_rmse; int max_it;
     int single;                                  // 1: linearise once, never update (debug / evaluate)
-    int dbg_visits;                              // diagnostics: store node/leaf visit counts instead of matches
-    int dbg_phase;                               // diagnostics (PCR_ICP_PHASE = 1 / 2): t_dbg[1] <- slowest workgroup's end of phase A / B of the fused kernel
-    unsigned long long *stamps_nn, *stamps_it;   // diagnostics (PCR_ICP_STAMPS): per-wavefront clocks of the first 16 launches
     // all scales of a pair behind ONE argument slot (pcr_dev_gicp_group_scales; ms_scales == 0: a single scale): when the criteria of scale ms_index
     // hold, the last workgroup stores the state in ms_hist[ms_index] and -- unless it was the last scale -- starts the next one itself: launches,
     // iterations and flags back to their start values, the pose kept, and ms_args[ms_index + 1] copied over *ms_self, the slot the next launch reads.
     // A launch that finds launches == 0 is the scale's first: no certificate is valid, every query is searched (what k_icp_nn + k_icp_lin do).
     const IcpArgs *ms_args; IcpArgs *ms_self; IcpState *ms_hist; int ms_scales, ms_index;
 };
-#define ICP_STAMP_LAUNCHES 16
 
 struct IcpInit { double T[16]; };
 __device__ static inline void d_icp_init(IcpState *st, const IcpInit &in) {
@@ -92,7 +88,7 @@ __global__ void k_icp_init_g(IcpState *st, const IcpInit *in) { d_icp_init(st + 
 // Returns the best index within r2cap (or -1) and, through start_pt, a point of the start leaf (next launch's hint).
 template <int OPB>
 __device__ static inline int oct_nn_query(const OctView &t, const OctMeta &m, OctStack<OPB> &stk, bool live, float qx, float qy, float qz,
-                                          float r2cap, int hint, int ol, int oct, int ob, int *start_pt, int *visits, float *d1_out, float *d2_out) {
+                                          float r2cap, int hint, int ol, int oct, int ob, int *start_pt, float *d1_out, float *d2_out) {
     // The walk keeps the TWO smallest squared distances (both capped at r2cap) and prunes with the second: the gap between
     // them is the certificate that lets later launches skip this query while it has moved by less than half the gap.
     int best = -1; float bestd = r2cap, secd = r2cap;
@@ -150,7 +146,7 @@ __device__ static inline int oct_nn_query(const OctView &t, const OctMeta &m, Oc
     }
     if (active) *start_pt = s_first;
     oct_search<OPB>(t, m, stk, active, node, node_li, s_first, s_count, s_key, s_parent, s_sib, s_nsib, qx, qy, qz, [&]() { return secd; }, visit,
-                    [](int, int) { return false; }, ol, oct, ob, visits);
+                    [](int, int) { return false; }, ol, oct, ob);
     *d1_out = bestd; *d2_out = secd;
     return best;
 }
@@ -382,7 +378,7 @@ __device__ static inline void d_icp_nn(const IcpArgs &a) {
         // margin = (d2 - d1)/2 - slack.  While the query has moved by less than the margin since then, rb is still its
         // unique nearest point (triangle inequality) and no search is needed; k_icp_iter re-tests the radius in float64.
         const float ex = qx - refv.x, ey = qy - refv.y, ez = qz - refv.z;
-        bool certified = launches > 0 && a.ref && !a.dbg_visits && refv.w > 0.0f;
+        bool certified = launches > 0 && a.ref && refv.w > 0.0f;
         if (GRID) { if (certified) certified = icp_list_eval(a.tgt_pts, qx, qy, qz, refv, lst, a.r2f, &rb) != 0; }   // list certificate: rb = the decided neighbour (or -1)
         else certified = certified && pcr_d2(ex, ey, ez) < refv.w * refv.w;
         need = nt > 0 && (!certified || a.verify);
@@ -406,10 +402,10 @@ __device__ static inline void d_icp_nn(const IcpArgs &a) {
     if (__ballot(live) == 0ull) return;
     int qi = 0;
     if (live) { const float4 r = rec_q[ob]; qx = r.x; qy = r.y; qz = r.z; hint = __float_as_int(r.w); qi = rec_i[ob]; }
-    int visits = 0, start_pt = 0; float d1 = 0, d2 = 0;
+    int start_pt = 0; float d1 = 0, d2 = 0;
     int best; int nnk[PCR_NN_K];
     if (GRID) { grid_nn_query8<PCR_NN_K>(a.grid, gmask, a.tgt_pts, live, qx, qy, qz, a.ref ? a.r2s : a.r2f, ol, nnk, &d1, &d2); best = nnk[0]; start_pt = hint >= 0 ? hint : 0; }
-    else best = oct_nn_query<OPB>(a.tgt, m, stk, live, qx, qy, qz, a.ref ? a.r2s : a.r2f, hint, ol, oct, ob, &start_pt, a.dbg_visits ? &visits : nullptr, &d1, &d2);
+    else best = oct_nn_query<OPB>(a.tgt, m, stk, live, qx, qy, qz, a.ref ? a.r2s : a.r2f, hint, ol, oct, ob, &start_pt, &d1, &d2);
     if (a.verify && ol == 0 && live && rec_c[ob] != -2) {
         const int claim = rec_c[ob];
         // (a decided neighbour may have drifted beyond the search cap r + g -- it is beyond r then, and the search finds nothing: no contradiction)
@@ -420,7 +416,7 @@ __device__ static inline void d_icp_nn(const IcpArgs &a) {
                         a.ref[qi].w, sqrtf(pcr_d2(qx - a.ref[qi].x, qy - a.ref[qi].y, qz - a.ref[qi].z)));
     }
     if (ol == 0 && live) {
-        a.match[qi] = a.dbg_visits ? visits : (best >= 0 ? best : -(start_pt + 2));
+        a.match[qi] = best >= 0 ? best : -(start_pt + 2);
         if (a.ref && GRID) {
             a.ref[qi] = make_float4(qx, qy, qz, sqrtf(d2));          // d2 = squared distance of the first point NOT listed (or the cap)
             a.clist[qi] = make_int4(nnk[0], nnk[1], nnk[2], nnk[3]);
@@ -431,10 +427,6 @@ __device__ static inline void d_icp_nn(const IcpArgs &a) {
             a.ref[qi] = make_float4(qx, qy, qz, margin > 0.0f ? margin : 0.0f);
             a.rbest[qi] = best;
         }
-    }
-    if (a.stamps_nn && lane == 0 && launches < ICP_STAMP_LAUNCHES) {
-        unsigned long long *w = a.stamps_nn + 2 * ((size_t)launches * gridDim.x * (ICP_BS / 64) + (size_t)blockIdx.x * (ICP_BS / 64) + (threadIdx.x >> 6));
-        w[0] = t_wave0; w[1] = wall_clock64();
     }
 }
 
@@ -458,7 +450,6 @@ __device__ static inline void icp_point(const IcpArgs &a, const double *T, int i
         qz = T[8] * px + T[9] * py + T[10] * pz + T[11];
         cand = cand_in;
     }
-    if (a.dbg_visits) cand = -1;
 
     // ---- one correspondence per lane, float64
     if (i < ns && cand >= 0) {
@@ -554,8 +545,7 @@ __device__ static inline void icp_point(const IcpArgs &a, const double *T, int i
 // ---- workgroup reduction of acc[], write-through partial row + ticket, and -- in the last-arriving workgroup -- the end of
 // the iteration: gather the rows, fixed-order sums, convergence test, 6x6 solve, pose update.  BS = workgroup size.
 template <int MODE, int BS>
-__device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const double *T, double *acc, int nb, int ns, int launches, unsigned long long t_entry, int row,
-                                         unsigned long long t_p = 0, unsigned long long t_a = 0, unsigned long long t_b = 0) {
+__device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const double *T, double *acc, int nb, int ns, int launches, unsigned long long t_entry, int row) {
     __shared__ double red[BS / 16][NVP];           // one row per 16-lane DPP row
     __shared__ double fin[16][NVP];
     __shared__ int is_last;
@@ -576,7 +566,6 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
         if (16 + r < NV) red[threadIdx.x >> 4][16 + r] = hi;
     }
 #endif
-    const unsigned long long t_ws = wall_clock64();
     __syncthreads();
     if (threadIdx.x < NV) {
         double s = red[0][threadIdx.x];
@@ -586,16 +575,11 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
         // them per launch serialised to >100 us).  cdna_hip_programming.md Guideline 16, recipe R1.
         __hip_atomic_store(&a.partials[(size_t)row * NVP + threadIdx.x], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (threadIdx.x == 63) {   // diagnostics in the two padding columns: ticks to end-of-search / end-of-reduction
-        // PCR_ICP_PHASE = phase + 16 * mean: column 31 <- this workgroup's ticks from its entry to the end of phase 1 prologue / 2 certificates /
-        // 3 searches / 4 linearisation / 5 row sums (0: to here); gathered as the maximum over the workgroups, or their mean with + 16
-        const int ph = a.dbg_phase & 15;
-        const unsigned long long t_sel = ph == 1 ? t_p : ph == 2 ? t_a : ph == 3 ? t_b : ph == 4 ? t_search : ph == 5 ? t_ws - t_entry : wall_clock64() - t_entry;
+    if (threadIdx.x == 63) {   // diagnostics in the two padding columns: ticks to end-of-search / end-of-reduction (gathered as the maximum over the workgroups)
         __hip_atomic_store(&a.partials[(size_t)row * NVP + 30], (double)t_search, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.partials[(size_t)row * NVP + 31], (double)t_sel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.partials[(size_t)row * NVP + 31], (double)(wall_clock64() - t_entry), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its stores ...
-    const unsigned long long t_drain = wall_clock64();
     __syncthreads();                                       // ... before ONE lane signals for the workgroup
     if (threadIdx.x == 0) {
         const unsigned int t = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -603,11 +587,6 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
         is_last = last;
     }
     __syncthreads();
-    if (a.stamps_it && (threadIdx.x & 63) == 0 && launches < ICP_STAMP_LAUNCHES) {
-        unsigned long long *w = a.stamps_it + 12 * ((size_t)launches * gridDim.x * (BS / 64) + (size_t)blockIdx.x * (BS / 64) + (threadIdx.x >> 6));
-        w[0] = t_entry; w[1] = t_entry + t_search; w[2] = wall_clock64(); w[3] = 0; w[4] = t_ws; w[5] = t_drain;
-    }
-    unsigned long long *wl = (a.stamps_it && launches < ICP_STAMP_LAUNCHES) ? a.stamps_it + 12 * ((size_t)launches * gridDim.x * (BS / 64) + (size_t)blockIdx.x * (BS / 64)) : nullptr;
     if (!is_last) return;
 
     // ---- last workgroup: gather the partial rows with sc0 sc1 loads (coherent at agent scope without invalidating this XCD's
@@ -630,16 +609,15 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
                 v[r] = x.d;
             }
 #pragma unroll
-            for (int r = 0; r < 20; r++) { const double x = b0 + chunk + NCH * r < nb ? v[r] : 0.0; s = (vcol < NV || (vcol == 31 && a.dbg_phase >= 16)) ? s + x : fmax(s, x); }
+            for (int r = 0; r < 20; r++) { const double x = b0 + chunk + NCH * r < nb ? v[r] : 0.0; s = vcol < NV ? s + x : fmax(s, x); }
         }
         fin[chunk][vcol] = s;
     }
-    if (wl && threadIdx.x == 0) wl[6] = wall_clock64();
     __syncthreads();
     if (threadIdx.x < NVP) {
         double s = 0;
 #pragma unroll
-        for (int c = 0; c < BS / 32; c++) s = (threadIdx.x < NV || (threadIdx.x == 31 && a.dbg_phase >= 16)) ? s + fin[c][threadIdx.x] : fmax(s, fin[c][threadIdx.x]);
+        for (int c = 0; c < BS / 32; c++) s = threadIdx.x < NV ? s + fin[c][threadIdx.x] : fmax(s, fin[c][threadIdx.x]);
         fin[0][threadIdx.x] = s;
         st->sums[threadIdx.x] = s;
     }
@@ -652,8 +630,7 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
         const unsigned long long t0k = st->t_start;    // stamped by k_icp_nn (previous kernel)
         if (lead) {
             st->t_dbg[3] += wall_clock64() - t0k;
-            st->t_dbg[0] += (unsigned long long)fin[0][30]; st->t_dbg[1] += (unsigned long long)(a.dbg_phase >= 16 ? fin[0][31] / nb : fin[0][31]);
-            if (wl) wl[7] = wall_clock64();
+            st->t_dbg[0] += (unsigned long long)fin[0][30]; st->t_dbg[1] += (unsigned long long)fin[0][31];
         }
         const double *S = fin[0];
         const long long count = (long long)(S[29] + 0.5);
@@ -699,7 +676,6 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
                     U[8] = -sb;     U[9] = cb * sa;                U[10] = cb * ca;               U[11] = x[5];
                 }
             }
-            if (wl && lead) wl[8] = wall_clock64();
             if (lead) {
                 double Tn[16];
                 for (int r = 0; r < 4; r++)
@@ -718,8 +694,6 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
             __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             st->ns = ns;
             st->t_live += wall_clock64() - t0k;
-            if (a.stamps_it && launches < ICP_STAMP_LAUNCHES)
-                a.stamps_it[12 * ((size_t)launches * gridDim.x * (BS / 64) + (size_t)blockIdx.x * (BS / 64)) + 3] = wall_clock64();
             st->done = stop ? 1 : 0;          // visible to the next launch through the kernel boundary
         }
         if (a.ms_scales > 0 && stop) {        // (wave-uniform) the scale is over: keep its result; not the last one: the pair goes on by itself
@@ -871,7 +845,6 @@ __device__ static inline void d_icp_fused(const IcpArgs &a) {
     if (tid < (int)(sizeof(OctMeta) / 4)) ((int *)&m)[tid] = mword;
     if (tid == 0) n_rec = 0;
     __syncthreads();
-    const unsigned long long t_p = wall_clock64() - t_entry;
     // ---- phase A: per point -- certificate or a place in the pending list.  The listed points of ALL the lane's queries are requested first
     // (one round trip for the lane), and the moment a neighbour is decided its normal is requested for phase C.
     float4 ltp[PPL][PCR_NN_K];
@@ -921,7 +894,6 @@ __device__ static inline void d_icp_fused(const IcpArgs &a) {
         if (mine) cand_l[p * FUSED_BS + tid] = cand;
     }
     __syncthreads();
-    const unsigned long long t_a = wall_clock64() - t_entry;
     // ---- phase B: the pending list, one query per octet, 64 per round (one query per LANE through the cell hash was measured: divergent
     // per-lane scans, 47 us against 27 us per launch at the coarsest scale)
     const int npend = n_rec;
@@ -951,7 +923,7 @@ __device__ static inline void d_icp_fused(const IcpArgs &a) {
         int start_pt = 0; float d1 = 0, d2 = 0;
         int best; int nnk[PCR_NN_K];
         if (GRID) { grid_nn_query8<PCR_NN_K>(a.grid, gmask, a.tgt_pts, live, qx, qy, qz, a.r2s, ol, nnk, &d1, &d2); best = nnk[0]; start_pt = hint >= 0 ? hint : 0; }
-        else best = oct_nn_query<OPB>(a.tgt, m, stk, live, qx, qy, qz, a.r2s, hint, ol, oct, ob, &start_pt, nullptr, &d1, &d2);
+        else best = oct_nn_query<OPB>(a.tgt, m, stk, live, qx, qy, qz, a.r2s, hint, ol, oct, ob, &start_pt, &d1, &d2);
         if (ol == 0 && live) {
             const int qi = tile0 + l;
             if (GRID) {
@@ -968,7 +940,6 @@ __device__ static inline void d_icp_fused(const IcpArgs &a) {
         }
     }
     __syncthreads();
-    const unsigned long long t_b = wall_clock64() - t_entry;
     // ---- phase C: the lane's correspondences one after the other (icp_point stores the match, or the hint when the radius test fails)
     double acc[NV];
 #pragma unroll
@@ -983,7 +954,7 @@ __device__ static inline void d_icp_fused(const IcpArgs &a) {
             icp_point<ICP_MODE_GICP>(a, T, i, ns, c, acc, &pre[p]);
         }
     }
-    icp_finish<ICP_MODE_GICP, FUSED_BS>(a, st, T, acc, nb, ns, launches, t_entry, bid, t_p, t_a, t_b);
+    icp_finish<ICP_MODE_GICP, FUSED_BS>(a, st, T, acc, nb, ns, launches, t_entry, bid);
 }
 template <int TILE_PTS, bool GRID> __global__ void __launch_bounds__(FUSED_BS) FUSED_OCC k_icp_fused(IcpArgs a) { d_icp_fused<TILE_PTS, GRID>(a); }
 // (the problem's arguments are copied out of the device buffer ONCE, by scalar loads, like by-value kernel arguments: read through the
@@ -1065,9 +1036,6 @@ static void fill_args(IcpArgs &a, const DevCloud *src, const DevCloud *tgt, doub
     a.loss = p ? p->loss : 0; a.loss_k = p ? p->loss_k : 1.0; a.a = 1.0 - (p ? p->epsilon : 1e-3);
     a.rel_fit = p ? p->relative_fitness : 1e-6; a.rel_rmse = p ? p->relative_rmse : 1e-6; a.max_it = p ? p->max_iteration : 30;
     a.single = single;
-    a.dbg_visits = (single && pcr_options().debug_visits.load(std::memory_order_relaxed)) ? 1 : 0;      // (diagnostic switches: pcr_set_option, latched from the environment once)
-    a.dbg_phase = pcr_options().icp_phase.load(std::memory_order_relaxed);
-    a.stamps_nn = nullptr; a.stamps_it = nullptr;
     a.ref = nullptr; a.rbest = nullptr; a.clist = nullptr;
     memset(&a.grid, 0, sizeof a.grid); a.grid.L = -1;
 }
@@ -1146,12 +1114,6 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
     const bool grid = a.grid.tab != nullptr;
     IcpInit in; memcpy(in.T, T0, sizeof in.T);
     PCR_LAUNCH(ctx, k_icp_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
-    static const char *const stamp_path = getenv("PCR_ICP_STAMPS");          // diagnostics only (latched once)
-    const size_t sw_nn = (size_t)ICP_STAMP_LAUNCHES * nbnn * (ICP_BS / 64) * 2, sw_it = (size_t)ICP_STAMP_LAUNCHES * nbmax * (LIN_BS / 64) * 12;
-    if (stamp_path) {
-        if (hipMalloc(&a.stamps_nn, sw_nn * 8) != hipSuccess || hipMalloc(&a.stamps_it, sw_it * 8) != hipSuccess) return PCR_ENOMEM;
-        PCR_HIP_CHECK(ctx, hipMemsetAsync(a.stamps_nn, 0, sw_nn * 8, ctx->stream)); PCR_HIP_CHECK(ctx, hipMemsetAsync(a.stamps_it, 0, sw_it * 8, ctx->stream));
-    }
 
     // Launch in chunks; the state of chunk c is copied back while chunk c+1 is already queued, so the GPU never
     // idles on the host.  Launches after 'done' return at their first instruction.
@@ -1166,7 +1128,7 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
     // (round 5: also for the 0.5-1.6M-point scales of config 5, which ran three streaming kernels per iteration -- certificates, one pending
     // list for the cloud, tile linearisation -- while 17 % of their queries were searched again per launch; with list certificates it is 3 %
     // and the one kernel is the faster form there too: 167 against 184 us per launch, 26.7 against 26.4 pairs/s.  The streaming kernels are gone.)
-    const bool fused = use_fused && a.ref && !use_cov && !stamp_path && nbf <= 4096;
+    const bool fused = use_fused && a.ref && !use_cov && nbf <= 4096;
     auto enqueue = [&](int launch_index) {
         if (fused && launch_index > 0) {
             PCR_FUSED_LAUNCH(ctx, k_icp_fused, grid, tile_pts, dim3(nbf), a);
@@ -1175,13 +1137,12 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
         if (grid) PCR_LAUNCH(ctx, k_icp_nn<true>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
         else PCR_LAUNCH(ctx, k_icp_nn<false>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
         if (use_cov) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP_COV>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
-        else if (stamp_path) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
         else PCR_LAUNCH(ctx, k_icp_lin, dim3(nblin), dim3(LIN_BS), 0, ctx->stream, a);
     };
     // graph of a chunk of `len` launches: which = 0 starts with launch 0 (cold search + linearisation), which = 1 holds later launches only
     auto graph_for = [&](int which, int len, hipGraphExec_t *out) -> int {
         *out = nullptr;
-        if (!use_graph || stamp_path) return PCR_OK;
+        if (!use_graph) return PCR_OK;
         std::string key((const char *)&a, sizeof a);
         const int extra[7] = {nbnn, nbmax, use_cov ? 1 : 0, len, fused ? nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0};
         key.append((const char *)extra, sizeof extra);
@@ -1253,16 +1214,6 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
         ctx->prof[5] += launched; ctx->prof[13] += fin.launches;          // issued / live launches of the loop: the rest returned at once
         ctx->prof[6] += (double)fin.t_dbg[0] * 0.01; ctx->prof[7] += (double)fin.t_dbg[3] * 0.01; ctx->prof[14] += (double)fin.t_dbg[1] * 0.01;
         ctx->prof[11] += (double)fin.searched;
-        if (pcr_options().debug_stamps.load(std::memory_order_relaxed)) fprintf(stderr, "icp stamps (us/launch): slowest-wg search %.1f slowest-wg reduce %.1f (unused %.1f) sums-done %.1f end %.1f (launches %d ns %d)\n", fin.t_dbg[0] * 0.01 / fin.launches, fin.t_dbg[1] * 0.01 / fin.launches, fin.t_dbg[2] * 0.01 / fin.launches, fin.t_dbg[3] * 0.01 / fin.launches, fin.t_live * 0.01 / fin.launches, fin.launches, fin.ns);
-    }
-    if (stamp_path) {
-        unsigned long long *h = (unsigned long long *)malloc((sw_nn + sw_it) * 8);
-        (void)hipMemcpy(h, a.stamps_nn, sw_nn * 8, hipMemcpyDeviceToHost); (void)hipMemcpy(h + sw_nn, a.stamps_it, sw_it * 8, hipMemcpyDeviceToHost);
-        if (FILE *f = fopen(stamp_path, "ab")) {
-            const unsigned long long hdr[6] = {0x49435053ull, (unsigned long long)nbnn * (ICP_BS / 64), (unsigned long long)nbmax * (LIN_BS / 64), ICP_STAMP_LAUNCHES, (unsigned long long)fin.launches, (unsigned long long)fin.ns};
-            fwrite(hdr, 8, 6, f); fwrite(h, 8, sw_nn + sw_it, f); fclose(f);
-        }
-        free(h); (void)hipFree(a.stamps_nn); (void)hipFree(a.stamps_it);
     }
     state_to_result(fin, out);
     for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = "non-finite pose"; return PCR_ENUMERIC; }
@@ -1498,11 +1449,6 @@ int pcr_dev_gicp_group(pcr_context *ctx, int G, const DevCloud *const *src, cons
             ctx->prof[6] += (double)fin[g].t_dbg[0] * 0.01; ctx->prof[7] += (double)fin[g].t_dbg[3] * 0.01; ctx->prof[14] += (double)fin[g].t_dbg[1] * 0.01;
         }
         ctx->prof[5] += launched; ctx->prof[13] += longest;                // issued / live launches of the GROUP's loop (live: some pair still iterating)
-        if (pcr_options().debug_stamps.load(std::memory_order_relaxed)) {
-            double l = 0, t0 = 0, t1 = 0, t3 = 0, tl = 0;
-            for (int g = 0; g < G; g++) { l += fin[g].launches; t0 += fin[g].t_dbg[0] * 0.01; t1 += fin[g].t_dbg[1] * 0.01; t3 += fin[g].t_dbg[3] * 0.01; tl += fin[g].t_live * 0.01; }
-            fprintf(stderr, "icp group stamps (us/launch, mean over %d pairs): slowest-wg A+B+C %.1f phase %.1f sums-done %.1f end %.1f (pair-launches %.0f ns %d)\n", G, t0 / l, t1 / l, t3 / l, tl / l, l, fin[0].ns);
-        }
     }
     for (int g = 0; g < G; g++) {
         state_to_result(fin[g], &out[g]);
@@ -1527,7 +1473,7 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
     if (G < 1 || G > 32 || S < 1 || S > 8) return 1;
     static const bool use_fused_g = !(getenv("PCR_ICP_FUSED") && atoi(getenv("PCR_ICP_FUSED")) == 0);
     if (!use_fused_g || !icp_use_grid()) return 1;
-    if (pcr_options().icp_verify.load(std::memory_order_relaxed) || pcr_options().debug_visits.load(std::memory_order_relaxed)) return 1;
+    if (pcr_options().icp_verify.load(std::memory_order_relaxed)) return 1;
     for (int k = 0; k < G * S; k++) {
         if (!(max_dists[k] > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
         if (!src[k]->nrm || !tgt[k]->nrm) { ctx->err = "GICP needs normals on both clouds"; return PCR_EINVAL; }
@@ -1691,12 +1637,6 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
                 ctx->prof[0] += ms; ctx->prof[1] += chunk_last[c] - chunk_first[c];
             }
         ctx->prof[5] += launched; ctx->prof[13] += live_launches;
-    }
-    if (pcr_options().debug_stamps.load(std::memory_order_relaxed)) {
-        long long sum = 0, mx = 0;
-        for (int g = 0; g < G; g++) { long long t = 0; for (int s_ = 0; s_ < S; s_++) t += hh[(size_t)g * S + s_].launches; sum += t; mx = t > mx ? t : mx; }
-        fprintf(stderr, "icp group, all scales in one loop: %d pairs x %d scales, %d launches queued in %d chunks (%d before the last pair stopped); launches of a pair: mean %.1f, largest %lld\n",
-                G, S, launched, n_chunks, live_launches, (double)sum / G, mx);
     }
     return PCR_OK;
 }

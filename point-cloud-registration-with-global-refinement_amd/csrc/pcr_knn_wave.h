@@ -89,11 +89,10 @@ __device__ static inline float kw_boxbox_d2(const float4 lo, const float4 hi, co
 //   AT the k-th distance).  scan(nb) consumes the nb candidates staged in LDS (stage[j] = xyz + index bits, slots beyond nb at infinity).
 // The gather of a batch is issued one batch AHEAD whenever the pending point range continues (seed ranges and fat leaves are longer than
 // a batch more often than not): the scan of the current batch then hides the load latency of the next.
-struct KwStats { int tests, exact_inner, pops, leaf_hits, climbs, batches, cands, events; unsigned long long t_walk, t_stage, t_scan; int culled; };
 // Returns false when the pass was given up after `budget` batches (a wavefront whose queries lie far apart: the caller hands them over).
-template <bool INCL, bool STATS, class WorstFn, class ScanFn>
+template <bool INCL, class WorstFn, class ScanFn>
 __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStack &stk, bool live, int start_node, int start_point, float qx, float qy, float qz,
-                                      int plo, int phi, const uint8_t *keep, KwStage &stage, int budget, WorstFn worst, ScanFn scan, KwStats &st) {
+                                      int plo, int phi, const uint8_t *keep, KwStage &stage, int budget, WorstFn worst, ScanFn scan) {
     const int lane = threadIdx.x & 63, c8 = lane & 7;
     // boxes of the wavefront's queries and of each 8-lane subgroup
     float sglo[3] = {live ? qx : 3.4e38f, live ? qy : 3.4e38f, live ? qz : 3.4e38f};
@@ -112,7 +111,6 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
         bool pass = false; int f = 0, c = 0; float d2 = __builtin_inff();
         float4 lo = make_float4(0, 0, 0, 0), hi = make_float4(0, 0, 0, 0);
         if (lane < OCT) stk.cd2[li][lane] = 0x7f800000u;
-        if (STATS) st.tests++;
         const float wsub = pcr_octet_max(worst());
         if (c8 < cnt) {
             const size_t j = (size_t)(m.off[li] + cs + c8);
@@ -137,7 +135,6 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
             int keep = 0;
             for (int mm = cmask; mm != 0; mm &= mm - 1) {
                 const int cc = __builtin_ctz((unsigned)mm);
-                if (STATS) st.exact_inner++;
                 const float4 blo = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo.x), cc)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo.y), cc)),
                                                __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo.z), cc)), 0.0f);
                 const float4 bhi = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi.x), cc)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi.y), cc)),
@@ -194,7 +191,6 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
     int4 u_pre = make_int4(0, 0, 1, 0);                         // up-link of `anc`, loaded when anc is set (one round trip less per climb)
     for (;;) {
         bool done = false;
-        const unsigned long long tw0 = STATS ? __builtin_readcyclecounter() : 0ull;
         for (;;) {
             while (r0c > 0 && nb < 64) {
                 const int take = r0c < 64 - nb ? r0c : 64 - nb;
@@ -219,7 +215,6 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
                 const int4 u = u_pre;
                 const int ux = __builtin_amdgcn_readfirstlane(u.x), uy = __builtin_amdgcn_readfirstlane(u.y), uz = __builtin_amdgcn_readfirstlane(u.z);
                 const int nm = test(anc_li, uy, uz);
-                if (STATS) st.climbs++;
                 li = anc_li; base_li = anc_li; cs = uy;
                 mask = nm & ~(1 << (anc - uy));
                 anc = ux; anc_li++;
@@ -229,23 +224,19 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
             const int c = pop(li, mask);
             if (c < 0) { mask = 0; continue; }
             mask &= ~(1 << c);
-            if (STATS) st.pops++;
             const int nf = __builtin_amdgcn_readfirstlane(stk.first[li][c]), nc = __builtin_amdgcn_readfirstlane(stk.count[li][c]);
             if (li == 1) {
                 // a fat leaf is staged only when its box meets the ball of some lane (exact test; the boxes of the current list are in LDS)
                 const float4 lo = stk.leafbox[c][0], hi = stk.leafbox[c][1];
                 const float bd2 = pcr_box_d2(lo, hi, qx, qy, qz);
-                if (__ballot(beats(bd2, worst())) != 0ull) { add_clipped(nf, nc); if (STATS) st.leaf_hits++; }
+                if (__ballot(beats(bd2, worst())) != 0ull) add_clipped(nf, nc);
             } else {
                 if (lane == 0) { stk.cs[li] = cs; stk.mask[li] = mask; }
                 li--; cs = nf;
                 mask = test(li, nf, nc);
             }
         }
-        const unsigned long long tw1 = STATS ? __builtin_readcyclecounter() : 0ull;
-        if (STATS) st.t_walk += tw1 - tw0;
         if (nb > 0) {
-            if (STATS) { st.batches++; st.cands += nb; }
             if (--budget < 0) return false;
             const float inf = __builtin_inff();
             float4 p = make_float4(inf, inf, inf, 0.0f);        // empty slots and points outside `keep` are staged at infinity
@@ -269,10 +260,7 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
             __builtin_amdgcn_wave_barrier();
             stage.x[slot] = in ? p.x : inf; stage.y[slot] = in ? p.y : inf; stage.z[slot] = in ? p.z : inf; stage.i[slot] = __float_as_int(p.w);
             __builtin_amdgcn_wave_barrier();
-            unsigned long long ts0 = 0;
-            if (STATS) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ts0 = __builtin_readcyclecounter(); st.t_stage += ts0 - tw1; st.culled += nb - nkeep; }
             if (nkeep > 0) scan(nkeep);
-            if (STATS) st.t_scan += __builtin_readcyclecounter() - ts0;
             nb = nx; pre_n = nx; bidx = nidx;
         }
         if (done && nb == 0) return true;
@@ -281,7 +269,7 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
 
 // PK: packed float32 distance math (v_pk_add / v_pk_mul / v_pk_fma, two candidates per instruction): 10 % fewer VALU instructions, but 7 % MORE
 // wave-cycles and 1-3 % fewer pairs/s (measured, interleaved A/B) -- packed float32 issues at half rate here.  Off.
-template <int MODE, int K, bool STATS = false, bool PK = false>
+template <int MODE, int K, bool PK = false>
 __device__ static inline void d_knn_wave(const KnnArgs &a) {
     constexpr int WPB = KW_BS / 64;
     __shared__ OctMeta m;
@@ -305,8 +293,6 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
     // the query's k-best row: MODE_SOR / MODE_NORMALS -> a.list_idx with a.list_pitch entries per row (indexed like the outputs), MODE_DEBUG -> dbg_idx
     int32_t *const row = MODE == KNN_MODE_DEBUG ? a.dbg_idx + (size_t)qi * a.k : a.list_idx + (size_t)(MODE == KNN_MODE_SOR ? qi : oq) * a.list_pitch;
 
-    KwStats st1 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st2 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long c_begin = STATS ? __builtin_readcyclecounter() : 0ull;
     // ---- the lane's k smallest squared distances, DESCENDING (sd[0] = the bound); slots beyond k and lanes without a query hold -1
     float sd[K];
 #pragma unroll
@@ -373,7 +359,6 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
             for (int u = 0; u < KW_STEP; u++) {
             const float d2 = d4[u];
             if (__ballot(d2 < sd[0]) != 0ull) {
-                if (STATS) st1.events++;
                 sh.log[nlog < KwShared<K>::LOG ? nlog : KwShared<K>::LOG - 1] = i4[u];      // all lanes, one address, one value
                 nlog = __builtin_amdgcn_readfirstlane(nlog + 1);
                 insert(d2);
@@ -385,14 +370,13 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
     // through the neighbourhoods of each: ~1 % of the wavefronts took 3-6x the mean and set the length of the launch.  They stop after
     // a.wave_budget batches (or when the log is full) and flag their queries in a.hard for the octet kernel, which serves 8 per wavefront.
     const bool handing = a.hard || a.hard_list;
-    const bool finished = kw_pass<false, STATS>(a.t, m, sh.stk, live, start_node, g0, q.x, q.y, q.z, plo, phi, a.keep, sh.stage, handing ? a.wave_budget : 0x7fffffff, [&]() { return sd[0]; }, scan1, st1);
+    const bool finished = kw_pass<false>(a.t, m, sh.stk, live, start_node, g0, q.x, q.y, q.z, plo, phi, a.keep, sh.stage, handing ? a.wave_budget : 0x7fffffff, [&]() { return sd[0]; }, scan1);
     if (handing) {
         const bool give_up = !finished || nlog > KwShared<K>::LOG;      // (wave-uniform)
         if (a.hard) { if (qi < n) a.hard[oq] = (give_up && live) ? 1 : 0; }
         else if (give_up && lane == 0) a.hard_list[atomicAdd(a.hard_count, 1)] = g0;      // one atomic per wavefront that gives up (~1 %)
         if (give_up) return;
     }
-    const unsigned long long c_mid = STATS ? __builtin_readcyclecounter() : 0ull;
 
     // ---- pass 2: indices under the final bound.  `ties` = how many list entries equal the bound: that many candidates AT the bound belong
     // to the k-best (a radius-capped list that is not full takes none: its bound is the cap itself)
@@ -436,7 +420,6 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
             const float d2 = d4[u];
             const bool le = d2 <= bound;
             if (__ballot(le) != 0ull) {
-                if (STATS) st2.events++;
                 const bool eq = d2 == bound;
                 const bool take = le && (!eq || tcnt < ties) && cnt < k;
                 if (take) row[cnt] = i4[u];
@@ -459,22 +442,10 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
             __builtin_amdgcn_wave_barrier();
             sh.stage.x[lane] = p.x; sh.stage.y[lane] = p.y; sh.stage.z[lane] = p.z; sh.stage.i[lane] = __float_as_int(p.w);
             __builtin_amdgcn_wave_barrier();
-            if (STATS) { st2.batches++; st2.cands += nb; }
             scan2(nb);
         }
-    } else kw_pass<true, STATS>(a.t, m, sh.stk, live, start_node, g0, q.x, q.y, q.z, plo, phi, a.keep, sh.stage, 0x7fffffff, [&]() { return bound; }, scan2, st2);
+    } else kw_pass<true>(a.t, m, sh.stk, live, start_node, g0, q.x, q.y, q.z, plo, phi, a.keep, sh.stage, 0x7fffffff, [&]() { return bound; }, scan2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the rows this wavefront has just stored are read back below
-    if (STATS && a.stamps && lane == 0) {                       // diagnostics (PCR_KNNW_STATS): 24 words per wavefront
-        unsigned long long *w = a.stamps + 24 * (size_t)(g0 / 64);
-        const unsigned long long c_end = __builtin_readcyclecounter();
-        w[0] = c_mid - c_begin; w[1] = c_end - c_mid; w[2] = wall_clock64(); w[3] = (unsigned long long)st1.culled;
-        const KwStats *ss[2] = {&st1, &st2};
-        for (int h = 0; h < 2; h++) {
-            w[4 + 8 * h] = ss[h]->tests; w[5 + 8 * h] = ss[h]->exact_inner; w[6 + 8 * h] = ss[h]->pops; w[7 + 8 * h] = ss[h]->leaf_hits;
-            w[8 + 8 * h] = ss[h]->climbs; w[9 + 8 * h] = ss[h]->batches; w[10 + 8 * h] = ss[h]->cands; w[11 + 8 * h] = ss[h]->events;
-        }
-        w[20] = st1.t_walk; w[21] = st1.t_stage; w[22] = st1.t_scan; w[23] = c_end - c_mid;
-    }
 
     // ---- epilogue in float64 on the selected neighbours (inputs are exact float32 -> same values as the oracle), one query per lane
     const double qx = q.x, qy = q.y, qz = q.z;
@@ -543,6 +514,6 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
 // spill 617 pairs/s, 4 wavefronts 643, 5 wavefronts, 96 VGPRs and 64 spilled 588)
 #define KW_OCC(K) __attribute__((amdgpu_waves_per_eu(K <= 32 ? 4 : 2, K <= 32 ? 4 : 3)))
 template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave(KnnArgs a) { d_knn_wave<MODE, K>(a); }
-template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_stats(KnnArgs a) { d_knn_wave<MODE, K, true>(a); }
 template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_batch(KnnBatch b) { d_knn_wave<MODE, K>(b.a[blockIdx.y]); }
-template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_batchp(const KnnArgs *a) { d_knn_wave<MODE, K>(a[blockIdx.y]); }
+// (device-pointer form: the body inlined by force, as in k_knn_batchp)
+template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn_wave<MODE, K>(a[blockIdx.y]); }

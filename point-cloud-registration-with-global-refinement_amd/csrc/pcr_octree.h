@@ -115,8 +115,7 @@ __device__ static inline bool oct_ball_in_cell(const OctMeta &m, uint32_t ix, ui
 template <int OPB, class BoundFn, class VisitFn, class SkipFn>
 __device__ static inline void oct_search(const OctView &t, const OctMeta &m, OctStack<OPB> &stk, bool live, int start_node, int start_li,
                                          int s_first, int s_count, uint64_t s_key, int s_parent, int s_sib, int s_nsib,
-                                         float qx, float qy, float qz, BoundFn bound, VisitFn visit, SkipFn skip, int ol, int oct, int ob,
-                                         int *visits) {
+                                         float qx, float qy, float qz, BoundFn bound, VisitFn visit, SkipFn skip, int ol, int oct, int ob) {
     bool done = !live || m.nl < 1;
     // ---- the start node's own points (a leaf, or a level-1 node taken as one fat leaf)
     visit(done ? 0 : s_first, done ? 0 : s_count);
@@ -148,7 +147,6 @@ __device__ static inline void oct_search(const OctView &t, const OctMeta &m, Oct
             int f, c;
             const uint32_t nm = oct_test_nodes(t, m, ascend, anc_li, pf, pc, qx, qy, qz, bound(), ol, oct, f, c);
             if (ascend) {
-                if (visits) *visits += 1 << 10;
                 li = anc_li; base_li = anc_li; cs = pf;
                 mask = nm & ~(1u << (anc - pf));
                 anc = p; anc_li++;
@@ -169,8 +167,7 @@ __device__ static inline void oct_search(const OctView &t, const OctMeta &m, Oct
                 const size_t j = (size_t)(m.off[li] + cs + pc_);
                 nf = __float_as_int(t.nodes[2 * j].w); nc = __float_as_int(t.nodes[2 * j + 1].w);
             }
-            if (visits) *visits += 1;
-            if (li == 0) { if (!skip(nf, nc)) { vf = nf; vc = nc; if (visits) *visits += 1 << 20; } }
+            if (li == 0) { if (!skip(nf, nc)) { vf = nf; vc = nc; } }
             else {
                 if (ol == 0) { stk.cs[li][ob] = cs; stk.mask[li][ob] = (unsigned char)mask; }
                 li--; cs = nf; dcs = nf; dcnt = nc; descend = true;
@@ -457,7 +454,7 @@ __device__ static inline float wave_or_octets_max(float v) { return pcr_xoct_max
 // skip(first, count) -> leaf already covered.  q*: this lane's query; live: octet-uniform.
 template <class WorstFn, class VisitFn, class SkipFn>
 __device__ static inline void oct_search_group(const OctView &t, const OctMeta &m, OctGroupStack &stk, bool live, int start_leaf,
-                                               float qx, float qy, float qz, WorstFn worst, VisitFn visit, SkipFn skip, int ol, int *visits) {
+                                               float qx, float qy, float qz, WorstFn worst, VisitFn visit, SkipFn skip, int ol) {
     if (m.nl < 1 || __ballot(live) == 0ull) return;
     // group box (live queries only)
     float glo[3] = {live ? qx : 3.4e38f, live ? qy : 3.4e38f, live ? qz : 3.4e38f};
@@ -539,7 +536,6 @@ __device__ static inline void oct_search_group(const OctView &t, const OctMeta &
         if (c < 0) { mask = 0; continue; }
         mask &= ~(1 << c);
         const int nf = stk.first[li][c], nc = stk.count[li][c];
-        if (visits) *visits += 1;
         if (li == 0) { if (!skip(nf, nc)) visit(nf, nc); }
         else {
             stk.cs[li] = cs; stk.mask[li] = mask;

@@ -1,7 +1,7 @@
 """Scan the gfx950 code objects of the library for a packed-FP32 instruction (v_pk_*_f32, v_pk_mov_b32) that reads the result of a
 transcendental instruction (v_rsq / v_rcp / v_sqrt / v_exp / v_log / v_sin / v_cos) within a few instructions of it.
 
-Why: round 5 measured (tools/lab/fpfh_race.py) that on MI355X such a pair can read a STALE register in one half of the
+Why: round 5 measured that on MI355X such a pair can read a STALE register in one half of the
 packed operation when other wavefronts keep the SIMD's transcendental pipe busy (the compiler separates the two by one wait state,
 s_nop 0; alone on the chip that is enough, next to kernels issuing float64 transcendentals it is not).  pcr_fgr.hip is therefore built
 with -fno-slp-vectorize (no packed FP32 at all); this scan is the check for the other translation units.
