@@ -68,6 +68,19 @@ typedef struct {
     int32_t max_iteration;
 } pcr_gicp_params;
 
+/* == TransformationEstimationPointToPoint(with_scaling) / TransformationEstimationPointToPlane(kernel) + ICPConvergenceCriteria(...)
+ *    (Open3D registration_icp; the reference itself only calls the GICP estimator)                                             */
+typedef enum { PCR_ICP_POINT_TO_POINT = 1, PCR_ICP_POINT_TO_PLANE = 2 } pcr_icp_estimation;
+typedef struct {
+    int32_t estimation;       /* pcr_icp_estimation */
+    int32_t with_scaling;     /* point-to-point: also estimate a uniform scale (Umeyama) */
+    int32_t loss;             /* point-to-plane: pcr_loss_kind of the robust kernel */
+    double loss_k;            /* GMLoss k */
+    double relative_fitness;
+    double relative_rmse;
+    int32_t max_iteration;
+} pcr_icp_params;
+
 /* per-scale record of pcr_multiscale_gicp (what the roofline byte model needs) */
 typedef struct {
     int64_t n_voxel[2];       /* D_k: source, target after voxel_down_sample           */
@@ -134,6 +147,15 @@ int pcr_registration_generalized_icp_cov(pcr_context *ctx, const float *src_xyz,
                                          const float *tgt_xyz, const float *tgt_cov6, int64_t n_tgt,
                                          double max_correspondence_distance, const double *init_T,
                                          const pcr_gicp_params *params, pcr_result *result, int32_t *correspondences);
+
+/* == registration_icp(..., TransformationEstimationPointToPoint(with_scaling) / TransformationEstimationPointToPlane(kernel), criteria)
+ *    (Open3D RegistrationICP; the reference itself only uses GICP).  The loop of pcr_registration_generalized_icp with the
+ *    estimator's update: point-to-plane r = (T p - t).n over the target normals AS GIVEN (tgt_normals required, not normalised),
+ *    weighted by the kernel, 6x6 LDLT; point-to-point Eigen::umeyama of the correspondences (a scaled pose when with_scaling).
+ *    tgt_normals is optional for point-to-point, which does not read it.  correspondences optional device int32 [n_src x 2]. */
+int pcr_registration_icp(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
+                         int64_t n_tgt, double max_correspondence_distance, const double *init_T,
+                         const pcr_icp_params *params, pcr_result *result, int32_t *correspondences);
 
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)

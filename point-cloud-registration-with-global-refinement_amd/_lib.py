@@ -29,6 +29,14 @@ class PcrGicpParams(C.Structure):
                 ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
 
 
+ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 1, 2          # pcr_icp_estimation
+
+
+class PcrIcpParams(C.Structure):
+    _fields_ = [("estimation", C.c_int32), ("with_scaling", C.c_int32), ("loss", C.c_int32), ("loss_k", C.c_double),
+                ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -74,6 +82,7 @@ EXPORTS = [
     "pcr_compute_fpfh_feature", "pcr_registration_fgr", "pcr_debug_knn", "pcr_debug_gicp_linearize",
     "pcr_profile_enable", "pcr_profile_read", "pcr_registration_generalized_icp_cov", "pcr_register_pairs", "pcr_pool_profile",
     "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists",
+    "pcr_registration_icp",
 ]
 
 _lib = None

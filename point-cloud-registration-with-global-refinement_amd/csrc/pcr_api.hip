@@ -444,6 +444,33 @@ extern "C" int pcr_registration_generalized_icp(pcr_context *ctx, const float *s
     });
 }
 
+extern "C" int pcr_registration_icp(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
+                                    int64_t n_tgt, double max_dist, const double *init_T, const pcr_icp_params *params, pcr_result *result,
+                                    int32_t *correspondences) {
+    return pcr_api_call(ctx, [&]() -> int {
+    if (!params || !result || n_src < 0 || n_tgt < 0) return PCR_EINVAL;
+    const bool p2pl = params->estimation == PCR_ICP_POINT_TO_PLANE;
+    if (!p2pl && params->estimation != PCR_ICP_POINT_TO_POINT) { ctx->err = "unknown estimation (pcr_icp_estimation)"; return PCR_EINVAL; }
+    if (!(max_dist > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
+    if (p2pl && !tgt_normals) { ctx->err = "point-to-plane ICP requires normals on the target"; return PCR_EINVAL; }
+    if ((n_src > 0 && !src_xyz) || (n_tgt > 0 && !tgt_xyz)) { ctx->err = "missing cloud"; return PCR_EINVAL; }
+    PCR_TRY(check_T(ctx, init_T));
+    PCR_TRY(pcr_arena_reserve(ctx, pcr_scratch_bytes_for(n_src) + pcr_scratch_bytes_for(n_tgt)));
+    DevCloud s, t; uint32_t *sperm = nullptr, *tperm = nullptr;
+    PCR_TRY(pcr_import_cloud(ctx, src_xyz, nullptr, n_src, &s, &sperm, false));
+    // (normals given to point-to-point are imported but not read: a problem then has the same scratch layout under either estimator)
+    PCR_TRY(pcr_import_cloud(ctx, tgt_xyz, tgt_normals, n_tgt, &t, &tperm, p2pl));
+    int32_t *match = arena<int32_t>(ctx, n_src > 0 ? n_src : 1);
+    if (!match) return PCR_ENOMEM;
+    PCR_TRY(pcr_dev_icp(ctx, &s, &t, max_dist, init_T, params, result, match));
+    if (correspondences) {
+        int64_t nc = 0;
+        PCR_TRY(pcr_dev_compact_matches(ctx, match, s.n, s.cap, sperm, tperm, correspondences, &nc));
+    }
+    return PCR_OK;
+    });
+}
+
 __global__ void k_gather_cov6(const float *__restrict__ src, const uint32_t *__restrict__ perm, int n, float *__restrict__ dst) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;

@@ -26,7 +26,9 @@
 #define LIN_BS 512           // linearise kernel: few fat workgroups => few partial rows for the last one to gather
 #define LIN_MAX_BLOCKS 128
 
-enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2 };   // _COV: per-point covariances given (GICP_robusto path)
+// _COV: per-point covariances given (GICP_robusto path); P2PL / P2P / P2P_SCALED: registration_icp with TransformationEstimationPointToPlane /
+// PointToPoint(with_scaling = false / true) -- k_icp_nn + k_icp_iter<MODE> only, never the fused or group forms
+enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2, ICP_MODE_P2PL = 3, ICP_MODE_P2P = 4, ICP_MODE_P2P_SCALED = 5 };
 
 struct IcpState {
     double T[16];
@@ -222,6 +224,80 @@ __device__ static inline void icp_sym3_inv_sqrt(const double *M6 /*xx,xy,xz,yy,y
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) W[i * 3 + j] = v[i][0] * v[j][0] * l0 + v[i][1] * v[j][1] * l1 + v[i][2] * v[j][2] * l2;
+}
+
+// Eigen::umeyama(source, target, with_scaling) (Eigen >= 3.3, what TransformationEstimationPointToPoint returns) from the float64 moments of the
+// n pairs (icp_point, P2P modes): M[0..2] = sum u, M[3..5] = sum v, M[6..14] = sum v u^T (row-major), M[15] = sum |u|^2, u = q - o, v = t - o.
+// sigma = cov(v, u); R = the rotation that maximises tr(R^T sigma), i.e. Umeyama's U S V^T with the reflection fixed, found as Horn's unit
+// quaternion: the eigenvector of the largest eigenvalue of the symmetric 4x4 N(sigma), by cyclic Jacobi in float64 with static indexing only
+// (registers); for sigma of rank >= 2 the same R.  c = tr(R^T sigma) / var(u) = tr(D S) / var(u) (1 without scaling), t = mean t - c R mean q.
+__host__ __device__ static inline void icp_umeyama(const double *M, double n, const double *o, bool scaling, double *U) {
+    const double inv = 1.0 / n;
+    const double mu[3] = {M[0] * inv, M[1] * inv, M[2] * inv}, mv[3] = {M[3] * inv, M[4] * inv, M[5] * inv};
+    double sg[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) sg[r][c] = M[6 + 3 * r + c] * inv - mv[r] * mu[c];
+    const double var = M[15] * inv - (mu[0] * mu[0] + mu[1] * mu[1] + mu[2] * mu[2]);
+    // Horn's S_ab = sum u_a v_b = sigma[b][a]
+    const double Sxx = sg[0][0], Sxy = sg[1][0], Sxz = sg[2][0], Syx = sg[0][1], Syy = sg[1][1], Syz = sg[2][1], Szx = sg[0][2], Szy = sg[1][2], Szz = sg[2][2];
+    double a[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                      {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                      {Szx - Sxz, Sxy + Syx, Syy - Sxx - Szz, Syz + Szy},
+                      {Sxy - Syx, Szx + Sxz, Syz + Szy, Szz - Sxx - Syy}};
+    double v[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < 16; sweep++) {
+        double off = 0, tot = 0;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            tot += a[p][p] * a[p][p];
+#pragma unroll
+            for (int q = p + 1; q < 4; q++) off += a[p][q] * a[p][q];
+        }
+        if (!(off > 1e-36 * tot)) break;
+#pragma unroll
+        for (int pq = 0; pq < 6; pq++) {
+            const int p = pq < 3 ? 0 : (pq < 5 ? 1 : 2), q = pq < 3 ? pq + 1 : (pq < 5 ? pq - 1 : 3);
+            const double apq = a[p][q];
+            if (apq != 0.0) {
+                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+#pragma unroll
+                for (int k = 0; k < 4; k++) { const double akp = a[k][p], akq = a[k][q]; a[k][p] = c * akp - sn * akq; a[k][q] = sn * akp + c * akq; }
+#pragma unroll
+                for (int k = 0; k < 4; k++) { const double apk = a[p][k], aqk = a[q][k]; a[p][k] = c * apk - sn * aqk; a[q][k] = sn * apk + c * aqk; }
+#pragma unroll
+                for (int k = 0; k < 4; k++) { const double vkp = v[k][p], vkq = v[k][q]; v[k][p] = c * vkp - sn * vkq; v[k][q] = sn * vkp + c * vkq; }
+            }
+        }
+    }
+    double lmax = a[0][0], w = v[0][0], x = v[1][0], y = v[2][0], z = v[3][0];      // largest eigenvalue (ties: the lower column)
+#pragma unroll
+    for (int k = 1; k < 4; k++)
+        if (a[k][k] > lmax) { lmax = a[k][k]; w = v[0][k]; x = v[1][k]; y = v[2][k]; z = v[3][k]; }
+    const double qn = 1.0 / sqrt(w * w + x * x + y * y + z * z);
+    w *= qn; x *= qn; y *= qn; z *= qn;
+    const double R[3][3] = {{w * w + x * x - y * y - z * z, 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
+                            {2.0 * (x * y + w * z), w * w - x * x + y * y - z * z, 2.0 * (y * z - w * x)},
+                            {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), w * w - x * x - y * y + z * z}};
+    double c = 1.0;
+    if (scaling) {
+        double tr = 0;
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) tr += R[r][k] * sg[r][k];
+        c = tr / var;
+    }
+    const double ms[3] = {mu[0] + o[0], mu[1] + o[1], mu[2] + o[2]}, md[3] = {mv[0] + o[0], mv[1] + o[1], mv[2] + o[2]};
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        U[r * 4 + 0] = c * R[r][0]; U[r * 4 + 1] = c * R[r][1]; U[r * 4 + 2] = c * R[r][2];
+        U[r * 4 + 3] = md[r] - c * (R[r][0] * ms[0] + R[r][1] * ms[1] + R[r][2] * ms[2]);
+    }
+    U[12] = 0; U[13] = 0; U[14] = 0; U[15] = 1;
 }
 
 // 6x6 symmetric solve on ONE lane.  Fast path: LDL^T without pivoting, fully unrolled so that every array lives in
@@ -523,6 +599,36 @@ __device__ static inline void icp_point(const IcpArgs &a, const double *T, int i
                         r2 += r * r;
                     }
                     acc[27] += r2;
+                } else if (MODE == ICP_MODE_P2PL) {
+                    // TransformationEstimationPointToPlane: r = (q - t).n, J = [q x n; n] with the target normal AS STORED (not normalised)
+                    const float4 tn = a.tgt_nrm[best];
+                    const double nx = tn.x, ny = tn.y, nz = tn.z;
+                    double J[6];
+                    J[0] = qy * nz - qz * ny; J[1] = qz * nx - qx * nz; J[2] = qx * ny - qy * nx;
+                    J[3] = nx; J[4] = ny; J[5] = nz;
+                    const double r = nx * dx + ny * dy + nz * dz;
+                    const double w = icp_weight(a.loss, a.loss_k, r);
+                    int t = 0;
+#pragma unroll
+                    for (int p = 0; p < 6; p++) {
+                        const double wj = w * J[p];
+#pragma unroll
+                        for (int q = p; q < 6; q++) acc[t++] += wj * J[q];
+                        acc[21 + p] += wj * r;
+                    }
+                    acc[27] += r * r;
+                } else if (MODE == ICP_MODE_P2P || MODE == ICP_MODE_P2P_SCALED) {
+                    // TransformationEstimationPointToPoint: the moments of the pairs (u = q - o, v = t - o about the problem's origin o = target point 0,
+                    // so that the centred moments do not cancel against coordinates far from it): [0..2] sum u, [3..5] sum v, [6..14] sum v u^T, [15] sum |u|^2
+                    const float4 o = a.tgt_pts[0];
+                    const double ux = qx - (double)o.x, uy = qy - (double)o.y, uz = qz - (double)o.z;
+                    const double vx = (double)tf.x - (double)o.x, vy = (double)tf.y - (double)o.y, vz = (double)tf.z - (double)o.z;
+                    acc[0] += ux; acc[1] += uy; acc[2] += uz;
+                    acc[3] += vx; acc[4] += vy; acc[5] += vz;
+                    acc[6] += vx * ux; acc[7] += vx * uy; acc[8] += vx * uz;
+                    acc[9] += vy * ux; acc[10] += vy * uy; acc[11] += vy * uz;
+                    acc[12] += vz * ux; acc[13] += vz * uy; acc[14] += vz * uz;
+                    acc[15] += ux * ux + uy * uy + uz * uz;
                 } else {
                     // GetInformationMatrixFromPointClouds: sum G^T G over matched TARGET points
                     const double x = tf.x, y = tf.y, z = tf.z;
@@ -645,9 +751,13 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
             st->dfit = launches > 0 ? fabs(fit_prev - fit) : 1e300; st->drmse = launches > 0 ? fabs(rmse_prev - rmse) : 1e300;
             st->fitness = fit; st->rmse = rmse; st->count = count;
         }
-        if (!stop && (MODE == ICP_MODE_GICP || MODE == ICP_MODE_GICP_COV)) {
+        if (!stop && MODE != ICP_MODE_EVAL) {
             double U[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-            if (count > 0) {
+            if (count > 0 && (MODE == ICP_MODE_P2P || MODE == ICP_MODE_P2P_SCALED)) {
+                const float4 o = a.tgt_pts[0];                 // the origin of the moments (icp_point)
+                const double org[3] = {o.x, o.y, o.z};
+                icp_umeyama(S, S[29], org, MODE == ICP_MODE_P2P_SCALED, U);
+            } else if (count > 0) {
                 double nb6[6], x[6];
 #pragma unroll
                 for (int p = 0; p < 6; p++) nb6[p] = -S[21 + p];
@@ -1071,11 +1181,15 @@ static int icp_next_chunk(const IcpState &s, double rel_fit, double rel_rmse, in
     return chunk;
 }
 
-int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,
-                 const pcr_gicp_params *p, pcr_result *out, int32_t *match_dev) {
+// The one-pair loop of every estimator: mode = ICP_MODE_GICP (GICP_COV when both clouds carry covariances), or P2PL / P2P / P2P_SCALED
+// (pcr_dev_icp), which take the same searches and the same loop through k_icp_nn + k_icp_iter<mode>
+static int icp_loop(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,
+                    const pcr_gicp_params *p, int mode, pcr_result *out, int32_t *match_dev) {
     if (!(max_dist > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
-    const bool use_cov = src->cov6 && tgt->cov6;
-    if (!use_cov && (!src->nrm || !tgt->nrm)) { ctx->err = "GICP needs normals (or covariances) on both clouds"; return PCR_EINVAL; }
+    const bool gicp = mode == ICP_MODE_GICP;
+    const bool use_cov = gicp && src->cov6 && tgt->cov6;
+    if (gicp && !use_cov && (!src->nrm || !tgt->nrm)) { ctx->err = "GICP needs normals (or covariances) on both clouds"; return PCR_EINVAL; }
+    if (mode == ICP_MODE_P2PL && !tgt->nrm) { ctx->err = "point-to-plane ICP needs normals on the target"; return PCR_EINVAL; }
     ArenaMark mark(ctx);
     const int cap = src->cap > 0 ? src->cap : 1;
     static const bool use_skip = !(getenv("PCR_ICP_SKIP") && atoi(getenv("PCR_ICP_SKIP")) == 0);
@@ -1128,7 +1242,7 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
     // (round 5: also for the 0.5-1.6M-point scales of config 5, which ran three streaming kernels per iteration -- certificates, one pending
     // list for the cloud, tile linearisation -- while 17 % of their queries were searched again per launch; with list certificates it is 3 %
     // and the one kernel is the faster form there too: 167 against 184 us per launch, 26.7 against 26.4 pairs/s.  The streaming kernels are gone.)
-    const bool fused = use_fused && a.ref && !use_cov && nbf <= 4096;
+    const bool fused = use_fused && gicp && a.ref && !use_cov && nbf <= 4096;      // (the fused kernel is the GICP linearisation only)
     auto enqueue = [&](int launch_index) {
         if (fused && launch_index > 0) {
             PCR_FUSED_LAUNCH(ctx, k_icp_fused, grid, tile_pts, dim3(nbf), a);
@@ -1137,14 +1251,18 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
         if (grid) PCR_LAUNCH(ctx, k_icp_nn<true>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
         else PCR_LAUNCH(ctx, k_icp_nn<false>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
         if (use_cov) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP_COV>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
-        else PCR_LAUNCH(ctx, k_icp_lin, dim3(nblin), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (gicp) PCR_LAUNCH(ctx, k_icp_lin, dim3(nblin), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (mode == ICP_MODE_P2PL) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2PL>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (mode == ICP_MODE_P2P) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P_SCALED>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
     };
     // graph of a chunk of `len` launches: which = 0 starts with launch 0 (cold search + linearisation), which = 1 holds later launches only
     auto graph_for = [&](int which, int len, hipGraphExec_t *out) -> int {
         *out = nullptr;
         if (!use_graph) return PCR_OK;
         std::string key((const char *)&a, sizeof a);
-        const int extra[7] = {nbnn, nbmax, use_cov ? 1 : 0, len, fused ? nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0};
+        // (the estimator is part of the key: point-to-point and point-to-plane problems have byte-identical arguments)
+        const int extra[8] = {nbnn, nbmax, use_cov ? 1 : 0, len, fused ? nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0, mode};
         key.append((const char *)extra, sizeof extra);
         for (auto &g : ctx->icp_graphs) if (g.key == key) { *out = g.exec; return PCR_OK; }
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -1195,7 +1313,7 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
         if (!enq) break;
         prev = cur; cur ^= 1;
     }
-    if (!have) { ctx->err = "GICP loop ended without a final state"; return PCR_EHIP; }
+    if (!have) { ctx->err = "ICP loop ended without a final state"; return PCR_EHIP; }
     // drain the (no-op) tail so the pinned slots and the arena can be reused safely
     PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->profiling) {
@@ -1218,6 +1336,26 @@ int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, dou
     state_to_result(fin, out);
     for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = "non-finite pose"; return PCR_ENUMERIC; }
     return PCR_OK;
+}
+
+int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,
+                 const pcr_gicp_params *p, pcr_result *out, int32_t *match_dev) {
+    return icp_loop(ctx, src, tgt, max_dist, T0, p, ICP_MODE_GICP, out, match_dev);
+}
+
+int pcr_dev_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,
+                const pcr_icp_params *p, pcr_result *out, int32_t *match_dev) {
+    int mode;
+    if (p->estimation == PCR_ICP_POINT_TO_PLANE) mode = ICP_MODE_P2PL;
+    else if (p->estimation == PCR_ICP_POINT_TO_POINT) mode = p->with_scaling ? ICP_MODE_P2P_SCALED : ICP_MODE_P2P;
+    else { ctx->err = "unknown ICP estimation (pcr_icp_estimation)"; return PCR_EINVAL; }
+    if (mode == ICP_MODE_P2PL && (p->loss < PCR_LOSS_L2 || p->loss > PCR_LOSS_GM)) { ctx->err = "unknown robust kernel (pcr_loss_kind)"; return PCR_EINVAL; }
+    // the loop's parameters; point-to-point has no kernel, so its problems carry L2 / 1 (the graph cache tells the estimators apart by mode)
+    pcr_gicp_params g;
+    memset(&g, 0, sizeof g);
+    g.loss = mode == ICP_MODE_P2PL ? p->loss : PCR_LOSS_L2; g.loss_k = mode == ICP_MODE_P2PL ? p->loss_k : 1.0; g.epsilon = 1e-3;
+    g.relative_fitness = p->relative_fitness; g.relative_rmse = p->relative_rmse; g.max_iteration = p->max_iteration;
+    return icp_loop(ctx, src, tgt, max_dist, T0, &g, mode, out, match_dev);
 }
 
 // ---- the GICP loops of a GROUP of pairs in lockstep: every launch serves all G problems (blockIdx.y = pair; argument structs and

@@ -42,6 +42,21 @@ class TransformationEstimationForGeneralizedICP:
         self.epsilon = float(epsilon)
 
 
+class TransformationEstimationPointToPoint:
+    """Open3D's default ``registration_icp`` estimator: the Umeyama fit of the correspondences (with a uniform scale when
+    ``with_scaling``)."""
+
+    def __init__(self, with_scaling: bool = False):
+        self.with_scaling = bool(with_scaling)
+
+
+class TransformationEstimationPointToPlane:
+    """Point-to-plane ICP over the target's normals, robustly weighted by ``kernel`` (L2, L1 or GM)."""
+
+    def __init__(self, kernel: RobustKernel | None = None):
+        self.kernel = kernel if kernel is not None else L2Loss()
+
+
 class ICPConvergenceCriteria:
     def __init__(self, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_iteration: int = 30):
         self.relative_fitness = float(relative_fitness)
@@ -164,10 +179,35 @@ def registration_generalized_icp(source: PointCloud, target: PointCloud, max_cor
 
 
 def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None, criteria=None):
-    """Only the GICP estimator is on the hot path (ALL_FUNCTIONS.py:220-226)."""
-    if not isinstance(estimation_method, TransformationEstimationForGeneralizedICP):
-        raise RuntimeError("registration_icp: only TransformationEstimationForGeneralizedICP is implemented on the MI355X path")
-    return registration_generalized_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)
+    """Open3D ``registration_icp``: ``estimation_method`` None is ``TransformationEstimationPointToPoint(False)``, Open3D's default;
+    the GICP estimator (ALL_FUNCTIONS.py:220-226) runs ``registration_generalized_icp``; point-to-point and point-to-plane run
+    ``pcr_registration_icp``, the same device loop with their own update."""
+    if isinstance(estimation_method, TransformationEstimationForGeneralizedICP):
+        return registration_generalized_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)
+    estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
+    if isinstance(estimation, TransformationEstimationPointToPoint):
+        p = _lib.PcrIcpParams(_lib.ICP_POINT_TO_POINT, int(estimation.with_scaling), _lib.LOSS_L2, 1.0, 0.0, 0.0, 0)
+    elif isinstance(estimation, TransformationEstimationPointToPlane):
+        p = _lib.PcrIcpParams(_lib.ICP_POINT_TO_PLANE, 0, int(estimation.kernel.kind), float(estimation.kernel.k), 0.0, 0.0, 0)
+    else:
+        raise RuntimeError(f"registration_icp: {type(estimation).__name__} is not implemented on the MI355X path")
+    criteria = criteria or ICPConvergenceCriteria()
+    p.relative_fitness, p.relative_rmse, p.max_iteration = float(criteria.relative_fitness), float(criteria.relative_rmse), int(criteria.max_iteration)
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    p2pl = p.estimation == _lib.ICP_POINT_TO_PLANE
+    if p2pl and not target.has_normals():
+        raise RuntimeError("TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal vectors for target PointCloud.")
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = len(source), len(target)
+    corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+    res = _lib.PcrResult()
+    T, Tp = _T(init)
+    ctx.check(ctx.lib.pcr_registration_icp(
+        ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), _ptr(target.device_normals() if target.has_normals() else None),
+        C.c_int64(nt), C.c_double(max_correspondence_distance), Tp, C.byref(p), C.byref(res), _ptr(corr)), "registration_icp")
+    return _result(res, corr)
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
