@@ -269,6 +269,49 @@ int pcr_registration_fgr(pcr_context *ctx, const float *src_xyz, const float *sr
                          const float *tgt_xyz, const float *tgt_feat33, int64_t n_tgt, const pcr_fgr_option *option,
                          pcr_result *result, int32_t *correspondences);
 
+/* == registration_ransac_based_on_correspondence / registration_ransac_based_on_feature_matching (Open3D 0.13 and later; the reference calls
+ *    neither, so the algorithm is stated here).  ONE sequential, deterministic loop defines the answer; the device may run it in any order.
+ *    Hypothesis i = 0, 1, ...: rows r_k = splitmix64(seed + ransac_n * i + k) % n_corres, k < ransac_n (the sampler of the FGR tuple test; repeats
+ *    allowed).  CorrespondenceCheckerBasedOnEdgeLength(thr): over every pair a < b of the sample, ls = |s_a - s_b|, lt = |t_a - t_b|, fails if
+ *    ls < lt * thr or lt < ls * thr.  T_i = Eigen::umeyama of the sampled pairs (with_scaling: a scaled pose).  CorrespondenceCheckerBasedOnDistance(thr)
+ *    fails if a sampled pair has |T s - t| > thr; CorrespondenceCheckerBasedOnNormal(thr) fails if one has (T[:3,:3] n_s) . n_t < cos(thr), and
+ *    passes when either cloud has no normals.  A hypothesis that fails a checker or has a non-finite T is invalid (it still uses up its iteration).
+ *    A valid one is scored in float64 over all rows: inliers dis = |T s - t| < max_distance, count_i, err2_i = sum dis^2 (fixed order: same bits
+ *    on every run).  i is better than the running best if count_i is larger, or equal with sqrt(err2_i / count_i) strictly smaller; count 0 is never
+ *    better than the empty start; on a full tie the earlier iteration stays.  est_k = max_iteration at the start, iteration i runs iff i < est_k; when
+ *    i becomes the best, k' = log(1 - confidence) / log(1 - (count_i / n_corres)^ransac_n) (the denominator evaluated as log1p(-rho^n), so that a tiny rho^n gives a
+ *    huge k' and not a division by zero), and if k' is finite and 0 <= k' < est_k then est_k = ceil(k').
+ *    result: transformation of the best hypothesis, fitness = count / n_corres, inlier_rmse = sqrt(err2 / count) -- over the correspondence LIST,
+ *    as Open3D (evaluate_registration gives whole-cloud figures) --, iterations = iterations run, converged = a best hypothesis exists;
+ *    correspondences (optional, device int32, capacity n_corres rows; n_src rows for the feature form) = the inlier rows of the list in input order.
+ *    Fewer rows than ransac_n: the empty result (identity, fitness 0, rmse 0), not an error.  A negative threshold = that checker is absent. */
+typedef struct {
+    int32_t ransac_n;                 /* 3..8 */
+    int32_t with_scaling;             /* TransformationEstimationPointToPoint(with_scaling) */
+    int32_t max_iteration;            /* RANSACConvergenceCriteria: 100000 */
+    double confidence;                /*                            0.999; in (0, 1], 1 never stops early */
+    uint64_t seed;
+    double edge_length_threshold;     /* CorrespondenceCheckerBasedOnEdgeLength(similarity_threshold) */
+    double distance_threshold;        /* CorrespondenceCheckerBasedOnDistance(distance_threshold) */
+    double normal_angle_threshold;    /* CorrespondenceCheckerBasedOnNormal(normal_angle_threshold), radians */
+} pcr_ransac_params;
+typedef struct {
+    int64_t iterations_run;
+    int64_t best_iteration;           /* -1: none */
+    int64_t n_valid;                  /* hypotheses among those run that passed every checker */
+    int64_t n_corres;                 /* rows of the correspondence list RANSAC ran on */
+} pcr_ransac_info;
+/* corres: device int32 [n_corres x 2] rows (source index, target index); normals optional (read by the normal checker only); info optional */
+int pcr_registration_ransac_correspondence(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *tgt_xyz,
+                                           const float *tgt_normals, int64_t n_tgt, const int32_t *corres, int64_t n_corres, double max_distance,
+                                           const pcr_ransac_params *params, pcr_result *result, int32_t *correspondences, pcr_ransac_info *info);
+/* the list is built first: every source row with its nearest target row in feature space (the exact searches of pcr_registration_fgr); with
+ * mutual_filter only the rows whose target row points back, unless fewer than ransac_n of them remain (then all rows, as Open3D) */
+int pcr_registration_ransac_feature_matching(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *src_feat33,
+                                             const float *tgt_xyz, const float *tgt_normals, int64_t n_tgt, const float *tgt_feat33, int mutual_filter,
+                                             double max_distance, const pcr_ransac_params *params, pcr_result *result, int32_t *correspondences,
+                                             pcr_ransac_info *info);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.
@@ -302,6 +345,13 @@ int pcr_debug_gicp_linearize(pcr_context *ctx, const float *src_xyz, const float
  * out_0to1 likewise.  mode 0: f16-split MFMA screen + exact float64 re-check (production; with tile pruning from ~70k rows per side),
  * 1: all-pairs float64 MFMA, 2: float32 brute force, 3 / 4: the screen with tile pruning forced on / off */
 int pcr_debug_feature_nn(pcr_context *ctx, const float *f0, int64_t n0, const float *f1, int64_t n1, int32_t *out_1to0, int32_t *out_0to1, int mode);
+
+/* what the RANSAC kernels compute for iterations [first, first + count) of pcr_registration_ransac_correspondence with these arguments, no early
+ * stop (max_iteration and confidence are not read).  All four outputs are device arrays: valid_out count bytes, T_out count x 16 float64 (zeros above
+ * the last row when the sample failed the edge-length check: no fit was made), inliers_out count int32 (-1: invalid), err2_out count float64. */
+int pcr_debug_ransac_hypotheses(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
+                                int64_t n_tgt, const int32_t *corres, int64_t n_corres, double max_distance, const pcr_ransac_params *params, int64_t first,
+                                int64_t count, uint8_t *valid_out, double *T_out, int32_t *inliers_out, double *err2_out);
 
 /* test / diagnostic switches of the process (no reference equivalent).  Each one is latched from the environment variable of the same
  * name in upper case with the PCR_ prefix when the library first needs it; this call overrides it afterwards without touching the

@@ -37,6 +37,16 @@ class PcrIcpParams(C.Structure):
                 ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
 
 
+class PcrRansacParams(C.Structure):
+    _fields_ = [("ransac_n", C.c_int32), ("with_scaling", C.c_int32), ("max_iteration", C.c_int32), ("confidence", C.c_double),
+                ("seed", C.c_uint64), ("edge_length_threshold", C.c_double), ("distance_threshold", C.c_double),
+                ("normal_angle_threshold", C.c_double)]
+
+
+class PcrRansacInfo(C.Structure):
+    _fields_ = [("iterations_run", C.c_int64), ("best_iteration", C.c_int64), ("n_valid", C.c_int64), ("n_corres", C.c_int64)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -82,7 +92,7 @@ EXPORTS = [
     "pcr_compute_fpfh_feature", "pcr_registration_fgr", "pcr_debug_knn", "pcr_debug_gicp_linearize",
     "pcr_profile_enable", "pcr_profile_read", "pcr_registration_generalized_icp_cov", "pcr_register_pairs", "pcr_pool_profile",
     "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists",
-    "pcr_registration_icp",
+    "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
 ]
 
 _lib = None

@@ -8,6 +8,7 @@
 #include <array>
 #include <vector>
 #include "pcr_octree.h"
+#include "pcr_umeyama.h"
 
 #define FB 256
 #define PI_D 3.14159265358979323846
@@ -537,6 +538,21 @@ static int feature_nn(pcr_context *ctx, const float *db, int n_db, const float *
     return PCR_OK;
 }
 
+// Both directions of the nearest-feature search as FGR and the RANSAC feature form run it: out_1to0[j] = row of f0 nearest to row j of f1 in full,
+// out_0to1 where the cross check can read it (the f16-split screen on the matrix cores + exact float64 re-check, second direction seeded by the
+// first: pcr_featnn.hip).  Fall-backs: clouds under 64 rows, feature values outside the f16 range or an exhausted record pool (PCR_ECAPACITY)
+// take feature_nn; PCR_FEATURE_NN=f64 forces that all-pairs float64 path, PCR_FEATURE_NN_BRUTE the float32 one.  want_0to1 false: the
+// fall-back leaves out_0to1 alone.
+static int feature_nn_both(pcr_context *ctx, const float *f0, int n0, const float *f1, int n1, int32_t *out_1to0, int32_t *out_0to1, bool want_0to1 = true) {
+    static const bool nn_f64 = getenv("PCR_FEATURE_NN") && !strcmp(getenv("PCR_FEATURE_NN"), "f64");
+    int nn_rc = PCR_ECAPACITY;
+    if (!nn_f64 && !getenv("PCR_FEATURE_NN_BRUTE") && n0 >= 64 && n1 >= 64) nn_rc = pcr_feature_nn_mutual(ctx, f0, n0, f1, n1, out_1to0, out_0to1, -1, 1);
+    if (nn_rc != PCR_ECAPACITY) return nn_rc;
+    PCR_TRY(feature_nn(ctx, f0, n0, f1, n1, out_1to0));
+    if (want_0to1) PCR_TRY(feature_nn(ctx, f1, n1, f0, n0, out_0to1));
+    return PCR_OK;
+}
+
 // test hook: the mutual nearest-feature search alone.  mode 0: f16-split screen + exact re-check (the production path; tile pruning
 // from ~70k rows per side), 1: all-pairs float64 MFMA, 2: float32 brute force, 3: the screen with tile pruning forced on, 4: forced off
 extern "C" int pcr_debug_feature_nn(pcr_context *ctx, const float *f0, int64_t n0, const float *f1, int64_t n1, int32_t *out_1to0, int32_t *out_0to1, int mode) {
@@ -567,13 +583,44 @@ __global__ void __launch_bounds__(FB) k_cross_emit(const int32_t *__restrict__ i
     cross[2 * (size_t)pos[i]] = i; cross[2 * (size_t)pos[i] + 1] = i_to_j[i];
 }
 
-// ======================================================================== tuple test (K8)
-__host__ __device__ static inline uint64_t pcr_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
+// ---- the correspondence list of registration_ransac_based_on_feature_matching (pcr_ransac.hip): every source row paired with its nearest
+// target row in feature space, (i, s_to_t[i]) in source order; with mutual_filter only the rows the cross check keeps, unless fewer than
+// min_rows of them remain (Open3D: "too few correspondences after mutual filter", then all rows).  The searches and their fall-backs are
+// those of fgr_pose.  corres: ns x 2 int32 (device); *n_out on the host.
+__global__ void __launch_bounds__(FB) k_corres_all(const int32_t *__restrict__ i_to_j, int n_i, int32_t *__restrict__ corres) {
+    const int i = blockIdx.x * FB + threadIdx.x;
+    if (i >= n_i) return;
+    corres[2 * (size_t)i] = i; corres[2 * (size_t)i + 1] = i_to_j[i];
 }
+size_t pcr_feature_corres_scratch_bytes(int64_t ns, int64_t nt) {
+    return pcr_feature_nn_scratch_bytes(nt, ns) + (size_t)(ns + nt) * (FK * 16 + 32 * 12 + 64 + 16) + (64u << 20);
+}
+int pcr_feature_corres(pcr_context *ctx, const float *src_feat, int ns, const float *tgt_feat, int nt, int mutual_filter, int min_rows,
+                       int32_t *corres, int64_t *n_out) {
+    *n_out = 0;
+    if (ns <= 0 || nt <= 0) return PCR_OK;
+    ArenaMark mark(ctx);
+    int32_t *s_to_t = arena<int32_t>(ctx, ns), *t_to_s = arena<int32_t>(ctx, nt);
+    uint8_t *cflags = arena<uint8_t>(ctx, ns);
+    int *cpos = arena<int>(ctx, ns), *ncross_dev = arena<int>(ctx, 1);
+    if (!s_to_t || !t_to_s || !cflags || !cpos || !ncross_dev) return PCR_ENOMEM;
+    // target = cloud 0: the first direction of the screen gives every source row its nearest target row, the second one (seeded by the
+    // first) only the target rows some source row points at -- all the cross check reads
+    PCR_TRY(feature_nn_both(ctx, tgt_feat, nt, src_feat, ns, s_to_t, t_to_s, mutual_filter != 0));
+    if (mutual_filter) {
+        PCR_LAUNCH(ctx, k_cross_flags, dim3((ns + FB - 1) / FB), dim3(FB), 0, ctx->stream, s_to_t, t_to_s, ns, cflags);
+        PCR_TRY(pcr_dev_flag_scan(ctx, cflags, nullptr, ns, cpos, ncross_dev));
+        PCR_LAUNCH(ctx, k_cross_emit, dim3((ns + FB - 1) / FB), dim3(FB), 0, ctx->stream, s_to_t, cflags, cpos, ns, corres);
+        int64_t ncross = 0;
+        PCR_TRY(pcr_read_count(ctx, ncross_dev, &ncross));
+        if (ncross >= min_rows) { *n_out = ncross; return PCR_OK; }
+    }
+    PCR_LAUNCH(ctx, k_corres_all, dim3((ns + FB - 1) / FB), dim3(FB), 0, ctx->stream, s_to_t, ns, corres);
+    *n_out = ns;
+    return PCR_OK;
+}
+
+// ======================================================================== tuple test (K8)
 struct TupleArgs {
     const double *pi, *pj;          // normalised clouds i (larger) and j, n x 3 float64
     const int32_t *cross; int ncross;
@@ -1098,15 +1145,7 @@ static int fgr_pose(pcr_context *ctx, const float *src_xyz, const float *src_fea
         if (!j_to_i || !i_to_j || !cflags || !cpos || !ncross_dev || !cross) return PCR_ENOMEM;
         hipEvent_t pe[2] = {nullptr, nullptr};
         if (ctx->profiling) { PCR_HIP_CHECK(ctx, hipEventCreate(&pe[0])); PCR_HIP_CHECK(ctx, hipEventCreate(&pe[1])); PCR_HIP_CHECK(ctx, hipEventRecord(pe[0], ctx->stream)); }
-        // both directions: f16-split screen on the matrix cores + exact float64 re-check (pcr_featnn.hip); PCR_FEATURE_NN=f64 keeps
-        // the all-pairs float64 MFMA path (also taken for feature values outside the f16 range), PCR_FEATURE_NN_BRUTE the float32 one
-        static const bool nn_f64 = getenv("PCR_FEATURE_NN") && !strcmp(getenv("PCR_FEATURE_NN"), "f64");
-        int nn_rc = PCR_ECAPACITY;
-        if (!nn_f64 && !getenv("PCR_FEATURE_NN_BRUTE") && nPti >= 64 && nPtj >= 64) nn_rc = pcr_feature_nn_mutual(ctx, fi, nPti, fj, nPtj, j_to_i, i_to_j, -1, 1);      // (only the cross check below reads the two lists)
-        if (nn_rc == PCR_ECAPACITY) {
-            PCR_TRY(feature_nn(ctx, fi, nPti, fj, nPtj, j_to_i));
-            PCR_TRY(feature_nn(ctx, fj, nPtj, fi, nPti, i_to_j));
-        } else if (nn_rc != PCR_OK) return nn_rc;
+        PCR_TRY(feature_nn_both(ctx, fi, nPti, fj, nPtj, j_to_i, i_to_j));      // (only the cross check below reads the two lists)
         if (ctx->profiling) {             // bench instrumentation: HIP-event time over the two matching passes (pcr_hip.h, out16[8..10])
             PCR_HIP_CHECK(ctx, hipEventRecord(pe[1], ctx->stream));
             PCR_HIP_CHECK(ctx, hipEventSynchronize(pe[1]));

@@ -260,6 +260,11 @@ int pcr_feature_nn_mutual(pcr_context *ctx, const float *f0, int n0, const float
 int pcr_feature_nn_mutual_batch(pcr_context *ctx, int G, const float *const *f0, const int *n0, const float *const *f1, const int *n1, int32_t *const *out_1to0,
                                 int32_t *const *out_0to1, const int **overflow_dev, int mutual_only = 0);
 
+// ---- the correspondence list of the RANSAC feature-matching form (pcr_fgr.hip, next to the searches it shares with FGR): (i, nearest target row of i)
+// in source order, with mutual_filter only the cross-checked rows unless fewer than min_rows remain.  corres: ns x 2 int32 (device), *n_out on the host.
+size_t pcr_feature_corres_scratch_bytes(int64_t ns, int64_t nt);
+int pcr_feature_corres(pcr_context *ctx, const float *src_feat, int ns, const float *tgt_feat, int nt, int mutual_filter, int min_rows, int32_t *corres, int64_t *n_out);
+
 // ---- gicp (pcr_gicp.hip) --------------------------------------------------------------------------
 struct IcpOutputs { pcr_result res; };
 int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,

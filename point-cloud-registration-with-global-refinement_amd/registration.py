@@ -525,6 +525,126 @@ def registration_fgr_based_on_feature_matching(source: PointCloud, target: Point
     return _result(res, corr)
 
 
+class RANSACConvergenceCriteria:
+    def __init__(self, max_iteration: int = 100000, confidence: float = 0.999):
+        self.max_iteration = int(max_iteration)
+        self.confidence = float(confidence)
+
+
+class CorrespondenceChecker:
+    """Base of the RANSAC pruning checks; ``require_pointcloud_alignment_`` as in Open3D (False: checked on the sample before the fit)."""
+    require_pointcloud_alignment_ = True
+
+
+class CorrespondenceCheckerBasedOnEdgeLength(CorrespondenceChecker):
+    require_pointcloud_alignment_ = False
+
+    def __init__(self, similarity_threshold: float = 0.9):
+        self.similarity_threshold = float(similarity_threshold)
+
+
+class CorrespondenceCheckerBasedOnDistance(CorrespondenceChecker):
+    def __init__(self, distance_threshold: float):
+        self.distance_threshold = float(distance_threshold)
+
+
+class CorrespondenceCheckerBasedOnNormal(CorrespondenceChecker):
+    def __init__(self, normal_angle_threshold: float):
+        self.normal_angle_threshold = float(normal_angle_threshold)
+
+
+def _ransac_params(fn, max_correspondence_distance, estimation_method, ransac_n, checkers, criteria, seed) -> _lib.PcrRansacParams:
+    """Arguments of the two RANSAC entry points -> ``pcr_ransac_params``.  Several checkers of one kind act as their strictest member (a
+    hypothesis has to pass all of them); a negative threshold tells the library that the checker is absent."""
+    estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
+    if not isinstance(estimation, TransformationEstimationPointToPoint):
+        raise RuntimeError(f"{fn}: {type(estimation).__name__} is not implemented on the MI355X path")
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    if not 3 <= int(ransac_n) <= 8:
+        raise RuntimeError(f"{fn}: ransac_n must be in 3..8 (got {ransac_n})")
+    criteria = criteria or RANSACConvergenceCriteria()
+    if criteria.max_iteration < 0 or not 0.0 < criteria.confidence <= 1.0:
+        raise RuntimeError(f"{fn}: RANSACConvergenceCriteria needs max_iteration >= 0 and 0 < confidence <= 1")
+    edge, dist, ang = -1.0, -1.0, -1.0
+    for c in checkers or ():
+        if isinstance(c, CorrespondenceCheckerBasedOnEdgeLength):
+            thr = c.similarity_threshold
+            edge = max(edge, thr)
+        elif isinstance(c, CorrespondenceCheckerBasedOnDistance):
+            thr = c.distance_threshold
+            dist = thr if dist < 0 else min(dist, thr)
+        elif isinstance(c, CorrespondenceCheckerBasedOnNormal):
+            thr = c.normal_angle_threshold
+            ang = thr if ang < 0 else min(ang, thr)
+        else:
+            raise RuntimeError(f"{fn}: {type(c).__name__} is not implemented on the MI355X path")
+        if not thr >= 0:
+            raise RuntimeError(f"{fn}: negative threshold in {type(c).__name__}")
+    if seed is None:                       # Open3D draws from std::random_device; here a process-local counter
+        _fgr_seed_counter[0] = (_fgr_seed_counter[0] * 6364136223846793005 + 1442695040888963407) & (2 ** 64 - 1)
+        seed = _fgr_seed_counter[0]
+    return _lib.PcrRansacParams(int(ransac_n), int(estimation.with_scaling), int(criteria.max_iteration), float(criteria.confidence),
+                                int(seed) & (2 ** 64 - 1), edge, dist, ang)
+
+
+def _ransac_result(res: _lib.PcrResult, info: _lib.PcrRansacInfo, corr) -> RegistrationResult:
+    out = _result(res, corr)
+    out.iterations = int(info.iterations_run)
+    out.best_iteration = int(info.best_iteration)
+    out.n_valid = int(info.n_valid)
+    out.n_corres = int(info.n_corres)
+    return out
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, estimation_method=None, ransac_n=3,
+                                                checkers=[], criteria=None, seed=None):
+    """Open3D ``registration_ransac_based_on_correspondence`` (0.13 and later): ``corres`` is (C, 2) rows of (source index, target index);
+    fitness and RMSE of the result are taken over that list, ``correspondence_set`` holds its inlier rows.  The loop is the sequential one
+    of include/pcr_hip.h (deterministic for a ``seed``; ``seed=None`` draws from a process-local counter).  The result also carries
+    ``iterations`` (iterations run), ``best_iteration`` (-1: none), ``n_valid`` (hypotheses among those run that passed every checker) and
+    ``n_corres`` (rows of the list), the fields of ``pcr_ransac_info``."""
+    p = _ransac_params("registration_ransac_based_on_correspondence", max_correspondence_distance, estimation_method, ransac_n, checkers, criteria, seed)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    if isinstance(corres, torch.Tensor):
+        cd = corres.to(device="cuda", dtype=torch.int32).reshape(-1, 2).contiguous()
+    else:
+        cd = torch.from_numpy(np.ascontiguousarray(np.asarray(corres, dtype=np.int64).reshape(-1, 2).astype(np.int32))).cuda()
+    nc = int(cd.shape[0])
+    ns, nt = len(source), len(target)
+    if nc and (ns == 0 or nt == 0 or int(cd[:, 0].min()) < 0 or int(cd[:, 1].min()) < 0 or int(cd[:, 0].max()) >= ns or int(cd[:, 1].max()) >= nt):
+        raise RuntimeError("registration_ransac_based_on_correspondence: correspondence index out of range")
+    out = torch.empty((max(nc, 1), 2), dtype=torch.int32, device="cuda")
+    res, info = _lib.PcrResult(), _lib.PcrRansacInfo()
+    ctx.check(ctx.lib.pcr_registration_ransac_correspondence(
+        ctx.handle, _ptr(source.device_xyz()), _ptr(source.device_normals() if source.has_normals() else None), C.c_int64(ns),
+        _ptr(target.device_xyz()), _ptr(target.device_normals() if target.has_normals() else None), C.c_int64(nt), _ptr(cd), C.c_int64(nc),
+        C.c_double(max_correspondence_distance), C.byref(p), C.byref(res), _ptr(out), C.byref(info)), "registration_ransac_based_on_correspondence")
+    return _ransac_result(res, info, out)
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter, max_correspondence_distance,
+                                                  estimation_method=None, ransac_n=3, checkers=[], criteria=None, seed=None):
+    """Open3D ``registration_ransac_based_on_feature_matching`` (0.13 and later): every source point is paired with its nearest target point
+    in feature space (with ``mutual_filter`` only the pairs whose target point points back, unless fewer than ``ransac_n`` remain), then
+    ``registration_ransac_based_on_correspondence`` runs on that list (same extra result fields; ``n_corres`` is the length of the list built)."""
+    p = _ransac_params("registration_ransac_based_on_feature_matching", max_correspondence_distance, estimation_method, ransac_n, checkers, criteria, seed)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = len(source), len(target)
+    if source_feature.num() != ns or target_feature.num() != nt:
+        raise RuntimeError("registration_ransac_based_on_feature_matching: one feature row per point is required")
+    out = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+    res, info = _lib.PcrResult(), _lib.PcrRansacInfo()
+    ctx.check(ctx.lib.pcr_registration_ransac_feature_matching(
+        ctx.handle, _ptr(source.device_xyz()), _ptr(source.device_normals() if source.has_normals() else None), C.c_int64(ns),
+        _ptr(source_feature._dev), _ptr(target.device_xyz()), _ptr(target.device_normals() if target.has_normals() else None), C.c_int64(nt),
+        _ptr(target_feature._dev), C.c_int(int(bool(mutual_filter))), C.c_double(max_correspondence_distance), C.byref(p), C.byref(res), _ptr(out),
+        C.byref(info)), "registration_ransac_based_on_feature_matching")
+    return _ransac_result(res, info, out)
+
+
 # pose-graph slice of o3d.pipelines.registration (3_Global_Optimizations...py:292-358; host side, posegraph.py)
 from .posegraph import (GlobalOptimizationConvergenceCriteria, GlobalOptimizationLevenbergMarquardt,  # noqa: E402,F401
                         GlobalOptimizationOption, PoseGraph, PoseGraphEdge, PoseGraphNode, global_optimization)
