@@ -12,6 +12,7 @@
 // inputs already in registers came out with other fused pairs than the same function in k_icp_lin -- poses 1e-7 apart under L1, where the
 // kernel forms are promised to give the same bits).  Before the includes: the helpers inlined into these kernels follow the same rule.
 #pragma clang fp contract(on)
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <cstdio>
@@ -1003,6 +1004,36 @@ template <int TILE_PTS, bool GRID> __global__ void __launch_bounds__(FUSED_BS) F
 struct IcpArgsB { IcpArgs a[ICP_BYVAL]; };
 template <int TILE_PTS, bool GRID> __global__ void __launch_bounds__(FUSED_BS) FUSED_OCC k_icp_fused_b(IcpArgsB b) { d_icp_fused<TILE_PTS, GRID>(b.a[blockIdx.y]); }
 
+// ---- the environment switches of this file, read together at the first use of any of them, once per process
+struct IcpSwitches {
+    bool skip;          // PCR_ICP_SKIP=0: no certificates, every query searched at every launch
+    double gap_frac;    // PCR_ICP_GAP: the certificate margin g as a fraction of max_dist (before icp_base_gap's clamp)
+    int chunk;          // PCR_ICP_CHUNK: launches per chunk, 1..32
+    int chunk_adapt;    // PCR_ICP_CHUNK_ADAPT: 0 / 1 forces icp_next_chunk's short chunks off / on; -1 (unset): the loop's own choice
+    bool graph;         // PCR_ICP_GRAPH=0: chunks are launched kernel by kernel
+    bool fused;         // PCR_ICP_FUSED=0: k_icp_nn + k_icp_lin at every launch
+    bool grid;          // PCR_ICP_GRID=0: every correspondence search over the octree (the independent check of tests/test_gpu_gicp.py::test_switches_do_not_change_the_result)
+    bool byval;         // PCR_ICP_BYVAL=0: groups of up to ICP_BYVAL read their arguments through the device pointer too
+    bool tile_set;      // PCR_ICP_TILE or PCR_ICP_PPL is given: no pair of a group picks a tile of its own
+    int tile_fixed;     // PCR_ICP_TILE, or FUSED_BS x PCR_ICP_PPL, or 0
+};
+static const IcpSwitches &icp_switches() {
+    static const IcpSwitches sw = [] {
+        const auto num = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+        const auto on = [&](const char *name) { return num(name, 1) != 0; };
+        IcpSwitches s;
+        s.skip = on("PCR_ICP_SKIP"); s.graph = on("PCR_ICP_GRAPH"); s.fused = on("PCR_ICP_FUSED"); s.grid = on("PCR_ICP_GRID"); s.byval = on("PCR_ICP_BYVAL");
+        s.gap_frac = getenv("PCR_ICP_GAP") ? atof(getenv("PCR_ICP_GAP")) : 0.25;
+        const int chunk = num("PCR_ICP_CHUNK", 8);
+        s.chunk = chunk < 1 ? 1 : (chunk > 32 ? 32 : chunk);
+        s.chunk_adapt = num("PCR_ICP_CHUNK_ADAPT", -1);
+        s.tile_set = getenv("PCR_ICP_TILE") || getenv("PCR_ICP_PPL");
+        s.tile_fixed = getenv("PCR_ICP_TILE") ? num("PCR_ICP_TILE", 0) : FUSED_BS * num("PCR_ICP_PPL", 0);
+        return s;
+    }();
+    return sw;
+}
+
 // Source points per workgroup of the fused kernel (PCR_ICP_TILE = 128 ... 2048; PCR_ICP_PPL = 1 / 2 / 4 is the older spelling of
 // 512 / 1024 / 2048).  The workgroup's 64 octets serve its pending queries 64 at a time, so a 512-point tile whose certificates do not
 // hold walks the tree up to 8 times in a row -- but that is NOT what the launch waits for: one pair alone, 25 iterations per scale,
@@ -1010,8 +1041,7 @@ template <int TILE_PTS, bool GRID> __global__ void __launch_bounds__(FUSED_BS) F
 // flight: 333 / 304 / 258 pairs/s for 1024 / 512 / 256.  One pair: 256 from 40k points (below: 512, the tile of k_icp_iter, so that
 // PCR_ICP_FUSED=0 stays the same arithmetic on NCLT-size clouds); groups: 1024.
 static int fused_tile_points(const pcr_context *ctx, int cap, int G) {
-    static const int fixed = getenv("PCR_ICP_TILE") ? atoi(getenv("PCR_ICP_TILE")) : (getenv("PCR_ICP_PPL") ? FUSED_BS * atoi(getenv("PCR_ICP_PPL")) : 0);
-    int t = fixed;
+    int t = icp_switches().tile_fixed;
     if (t <= 0) {
         // group_forms: a unit of a lockstep-group plan, whatever its size.  One pair: 256 from 40k points (the slowest workgroup's search sets the
         // launch), 1024 from 400k (round 5, config 5's 0.5-1.6M-point scales: the launch is several rounds of workgroups and fewer, fatter ones win:
@@ -1027,8 +1057,7 @@ static int fused_tile_points(const pcr_context *ctx, int cap, int G) {
 // round of a few workgroups and halving their work shortens it (script-2 stage on the shipped scans, groups of 8 x 4: 1590-1780 -> 1900-2020 pairs/s) --
 // else the kernel's 1024 (50k points: 1892 against 1841 with 512; 100k: 1197 against 1164; 200k: 698 against 672).  By the PAIR alone.
 static int icp_group_tile(int cap, int kernel_tile) {
-    static const bool fixed = getenv("PCR_ICP_TILE") || getenv("PCR_ICP_PPL");
-    if (fixed || kernel_tile != 1024) return 0;
+    if (icp_switches().tile_set || kernel_tile != 1024) return 0;
     return cap < 40000 ? 512 : 0;
 }
 #define PCR_FUSED_LAUNCH_(ctx, KERNEL, GRID, tile, grid, arg)                                                          \
@@ -1043,8 +1072,6 @@ static int icp_group_tile(int cap, int kernel_tile) {
 #define PCR_FUSED_LAUNCH(ctx, KERNEL, use_grid, tile, grid, arg)                                                       \
     do { if (use_grid) PCR_FUSED_LAUNCH_(ctx, KERNEL, true, tile, grid, arg); else PCR_FUSED_LAUNCH_(ctx, KERNEL, false, tile, grid, arg); } while (0)
 
-// PCR_ICP_GRID=0: every correspondence search over the octree (the independent check of tests/test_gpu_gicp.py::test_switches_do_not_change_the_result)
-static bool icp_use_grid() { static const bool on = !(getenv("PCR_ICP_GRID") && atoi(getenv("PCR_ICP_GRID")) == 0); return on; }
 // The search cap of the certificate mode is r + g.  With the cell hash the cap costs nothing up to what the level's cells cover (edge >= 2.04 cap,
 // pcr_grid_level_for), and the room of a certificate is bounded by it: a query with fewer than K + 1 target points inside the cap -- every
 // unmatched one: 45 % of the finest scale -- carries D = cap, i.e. g of room, and with g = 2.5 cm it was searched again every few launches.
@@ -1098,7 +1125,7 @@ static void state_to_result(const IcpState &s, pcr_result *out) {
 // ~10 us gap on the one stream there is, and short chunks have more of them than they save in 4.4-us launches.  So: on for groups, off
 // for the one-pair loop (PCR_ICP_CHUNK_ADAPT = 0 / 1 forces either).
 static int icp_next_chunk(const IcpState &s, double rel_fit, double rel_rmse, int chunk, bool group) {
-    static const int forced = getenv("PCR_ICP_CHUNK_ADAPT") ? atoi(getenv("PCR_ICP_CHUNK_ADAPT")) : -1;
+    const int forced = icp_switches().chunk_adapt;
     const bool adaptive = forced < 0 ? group : forced != 0;
     if (!adaptive || s.launches < 2 || !(rel_rmse > 0.0)) return chunk;
     const double quantum = s.ns > 0 ? 1.0 / (double)s.ns : 0.0;           // the fitness moves in steps of one correspondence
@@ -1106,6 +1133,171 @@ static int icp_next_chunk(const IcpState &s, double rel_fit, double rel_rmse, in
     if (s.dfit <= 2.5 * fit_tol && s.drmse <= 30.0 * rel_rmse) return chunk < 2 ? chunk : 2;
     if (s.dfit <= 8.5 * fit_tol && s.drmse <= 300.0 * rel_rmse) return chunk < 4 ? chunk : 4;
     return chunk;
+}
+
+// ---- what the three host loops below (icp_loop, pcr_dev_gicp_group, pcr_dev_gicp_group_scales) and the one-shot entry points share
+
+// Workgroup counts of the iteration kernels for a cloud of `cap` source points
+struct IcpGrids {
+    int nblin;      // k_icp_lin: one LIN_BS-point tile per workgroup
+    int nbmax;      // k_icp_iter: the same tiles over at most LIN_MAX_BLOCKS workgroups
+    int nbnn;       // k_icp_nn: one query per octet
+    int nbf;        // the fused kernel: one workgroup per `tile` source points, a multiple of 8 (XCD order); tile == 0: not asked for
+};
+static IcpGrids icp_grids(int cap, int tile) {
+    IcpGrids n;
+    n.nblin = (cap + LIN_BS - 1) / LIN_BS;
+    n.nbmax = n.nblin < LIN_MAX_BLOCKS ? n.nblin : LIN_MAX_BLOCKS;
+    n.nbnn = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT);
+    n.nbf = tile > 0 ? ((cap + tile - 1) / tile + 7) & ~7 : 0;
+    return n;
+}
+
+// certificate mode searches a slightly larger ball (r + g): a query with nothing inside it stays unmatched, without
+// a search, until it has moved by g; candidates between r and r + g are rejected by k_icp_iter's float64 radius test
+static double icp_base_gap(double max_dist) {
+    const double g = icp_switches().gap_frac * max_dist;
+    return g < 0.01 ? 0.01 : (g > 0.05 ? 0.05 : g);
+}
+static void icp_set_search_cap(IcpArgs &a, double max_dist, double g) {
+    const double rs = max_dist + g;
+    a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)(rs - max_dist);
+}
+
+// Arguments and start poses of a lockstep group: a per-context buffer whose device address is FIXED for the life of the context (the captured
+// graphs read them there), and its pinned host image
+#define ICP_GROUP_MAX 32
+struct IcpGroupBuf { IcpArgs *args, *dargs; IcpInit *inits, *dinits; size_t bytes; };     // host / device: ICP_GROUP_MAX argument structs, then as many poses
+static int icp_group_buf(pcr_context *ctx, IcpGroupBuf *b) {
+    const size_t inits_at = sizeof(IcpArgs) * ICP_GROUP_MAX;
+    b->bytes = inits_at + sizeof(IcpInit) * ICP_GROUP_MAX;
+    if ((!ctx->icp_group_dev && hipMalloc((void **)&ctx->icp_group_dev, b->bytes) != hipSuccess) ||
+        (!ctx->icp_group_host && hipHostMalloc((void **)&ctx->icp_group_host, b->bytes, hipHostMallocDefault) != hipSuccess)) {
+        ctx->err = "GICP group: argument buffers"; return PCR_ENOMEM;
+    }
+    b->args = (IcpArgs *)ctx->icp_group_host; b->inits = (IcpInit *)(ctx->icp_group_host + inits_at);
+    b->dargs = (IcpArgs *)ctx->icp_group_dev; b->dinits = (IcpInit *)(ctx->icp_group_dev + inits_at);
+    return PCR_OK;
+}
+
+// ---- the graph cache.  One chunk of launches is replayed as ONE hipGraph launch: the loops are launch-bound (a 3000-point pair still takes
+// 5 ms), and a graph costs one runtime call instead of 16.  The instantiated graphs are kept in the context under a key made by the loop.
+static IcpGraph *icp_graph_find(pcr_context *ctx, const std::string &key) {
+    for (auto &g : ctx->icp_graphs) if (g.key == key) return &g;
+    return nullptr;
+}
+// the kernel nodes of a captured chunk in launch order (for hipGraphExecKernelNodeSetParams): the chunk is a chain, walked from its root
+static int icp_graph_collect_nodes(pcr_context *ctx, IcpGraph &e, size_t expect) {
+    size_t nr = 1; hipGraphNode_t node = nullptr;
+    PCR_HIP_CHECK(ctx, hipGraphGetRootNodes(e.graph, &node, &nr));
+    if (nr != 1) { ctx->err = "GICP group: captured chunk has more than one root"; return PCR_EHIP; }
+    while (node) {
+        hipGraphNodeType nt;
+        PCR_HIP_CHECK(ctx, hipGraphNodeGetType(node, &nt));
+        if (nt != hipGraphNodeTypeKernel) { ctx->err = "GICP group: captured chunk holds a node that is not a kernel"; return PCR_EHIP; }
+        e.nodes.push_back(node);
+        size_t nd = 0;
+        PCR_HIP_CHECK(ctx, hipGraphNodeGetDependentNodes(node, nullptr, &nd));
+        if (nd == 0) break;
+        if (nd != 1) { ctx->err = "GICP group: captured chunk is not a chain"; return PCR_EHIP; }
+        hipGraphNode_t next = nullptr;
+        PCR_HIP_CHECK(ctx, hipGraphNodeGetDependentNodes(node, &next, &nd));
+        node = next;
+    }
+    if (e.nodes.size() != expect) { ctx->err = "GICP group: captured chunk does not match its launch list"; return PCR_EHIP; }
+    return PCR_OK;
+}
+// Captures enqueue(0) ... enqueue(len - 1) on the context's stream, instantiates the graph and stores it under `key`; expect_nodes > 0: its node
+// list is collected too and must have that many kernels.  *out is valid until the cache is next changed.
+template <class Enqueue>
+static int icp_graph_capture(pcr_context *ctx, const std::string &key, int len, size_t expect_nodes, Enqueue &&enqueue, IcpGraph **out) {
+    IcpGraph e; e.key = key;
+    // (the graph objects belong to `e` until it is stored: an early error return below must not leak them)
+    struct Owner { IcpGraph *g; ~Owner() { if (g) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); } } } owner{&e};
+    PCR_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    for (int k = 0; k < len; k++) enqueue(k);
+    PCR_HIP_CHECK(ctx, hipStreamEndCapture(ctx->stream, &e.graph));
+    PCR_HIP_CHECK(ctx, hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
+    if (expect_nodes) PCR_TRY(icp_graph_collect_nodes(ctx, e, expect_nodes));
+    if (ctx->icp_graphs.size() >= 48) {           // evict the oldest entry (the stream is drained first: a replay of it may still be queued)
+        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipGraphExecDestroy(ctx->icp_graphs[0].exec);
+        if (ctx->icp_graphs[0].graph) (void)hipGraphDestroy(ctx->icp_graphs[0].graph);
+        ctx->icp_graphs.erase(ctx->icp_graphs.begin());
+    }
+    owner.g = nullptr;                            // stored: the context owns the graph from here on
+    ctx->icp_graphs.push_back(std::move(e));
+    *out = &ctx->icp_graphs.back();
+    return PCR_OK;
+}
+
+// ---- the chunk pump.  Launches are queued in chunks; the states after chunk c are copied back while chunk c + 1 is already queued, so the GPU
+// never idles on the host.  Launches after 'done' return at their first instruction.
+struct IcpPump {
+    pcr_context *ctx = nullptr;
+    const IcpState *st_dev = nullptr; size_t slot_bytes = 0;
+    IcpState *slots[2] = {nullptr, nullptr};          // two read-back slots of G states each in the pinned window
+    int cur = 0, prev = -1;
+    int launched = 0;                                 // launches queued so far
+    bool done = false;                                // the judge ended the loop (else: `total` launches were queued and read back)
+    std::vector<int> chunk_first, chunk_last;         // launches [first, last) of every chunk; chunk c lies between prof_events 2c and 2c + 1
+
+    int init(pcr_context *c, const IcpState *states_dev, int G) {
+        ctx = c; st_dev = states_dev; slot_bytes = sizeof(IcpState) * (size_t)G;
+        if (2 * slot_bytes > ctx->pinned_cap) { ctx->err = "ICP loop: pinned window too small"; return PCR_ENOMEM; }
+        slots[0] = (IcpState *)ctx->pinned; slots[1] = (IcpState *)(ctx->pinned + slot_bytes);
+        return PCR_OK;
+    }
+    // issue(k, c, ragged) queues launches k ... k + c - 1; ragged: `total` cut the chunk short of the length asked for.
+    // judge(states, upto, &next) sees the states after launch upto - 1, the end of the chunk before the one just queued, and sets the length
+    // of the next chunk: 0 ends the loop.  The first two chunks have first_len launches.  No more than `total` launches are queued in all.
+    template <class Issue, class Judge>
+    int run(int first_len, int total, Issue &&issue, Judge &&judge) {
+        int want = first_len;
+        for (;;) {
+            const int room = total - launched, c = room < want ? (room > 0 ? room : 0) : want;
+            if (c > 0) {
+                const size_t n = chunk_first.size();
+                if (ctx->profiling) {
+                    while (ctx->prof_events.size() < 2 * (n + 1)) { hipEvent_t e; PCR_HIP_CHECK(ctx, hipEventCreate(&e)); ctx->prof_events.push_back(e); }
+                    PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n], ctx->stream));
+                }
+                PCR_TRY(issue(launched, c, c != want));
+                if (ctx->profiling) PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n + 1], ctx->stream));
+                chunk_first.push_back(launched); chunk_last.push_back(launched + c);
+                launched += c;
+                PCR_HIP_CHECK(ctx, hipMemcpyAsync(slots[cur], st_dev, slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
+                PCR_HIP_CHECK(ctx, hipEventRecord(ctx->ev[cur], ctx->stream));
+            }
+            if (prev >= 0) {
+                PCR_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev[prev]));
+                PCR_TRY(judge((const IcpState *)slots[prev], launched - c, &want));
+                if (want == 0) { done = true; return PCR_OK; }
+            }
+            if (c == 0) return PCR_OK;
+            prev = cur; cur ^= 1;
+        }
+    }
+    // bench instrumentation: chunks whose launches were all live (before 'done'): HIP-event time / launches = launch-to-launch period;
+    // issued / live launches of the loop: the rest returned at once
+    int add_profile(int live) {
+        for (size_t c = 0; c < chunk_first.size(); c++) {
+            if (chunk_last[c] > live) continue;
+            float ms = 0;
+            PCR_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->prof_events[2 * c], ctx->prof_events[2 * c + 1]));
+            ctx->prof[0] += ms; ctx->prof[1] += chunk_last[c] - chunk_first[c];
+        }
+        ctx->prof[5] += launched; ctx->prof[13] += live;
+        return PCR_OK;
+    }
+};
+// bench instrumentation: what a finished problem (one scale of one pair) adds to the profile
+static void icp_prof_add_state(pcr_context *ctx, const IcpState &s) {
+    ctx->prof[2] += (double)s.t_live * 0.01;            // 100 MHz ticks -> microseconds
+    ctx->prof[3] += s.launches;
+    ctx->prof[4] += 48.0 * (double)s.ns * (double)s.launches;   // 48 B per source point per launch
+    ctx->prof[6] += (double)s.t_dbg[0] * 0.01; ctx->prof[7] += (double)s.t_dbg[3] * 0.01; ctx->prof[14] += (double)s.t_dbg[1] * 0.01;
+    ctx->prof[11] += (double)s.searched;
 }
 
 // The one-pair loop of every estimator: mode = ICP_MODE_GICP (GICP_COV when both clouds carry covariances), or P2PL / P2P / P2P_SCALED
@@ -1118,147 +1310,90 @@ static int icp_loop(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, 
     if (gicp && !use_cov && (!src->nrm || !tgt->nrm)) { ctx->err = "GICP needs normals (or covariances) on both clouds"; return PCR_EINVAL; }
     if (mode == ICP_MODE_P2PL && !tgt->nrm) { ctx->err = "point-to-plane ICP needs normals on the target"; return PCR_EINVAL; }
     ArenaMark mark(ctx);
+    const IcpSwitches &sw = icp_switches();
     const int cap = src->cap > 0 ? src->cap : 1;
-    static const bool use_skip = !(getenv("PCR_ICP_SKIP") && atoi(getenv("PCR_ICP_SKIP")) == 0);
-    const int nblin = (cap + LIN_BS - 1) / LIN_BS;                  // k_icp_lin: one tile per workgroup
-    const int nbmax = nblin < LIN_MAX_BLOCKS ? nblin : LIN_MAX_BLOCKS;
-    const int nbnn = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT);
     const int tile_pts = fused_tile_points(ctx, cap, 1);
     const int tile_eff = (ctx->group_forms && icp_group_tile(cap, tile_pts)) ? icp_group_tile(cap, tile_pts) : tile_pts;
-    const int nbf = ((cap + tile_eff - 1) / tile_eff + 7) & ~7;      // workgroups of the fused kernel: one per tile of source points, a multiple of 8 (XCD order)
+    const IcpGrids n = icp_grids(cap, tile_eff);
     IcpState *st = arena<IcpState>(ctx, 1);
-    const int rows = nblin > nbf ? nblin : nbf;
+    const int rows = n.nblin > n.nbf ? n.nblin : n.nbf;
     double *partials = arena<double>(ctx, (size_t)rows * NVP);
     int32_t *match = match_dev ? match_dev : arena<int32_t>(ctx, cap);
     if (!st || !partials || !match) return PCR_ENOMEM;
     IcpArgs a; memset(&a, 0, sizeof a); fill_args(a, src, tgt, max_dist, p, match, st, partials, 0);
     a.tile_rt = ctx->group_forms ? icp_group_tile(cap, tile_pts) : 0;
-    if (use_skip && max_dist < 1e15) {
+    if (sw.skip && max_dist < 1e15) {
         a.ref = arena<float4>(ctx, cap); a.rbest = arena<int32_t>(ctx, cap); a.clist = arena<int4>(ctx, cap);
         if (!a.ref || !a.rbest || !a.clist) return PCR_ENOMEM;
-        // certificate mode searches a slightly larger ball (r + g): a query with nothing inside it stays unmatched, without
-        // a search, until it has moved by g; candidates between r and r + g are rejected by k_icp_iter's float64 radius test
-        static const double gfrac = getenv("PCR_ICP_GAP") ? atof(getenv("PCR_ICP_GAP")) : 0.25;
-        double g = gfrac * max_dist; g = g < 0.01 ? 0.01 : (g > 0.05 ? 0.05 : g);
-        const double rs = max_dist + g;
-        a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)g;
+        const double g = icp_base_gap(max_dist);
+        icp_set_search_cap(a, max_dist, g);
+        a.rs_minus_r = (float)g;            // (the unwidened margin is g itself: (max_dist + g) - max_dist is another float for radii of kilometres)
         a.verify = pcr_options().icp_verify.load(std::memory_order_relaxed) ? 1 : 0;
     }
-    if (icp_use_grid() && !use_cov) {       // cell hash of the target for radii of a few voxels (pcr_octree.h GridView); the octree serves the others
+    if (sw.grid && !use_cov) {       // cell hash of the target for radii of a few voxels (pcr_octree.h GridView); the octree serves the others
         const int L = pcr_grid_level_for(tgt, std::sqrt((double)(a.ref ? a.r2s : a.r2f)));
         PCR_TRY(pcr_dev_build_grid_batch(ctx, &tgt, &L, 1, &a.grid));
-        if (a.ref && a.grid.tab) {
-            const double rs = max_dist + icp_gap_for_level(tgt, L, max_dist, (double)a.rs_minus_r);
-            a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)(rs - max_dist);
-        }
+        if (a.ref && a.grid.tab) icp_set_search_cap(a, max_dist, icp_gap_for_level(tgt, L, max_dist, (double)a.rs_minus_r));
     }
     const bool grid = a.grid.tab != nullptr;
     IcpInit in; memcpy(in.T, T0, sizeof in.T);
     PCR_LAUNCH(ctx, k_icp_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
 
-    // Launch in chunks; the state of chunk c is copied back while chunk c+1 is already queued, so the GPU never
-    // idles on the host.  Launches after 'done' return at their first instruction.
-    static const int chunk_env = getenv("PCR_ICP_CHUNK") ? atoi(getenv("PCR_ICP_CHUNK")) : 8;
-    const int total = a.max_it + 1, CHUNK = chunk_env < 1 ? 1 : (chunk_env > 32 ? 32 : chunk_env);
-    // One chunk = CHUNK x (k_icp_nn, k_icp_iter) replayed as ONE hipGraph launch: the loop is launch-bound (a 3000-point
-    // pair still takes 5 ms), and a graph costs one runtime call instead of 16.  The arena hands out the same addresses
-    // for the same problem sizes, so the instantiated graph is cached in the context under its argument bytes.
-    static const bool use_graph = !(getenv("PCR_ICP_GRAPH") && atoi(getenv("PCR_ICP_GRAPH")) == 0);
-    static const bool use_fused = !(getenv("PCR_ICP_FUSED") && atoi(getenv("PCR_ICP_FUSED")) == 0);
     // launch 0 of a scale searches every query (cold): two kernels at full occupancy; later launches: the fused kernel
     // (round 5: also for the 0.5-1.6M-point scales of config 5, which ran three streaming kernels per iteration -- certificates, one pending
     // list for the cloud, tile linearisation -- while 17 % of their queries were searched again per launch; with list certificates it is 3 %
     // and the one kernel is the faster form there too: 167 against 184 us per launch, 26.7 against 26.4 pairs/s.  The streaming kernels are gone.)
-    const bool fused = use_fused && gicp && a.ref && !use_cov && nbf <= 4096;      // (the fused kernel is the GICP linearisation only)
+    const bool fused = sw.fused && gicp && a.ref && !use_cov && n.nbf <= 4096;      // (the fused kernel is the GICP linearisation only)
     auto enqueue = [&](int launch_index) {
         if (fused && launch_index > 0) {
-            PCR_FUSED_LAUNCH(ctx, k_icp_fused, grid, tile_pts, dim3(nbf), a);
+            PCR_FUSED_LAUNCH(ctx, k_icp_fused, grid, tile_pts, dim3(n.nbf), a);
             return;
         }
-        if (grid) PCR_LAUNCH(ctx, k_icp_nn<true>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
-        else PCR_LAUNCH(ctx, k_icp_nn<false>, dim3(nbnn), dim3(ICP_BS), 0, ctx->stream, a);
-        if (use_cov) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP_COV>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
-        else if (gicp) PCR_LAUNCH(ctx, k_icp_lin, dim3(nblin), dim3(LIN_BS), 0, ctx->stream, a);
-        else if (mode == ICP_MODE_P2PL) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2PL>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
-        else if (mode == ICP_MODE_P2P) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
-        else PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P_SCALED>, dim3(nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        if (grid) PCR_LAUNCH(ctx, k_icp_nn<true>, dim3(n.nbnn), dim3(ICP_BS), 0, ctx->stream, a);
+        else PCR_LAUNCH(ctx, k_icp_nn<false>, dim3(n.nbnn), dim3(ICP_BS), 0, ctx->stream, a);
+        if (use_cov) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP_COV>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (gicp) PCR_LAUNCH(ctx, k_icp_lin, dim3(n.nblin), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (mode == ICP_MODE_P2PL) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2PL>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (mode == ICP_MODE_P2P) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P_SCALED>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
     };
-    // graph of a chunk of `len` launches: which = 0 starts with launch 0 (cold search + linearisation), which = 1 holds later launches only
-    auto graph_for = [&](int which, int len, hipGraphExec_t *out) -> int {
-        *out = nullptr;
-        if (!use_graph) return PCR_OK;
+    // One chunk = CHUNK x (k_icp_nn, k_icp_iter) as one graph.  The arena hands out the same addresses for the same problem sizes, so the
+    // graph is cached under its argument bytes.  which = 0 starts with launch 0 (cold search + linearisation), which = 1 holds later launches only.
+    auto graph_for = [&](int which, int len, hipGraphExec_t *exec) -> int {
         std::string key((const char *)&a, sizeof a);
         // (the estimator is part of the key: point-to-point and point-to-plane problems have byte-identical arguments)
-        const int extra[8] = {nbnn, nbmax, use_cov ? 1 : 0, len, fused ? nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0, mode};
+        const int extra[8] = {n.nbnn, n.nbmax, use_cov ? 1 : 0, len, fused ? n.nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0, mode};
         key.append((const char *)extra, sizeof extra);
-        for (auto &g : ctx->icp_graphs) if (g.key == key) { *out = g.exec; return PCR_OK; }
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        PCR_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-        for (int k = 0; k < len; k++) enqueue(which == 0 ? k : len + k);
-        PCR_HIP_CHECK(ctx, hipStreamEndCapture(ctx->stream, &graph));
-        PCR_HIP_CHECK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        if (ctx->icp_graphs.size() >= 48) {           // evict the oldest entry (the stream is drained first: a replay of it may still be queued)
-            PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipGraphExecDestroy(ctx->icp_graphs[0].exec);
-            if (ctx->icp_graphs[0].graph) (void)hipGraphDestroy(ctx->icp_graphs[0].graph);
-            ctx->icp_graphs.erase(ctx->icp_graphs.begin());
+        IcpGraph *hit = icp_graph_find(ctx, key);
+        if (!hit) {
+            PCR_TRY(icp_graph_capture(ctx, key, len, 0, [&](int k) { enqueue(which == 0 ? k : len + k); }, &hit));
+            (void)hipGraphDestroy(hit->graph); hit->graph = nullptr;      // no node of it is patched later: the instantiated graph is all that is kept
         }
-        { IcpGraph e; e.key = std::move(key); e.exec = exec; ctx->icp_graphs.push_back(std::move(e)); }
-        *out = exec;
+        *exec = hit->exec;
         return PCR_OK;
     };
-    IcpState *slots = (IcpState *)ctx->pinned;      // two read-back slots
-    int launched = 0, cur = 0, prev = -1, n_chunks = 0, next_len = CHUNK;
-    std::vector<int> chunk_first, chunk_last;
-    IcpState fin; bool have = false;
-    for (;;) {
-        const bool enq = launched < total;
-        if (enq) {
-            const int want = launched == 0 ? CHUNK : next_len;
-            const int c = total - launched < want ? total - launched : want;
-            if (ctx->profiling) {
-                while ((int)ctx->prof_events.size() < 2 * (n_chunks + 1)) { hipEvent_t e; PCR_HIP_CHECK(ctx, hipEventCreate(&e)); ctx->prof_events.push_back(e); }
-                PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks], ctx->stream));
-            }
-            hipGraphExec_t ge = nullptr;
-            if (c == want) PCR_TRY(graph_for(launched == 0 ? 0 : 1, c, &ge));      // (a ragged last chunk before max_iteration is launched directly)
-            if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-            else for (int k = 0; k < c; k++) enqueue(launched + k);
-            if (ctx->profiling) PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks + 1], ctx->stream));
-            chunk_first.push_back(launched); chunk_last.push_back(launched + c);
-            n_chunks++;
-            launched += c;
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(&slots[cur], st, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
-            PCR_HIP_CHECK(ctx, hipEventRecord(ctx->ev[cur], ctx->stream));
-        }
-        if (prev >= 0) {
-            PCR_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev[prev]));
-            if (slots[prev].done) { fin = slots[prev]; have = true; break; }
-            next_len = icp_next_chunk(slots[prev], a.rel_fit, a.rel_rmse, CHUNK, false);
-        }
-        if (!enq) break;
-        prev = cur; cur ^= 1;
-    }
-    if (!have) { ctx->err = "ICP loop ended without a final state"; return PCR_EHIP; }
+    auto issue = [&](int k, int c, bool ragged) -> int {
+        hipGraphExec_t ge = nullptr;
+        if (sw.graph && !ragged) PCR_TRY(graph_for(k == 0 ? 0 : 1, c, &ge));      // (a ragged last chunk before max_iteration is launched directly)
+        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
+        else for (int i = 0; i < c; i++) enqueue(k + i);
+        return PCR_OK;
+    };
+    IcpState fin;
+    auto judge = [&](const IcpState *s, int, int *next) -> int {
+        if (s->done) { fin = *s; *next = 0; }
+        else *next = icp_next_chunk(*s, a.rel_fit, a.rel_rmse, sw.chunk, false);
+        return PCR_OK;
+    };
+    IcpPump pump;
+    PCR_TRY(pump.init(ctx, st, 1));
+    PCR_TRY(pump.run(sw.chunk, a.max_it + 1, issue, judge));
+    if (!pump.done) { ctx->err = "ICP loop ended without a final state"; return PCR_EHIP; }
     // drain the (no-op) tail so the pinned slots and the arena can be reused safely
     PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->profiling) {
-        // chunks whose launches were all live (before 'done'): HIP-event time / launches = launch-to-launch period
-        for (int c = 0; c < n_chunks; c++) {
-            const int first = chunk_first[c], last = chunk_last[c];
-            if (last <= fin.launches) {
-                float ms = 0;
-                PCR_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->prof_events[2 * c], ctx->prof_events[2 * c + 1]));
-                ctx->prof[0] += ms; ctx->prof[1] += last - first;
-            }
-        }
-        ctx->prof[2] += (double)fin.t_live * 0.01;            // 100 MHz ticks -> microseconds
-        ctx->prof[3] += fin.launches;
-        ctx->prof[4] += 48.0 * (double)fin.ns * (double)fin.launches;   // 48 B per source point per launch
-        ctx->prof[5] += launched; ctx->prof[13] += fin.launches;          // issued / live launches of the loop: the rest returned at once
-        ctx->prof[6] += (double)fin.t_dbg[0] * 0.01; ctx->prof[7] += (double)fin.t_dbg[3] * 0.01; ctx->prof[14] += (double)fin.t_dbg[1] * 0.01;
-        ctx->prof[11] += (double)fin.searched;
+        icp_prof_add_state(ctx, fin);
+        PCR_TRY(pump.add_profile(fin.launches));
     }
     state_to_result(fin, out);
     for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = "non-finite pose"; return PCR_ENUMERIC; }
@@ -1295,26 +1430,27 @@ int pcr_dev_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, doub
 int pcr_dev_gicp_group(pcr_context *ctx, int G, const DevCloud *const *src, const DevCloud *const *tgt, const double *max_dists, const double *T0,
                        const pcr_gicp_params *p, pcr_result *out, int32_t *const *match_dev) {
     for (int g = 0; g < G; g++) if (!(max_dists[g] > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
-    if (G < 1 || G > 32) { ctx->err = "GICP group size must be in 1..32"; return PCR_EINVAL; }
+    if (G < 1 || G > ICP_GROUP_MAX) { ctx->err = "GICP group size must be in 1..32"; return PCR_EINVAL; }
     for (int g = 0; g < G; g++) if (!src[g]->nrm || !tgt[g]->nrm) { ctx->err = "GICP needs normals on both clouds"; return PCR_EINVAL; }
     ArenaMark mark(ctx);
+    const IcpSwitches &sw = icp_switches();
     // two source points per lane in lockstep groups (G x the workgroups per launch: half of them leave more of the chip to the other
     // groups in flight: 200k points, groups of 2, 4 groups in flight 367 -> 408 pairs/s); PCR_ICP_PPL overrides
     int max_cap = 1;
     for (int g = 0; g < G; g++) max_cap = src[g]->cap > max_cap ? src[g]->cap : max_cap;
     const int tile_pts = fused_tile_points(ctx, max_cap, G);
-    int nbmax = 1, nbnn = 1, nbf = 1;
-    std::vector<IcpArgs> args((size_t)G); std::vector<IcpInit> inits((size_t)G);
+    IcpGroupBuf buf;
+    PCR_TRY(icp_group_buf(ctx, &buf));
+    IcpArgs *args = buf.args;
+    int nblin = 1, nbnn = 1, nbf = 1;       // of the group's launches: the largest of its pairs
     IcpState *st = arena<IcpState>(ctx, G);
     if (!st) return PCR_ENOMEM;
-    static const double gfrac = getenv("PCR_ICP_GAP") ? atof(getenv("PCR_ICP_GAP")) : 0.25;
     for (int g = 0; g < G; g++) {
         const int cap = src[g]->cap > 0 ? src[g]->cap : 1;
-        const int m_ = (cap + LIN_BS - 1) / LIN_BS;                      // k_icp_lin_g: one 512-point tile per workgroup
         const int tile_g = icp_group_tile(cap, tile_pts) ? icp_group_tile(cap, tile_pts) : tile_pts;
-        const int n_ = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT), f_ = ((cap + tile_g - 1) / tile_g + 7) & ~7;
-        nbmax = m_ > nbmax ? m_ : nbmax; nbnn = n_ > nbnn ? n_ : nbnn; nbf = f_ > nbf ? f_ : nbf;
-        double *partials = arena<double>(ctx, (size_t)(m_ > f_ ? m_ : f_) * NVP);
+        const IcpGrids n = icp_grids(cap, tile_g);
+        nblin = n.nblin > nblin ? n.nblin : nblin; nbnn = n.nbnn > nbnn ? n.nbnn : nbnn; nbf = n.nbf > nbf ? n.nbf : nbf;
+        double *partials = arena<double>(ctx, (size_t)(n.nblin > n.nbf ? n.nblin : n.nbf) * NVP);
         int32_t *match = (match_dev && match_dev[g]) ? match_dev[g] : arena<int32_t>(ctx, cap);
         if (!partials || !match) return PCR_ENOMEM;
         IcpArgs &a = args[g]; memset(&a, 0, sizeof a);
@@ -1323,197 +1459,109 @@ int pcr_dev_gicp_group(pcr_context *ctx, int G, const DevCloud *const *src, cons
         a.tile_rt = icp_group_tile(cap, tile_pts);
         a.ref = arena<float4>(ctx, cap); a.rbest = arena<int32_t>(ctx, cap); a.clist = arena<int4>(ctx, cap);
         if (!a.ref || !a.rbest || !a.clist) return PCR_ENOMEM;
-        double gg = gfrac * max_dist; gg = gg < 0.01 ? 0.01 : (gg > 0.05 ? 0.05 : gg);
-        const double rs = max_dist + gg;
-        a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)gg;
-        memcpy(inits[g].T, T0 + 16 * g, sizeof inits[g].T);
+        const double gg = icp_base_gap(max_dist);
+        icp_set_search_cap(a, max_dist, gg);
+        a.rs_minus_r = (float)gg;           // (as in icp_loop)
+        memcpy(buf.inits[g].T, T0 + 16 * g, sizeof buf.inits[g].T);
     }
-    bool grid = false, grid_ok = false; (void)grid_ok;
-    if (icp_use_grid()) {
+    bool grid = false;
+    if (sw.grid) {
         std::vector<int> levels((size_t)G); std::vector<GridView> views((size_t)G);
         for (int g = 0; g < G; g++) levels[g] = pcr_grid_level_for(tgt[g], std::sqrt((double)args[g].r2s));
         bool all = true;
         for (int g = 0; g < G; g++) all = all && levels[g] >= 0 && tgt[g]->cap > 0;
         if (all) {                          // one kernel form per launch: the grid form only when every target of the group has a cell hash
             PCR_TRY(pcr_dev_build_grid_batch(ctx, tgt, levels.data(), G, views.data()));
-            for (int g = 0; g < G; g++) { args[g].grid = views[g]; grid = grid_ok = true; }
-            for (int g = 0; g < G; g++) grid = grid && views[g].tab != nullptr;
+            grid = true;
+            for (int g = 0; g < G; g++) { args[g].grid = views[g]; grid = grid && views[g].tab != nullptr; }
             if (grid)
-                for (int g = 0; g < G; g++) {
-                    const double rs = max_dists[g] + icp_gap_for_level(tgt[g], levels[g], max_dists[g], (double)args[g].rs_minus_r);
-                    args[g].r2s = (float)(rs * rs * (1.0 + 1e-6)); args[g].rs_minus_r = (float)(rs - max_dists[g]);
-                }
+                for (int g = 0; g < G; g++)
+                    icp_set_search_cap(args[g], max_dists[g], icp_gap_for_level(tgt[g], levels[g], max_dists[g], (double)args[g].rs_minus_r));
         }
     }
     if (nbf > 4096) { ctx->err = "GICP group: cloud too large for the fused iteration kernel"; return PCR_EINVAL; }
-    // arguments and start poses live in a per-context device buffer at a FIXED address (the captured graph reads them there)
-    const size_t args_bytes = sizeof(IcpArgs) * 32 + sizeof(IcpInit) * 32;
-    if (!ctx->icp_group_dev) {
-        if (hipMalloc((void **)&ctx->icp_group_dev, args_bytes) != hipSuccess || hipHostMalloc((void **)&ctx->icp_group_host, args_bytes, hipHostMallocDefault) != hipSuccess) {
-            ctx->err = "GICP group: argument buffers"; return PCR_ENOMEM;
-        }
-    }
-    memcpy(ctx->icp_group_host, args.data(), sizeof(IcpArgs) * (size_t)G);
-    memcpy(ctx->icp_group_host + sizeof(IcpArgs) * 32, inits.data(), sizeof(IcpInit) * (size_t)G);
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->icp_group_dev, ctx->icp_group_host, args_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const IcpArgs *dargs = (const IcpArgs *)ctx->icp_group_dev;
-    const IcpInit *dinit = (const IcpInit *)(ctx->icp_group_dev + sizeof(IcpArgs) * 32);
-    PCR_LAUNCH(ctx, k_icp_init_g, dim3(G), dim3(64), 0, ctx->stream, st, dinit);
-    static const int chunk_env = getenv("PCR_ICP_CHUNK") ? atoi(getenv("PCR_ICP_CHUNK")) : 8;
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(buf.dargs, buf.args, buf.bytes, hipMemcpyHostToDevice, ctx->stream));
+    const IcpArgs *dargs = buf.dargs;
+    PCR_LAUNCH(ctx, k_icp_init_g, dim3(G), dim3(64), 0, ctx->stream, st, (const IcpInit *)buf.dinits);
     const int max_it = p ? p->max_iteration : 30;
-    const int total = max_it + 1, CHUNK = chunk_env < 1 ? 1 : (chunk_env > 32 ? 32 : chunk_env);
-    static const bool use_graph = !(getenv("PCR_ICP_GRAPH") && atoi(getenv("PCR_ICP_GRAPH")) == 0);
-    static const bool use_fused_g = !(getenv("PCR_ICP_FUSED") && atoi(getenv("PCR_ICP_FUSED")) == 0);
-    static const bool byval_env = !(getenv("PCR_ICP_BYVAL") && atoi(getenv("PCR_ICP_BYVAL")) == 0);
-    const bool byval = byval_env && G <= ICP_BYVAL;
+    const bool byval = sw.byval && G <= ICP_BYVAL;
     IcpArgsB hb; memset(&hb, 0, sizeof hb);
     for (int g = 0; g < G && g < ICP_BYVAL; g++) hb.a[g] = args[g];
+    // launch 0 is search + linearisation (two kernels), every later launch one fused kernel (or the same two)
+    auto one_kernel = [&](int launch_index) { return launch_index > 0 && sw.fused; };
     auto enqueue = [&](int launch_index) {
-        if (launch_index > 0 && use_fused_g) {
+        if (one_kernel(launch_index)) {
             if (byval) PCR_FUSED_LAUNCH(ctx, k_icp_fused_b, grid, tile_pts, dim3(nbf, G), hb);
             else PCR_FUSED_LAUNCH(ctx, k_icp_fused_g, grid, tile_pts, dim3(nbf, G), dargs);
             return;
         }
         if (grid) PCR_LAUNCH(ctx, k_icp_nn_g<true>, dim3(nbnn, G), dim3(ICP_BS), 0, ctx->stream, dargs);
         else PCR_LAUNCH(ctx, k_icp_nn_g<false>, dim3(nbnn, G), dim3(ICP_BS), 0, ctx->stream, dargs);
-        PCR_LAUNCH(ctx, k_icp_lin_g, dim3(nbmax, G), dim3(LIN_BS), 0, ctx->stream, dargs);
+        PCR_LAUNCH(ctx, k_icp_lin_g, dim3(nblin, G), dim3(LIN_BS), 0, ctx->stream, dargs);
     };
     // One captured chunk per launch FORM (group size, kernel forms, tile, chunk length): what differs from call to call -- the
     // grid widths and, for the by-value kernels, the argument batch -- is patched into the instantiated graph's kernel nodes
     // (hipGraphExecKernelNodeSetParams), so circuits whose clouds differ in size do not pay a capture + instantiate per call.
     const void *dargs_v = dargs;
     std::string now;
-    { const int w[3] = {nbnn, nbmax, nbf}; now.assign((const char *)w, sizeof w); if (byval) now.append((const char *)&hb, sizeof hb); }
-    auto graph_for = [&](int which, int len, hipGraphExec_t *out) -> int {
-        *out = nullptr;
-        if (!use_graph) return PCR_OK;
-        const long long kv[6] = {0x47525550ll /* "GRUP" */, G + (grid ? 1000 : 0) + (use_fused_g ? 0 : 2000) + (byval ? 4000 : 0), tile_pts, len, which, (long long)(uintptr_t)dargs_v};
-        std::string key((const char *)kv, sizeof kv);
-        IcpGraph *hit = nullptr;
-        for (auto &gr : ctx->icp_graphs) if (gr.key == key) { hit = &gr; break; }
+    { const int w[3] = {nbnn, nblin, nbf}; now.assign((const char *)w, sizeof w); if (byval) now.append((const char *)&hb, sizeof hb); }
+    // which = 0: the chunk starts with launch 0, which = 1: later launches only
+    auto graph_for = [&](int which, int len, hipGraphExec_t *exec) -> int {
+        const long long kv[6] = {0x47525550ll /* "GRUP" */, G + (grid ? 1000 : 0) + (sw.fused ? 0 : 2000) + (byval ? 4000 : 0), tile_pts, len, which, (long long)(uintptr_t)dargs_v};
+        const std::string key((const char *)kv, sizeof kv);
+        auto launch_of = [&](int k) { return which == 0 ? k : len + k; };
+        IcpGraph *hit = icp_graph_find(ctx, key);
         if (!hit) {
-            IcpGraph e; e.key = key;
-            // (the graph objects belong to `e` until it is stored: an early error return below must not leak them)
-            struct Owner { IcpGraph *g; ~Owner() { if (g) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); } } } owner{&e};
-            PCR_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            for (int k = 0; k < len; k++) enqueue(which == 0 ? k : len + k);
-            PCR_HIP_CHECK(ctx, hipStreamEndCapture(ctx->stream, &e.graph));
-            PCR_HIP_CHECK(ctx, hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
-            // the captured chunk is a chain: walk it from its root so that nodes[] is in launch order
-            size_t nr = 1; hipGraphNode_t node = nullptr;
-            PCR_HIP_CHECK(ctx, hipGraphGetRootNodes(e.graph, &node, &nr));
-            if (nr != 1) { ctx->err = "GICP group: captured chunk has more than one root"; return PCR_EHIP; }
-            while (node) {
-                hipGraphNodeType nt;
-                PCR_HIP_CHECK(ctx, hipGraphNodeGetType(node, &nt));
-                if (nt != hipGraphNodeTypeKernel) { ctx->err = "GICP group: captured chunk holds a node that is not a kernel"; return PCR_EHIP; }
-                e.nodes.push_back(node);
-                size_t nd = 0;
-                PCR_HIP_CHECK(ctx, hipGraphNodeGetDependentNodes(node, nullptr, &nd));
-                if (nd == 0) break;
-                if (nd != 1) { ctx->err = "GICP group: captured chunk is not a chain"; return PCR_EHIP; }
-                hipGraphNode_t next = nullptr;
-                PCR_HIP_CHECK(ctx, hipGraphNodeGetDependentNodes(node, &next, &nd));
-                node = next;
-            }
-            {   // launch order of a chunk: launch 0 is search + linearisation (two kernels), every later launch one fused kernel (or the same two)
-                size_t expect = 0;
-                for (int k = 0; k < len; k++) expect += ((which == 0 ? k : len + k) > 0 && use_fused_g) ? 1 : 2;
-                if (e.nodes.size() != expect) { ctx->err = "GICP group: captured chunk does not match its launch list"; return PCR_EHIP; }
-            }
-            e.baked = now;
-            if (ctx->icp_graphs.size() >= 48) {           // evict the oldest entry (the stream is drained first: a replay of it may still be queued)
-                PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-                (void)hipGraphExecDestroy(ctx->icp_graphs[0].exec);
-                if (ctx->icp_graphs[0].graph) (void)hipGraphDestroy(ctx->icp_graphs[0].graph);
-                ctx->icp_graphs.erase(ctx->icp_graphs.begin());
-            }
-            owner.g = nullptr;                            // stored: the context owns the graph from here on
-            ctx->icp_graphs.push_back(std::move(e));
-            hit = &ctx->icp_graphs.back();
+            size_t kernels = 0;
+            for (int k = 0; k < len; k++) kernels += one_kernel(launch_of(k)) ? 1 : 2;
+            PCR_TRY(icp_graph_capture(ctx, key, len, kernels, [&](int k) { enqueue(launch_of(k)); }, &hit));
+            hit->baked = now;
         } else if (hit->baked != now) {
-            // One captured chunk per launch FORM (group size, kernel forms, tile, chunk length): what differs from call to call -- the
-            // grid widths and, for the by-value kernels, the argument batch -- is patched into the instantiated graph's kernel nodes
-            // (hipGraphExecKernelNodeSetParams), so circuits whose clouds differ in size do not pay a capture + instantiate per call.
             size_t i = 0;
             for (int k = 0; k < len; k++) {
-                const int launch_index = which == 0 ? k : len + k;
-                const bool one = launch_index > 0 && use_fused_g;
+                const bool one = one_kernel(launch_of(k));
                 for (int part = 0; part < (one ? 1 : 2); part++, i++) {
                     if (i >= hit->nodes.size()) { ctx->err = "GICP group: captured chunk shorter than its launch list"; return PCR_EHIP; }
                     hipKernelNodeParams np;
                     PCR_HIP_CHECK(ctx, hipGraphKernelNodeGetParams(hit->nodes[i], &np));
                     void *kp[1];
                     if (one) { np.gridDim = dim3(nbf, G); kp[0] = byval ? (void *)&hb : (void *)&dargs_v; }
-                    else { np.gridDim = part == 0 ? dim3(nbnn, G) : dim3(nbmax, G); kp[0] = (void *)&dargs_v; }
+                    else { np.gridDim = part == 0 ? dim3(nbnn, G) : dim3(nblin, G); kp[0] = (void *)&dargs_v; }
                     np.kernelParams = kp; np.extra = nullptr;
                     PCR_HIP_CHECK(ctx, hipGraphExecKernelNodeSetParams(hit->exec, hit->nodes[i], &np));
                 }
             }
             hit->baked = now;
         }
-        *out = hit->exec;
+        *exec = hit->exec;
         return PCR_OK;
     };
-    // two read-back slots of G states each in the pinned window
-    const size_t slot_bytes = sizeof(IcpState) * (size_t)G;
-    if (2 * slot_bytes > ctx->pinned_cap) { ctx->err = "GICP group: pinned window too small"; return PCR_ENOMEM; }
-    IcpState *slots[2] = {(IcpState *)ctx->pinned, (IcpState *)(ctx->pinned + slot_bytes)};
-    int launched = 0, cur = 0, prev = -1, n_chunks = 0, next_len = CHUNK;
-    std::vector<int> chunk_first, chunk_last;
-    std::vector<IcpState> fin((size_t)G); bool have = false;
-    for (;;) {
-        const bool enq = launched < total;
-        if (enq) {
-            const int want = launched == 0 ? CHUNK : next_len;
-            const int c = total - launched < want ? total - launched : want;
-            if (ctx->profiling) {
-                while ((int)ctx->prof_events.size() < 2 * (n_chunks + 1)) { hipEvent_t e; PCR_HIP_CHECK(ctx, hipEventCreate(&e)); ctx->prof_events.push_back(e); }
-                PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks], ctx->stream));
-            }
-            hipGraphExec_t ge = nullptr;
-            if (c == want) PCR_TRY(graph_for(launched == 0 ? 0 : 1, c, &ge));
-            if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-            else for (int k = 0; k < c; k++) enqueue(launched + k);
-            if (ctx->profiling) PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks + 1], ctx->stream));
-            chunk_first.push_back(launched); chunk_last.push_back(launched + c);
-            n_chunks++;
-            launched += c;
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(slots[cur], st, slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
-            PCR_HIP_CHECK(ctx, hipEventRecord(ctx->ev[cur], ctx->stream));
-        }
-        if (prev >= 0) {
-            PCR_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev[prev]));
-            bool all = true;
-            for (int g = 0; g < G; g++) all = all && slots[prev][g].done;
-            if (all) { memcpy(fin.data(), slots[prev], slot_bytes); have = true; break; }
-            next_len = 1;                               // the group goes on until its last pair has stopped: the chunk that pair asks for
-            for (int g = 0; g < G; g++)
-                if (!slots[prev][g].done) { const int l = icp_next_chunk(slots[prev][g], args[g].rel_fit, args[g].rel_rmse, CHUNK, true); next_len = l > next_len ? l : next_len; }
-        }
-        if (!enq) break;
-        prev = cur; cur ^= 1;
-    }
-    if (!have) { ctx->err = "GICP group loop ended without a final state"; return PCR_EHIP; }
+    auto issue = [&](int k, int c, bool ragged) -> int {
+        hipGraphExec_t ge = nullptr;
+        if (sw.graph && !ragged) PCR_TRY(graph_for(k == 0 ? 0 : 1, c, &ge));
+        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
+        else for (int i = 0; i < c; i++) enqueue(k + i);
+        return PCR_OK;
+    };
+    std::vector<IcpState> fin((size_t)G);
+    auto judge = [&](const IcpState *s, int, int *next) -> int {
+        bool all = true;
+        for (int g = 0; g < G; g++) all = all && s[g].done;
+        if (all) { fin.assign(s, s + G); *next = 0; return PCR_OK; }
+        *next = 1;                                  // the group goes on until its last pair has stopped: the chunk that pair asks for
+        for (int g = 0; g < G; g++)
+            if (!s[g].done) { const int l = icp_next_chunk(s[g], args[g].rel_fit, args[g].rel_rmse, sw.chunk, true); *next = l > *next ? l : *next; }
+        return PCR_OK;
+    };
+    IcpPump pump;
+    PCR_TRY(pump.init(ctx, st, G));
+    PCR_TRY(pump.run(sw.chunk, max_it + 1, issue, judge));
+    if (!pump.done) { ctx->err = "GICP group loop ended without a final state"; return PCR_EHIP; }
     PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));      // drain the no-op tail: pinned slots, argument buffer and arena are reused
     if (ctx->profiling) {
-        int longest = 0;
-        for (int g = 0; g < G; g++) longest = fin[g].launches > longest ? fin[g].launches : longest;
-        for (int c = 0; c < n_chunks; c++) {
-            const int first = chunk_first[c], last = chunk_last[c];
-            if (last <= longest) {
-                float ms = 0;
-                PCR_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->prof_events[2 * c], ctx->prof_events[2 * c + 1]));
-                ctx->prof[0] += ms; ctx->prof[1] += last - first;
-            }
-        }
-        for (int g = 0; g < G; g++) {
-            ctx->prof[2] += (double)fin[g].t_live * 0.01; ctx->prof[3] += fin[g].launches;
-            ctx->prof[4] += 48.0 * (double)fin[g].ns * (double)fin[g].launches;
-            ctx->prof[11] += (double)fin[g].searched;
-            ctx->prof[6] += (double)fin[g].t_dbg[0] * 0.01; ctx->prof[7] += (double)fin[g].t_dbg[3] * 0.01; ctx->prof[14] += (double)fin[g].t_dbg[1] * 0.01;
-        }
-        ctx->prof[5] += launched; ctx->prof[13] += longest;                // issued / live launches of the GROUP's loop (live: some pair still iterating)
+        int longest = 0;                            // live launches of the GROUP's loop: some pair still iterating
+        for (int g = 0; g < G; g++) { icp_prof_add_state(ctx, fin[g]); longest = fin[g].launches > longest ? fin[g].launches : longest; }
+        PCR_TRY(pump.add_profile(longest));
     }
     for (int g = 0; g < G; g++) {
         state_to_result(fin[g], &out[g]);
@@ -1535,9 +1583,9 @@ int pcr_dev_gicp_group(pcr_context *ctx, int G, const DevCloud *const *src, cons
 // (nothing done) for groups it does not serve: the caller then runs the scales one after the other.
 int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *const *src, const DevCloud *const *tgt, const double *max_dists, const double *T0,
                               const pcr_gicp_params *p, pcr_result *out, int32_t *const *match_dev) {
-    if (G < 1 || G > 32 || S < 1 || S > 8) return 1;
-    static const bool use_fused_g = !(getenv("PCR_ICP_FUSED") && atoi(getenv("PCR_ICP_FUSED")) == 0);
-    if (!use_fused_g || !icp_use_grid()) return 1;
+    if (G < 1 || G > ICP_GROUP_MAX || S < 1 || S > 8) return 1;
+    const IcpSwitches &sw = icp_switches();
+    if (!sw.fused || !sw.grid) return 1;
     if (pcr_options().icp_verify.load(std::memory_order_relaxed)) return 1;
     for (int k = 0; k < G * S; k++) {
         if (!(max_dists[k] > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
@@ -1553,26 +1601,20 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
         if (tile_k != LIN_BS) return 1;
     }
     ArenaMark mark(ctx);
-    static const double gfrac = getenv("PCR_ICP_GAP") ? atof(getenv("PCR_ICP_GAP")) : 0.25;
-    // cell hashes of all G x S targets in one batch
+    // cell hashes of all G x S targets in one batch; the level of each from its unwidened search cap
     std::vector<int> levels((size_t)G * S); std::vector<GridView> views((size_t)G * S);
     for (int k = 0; k < G * S; k++) {
-        double gg = gfrac * max_dists[k]; gg = gg < 0.01 ? 0.01 : (gg > 0.05 ? 0.05 : gg);
-        const double rs = max_dists[k] + gg;
-        levels[k] = pcr_grid_level_for(tgt[k], std::sqrt((double)(float)(rs * rs * (1.0 + 1e-6))));
+        IcpArgs base;
+        icp_set_search_cap(base, max_dists[k], icp_base_gap(max_dists[k]));
+        levels[k] = pcr_grid_level_for(tgt[k], std::sqrt((double)base.r2s));
         if (levels[k] < 0) return 1;
     }
     PCR_TRY(pcr_dev_build_grid_batch(ctx, tgt, levels.data(), G * S, views.data()));
     for (int k = 0; k < G * S; k++) if (!views[k].tab) return 1;
     // per pair: one state and one set of certificate / partial-sum / match buffers (a pair is at one scale at a time), sized by its largest scale
-    const size_t args_bytes = sizeof(IcpArgs) * 32 + sizeof(IcpInit) * 32;
-    if (!ctx->icp_group_dev) {
-        if (hipMalloc((void **)&ctx->icp_group_dev, args_bytes) != hipSuccess || hipHostMalloc((void **)&ctx->icp_group_host, args_bytes, hipHostMallocDefault) != hipSuccess) {
-            ctx->err = "GICP group: argument buffers"; return PCR_ENOMEM;
-        }
-    }
-    IcpArgs *dargs = (IcpArgs *)ctx->icp_group_dev;
-    IcpInit *dinit = (IcpInit *)(ctx->icp_group_dev + sizeof(IcpArgs) * 32);
+    IcpGroupBuf buf;
+    PCR_TRY(icp_group_buf(ctx, &buf));
+    IcpArgs *dargs = buf.dargs;
     const void *dargs_v = dargs;
     IcpState *st = arena<IcpState>(ctx, G), *hist = arena<IcpState>(ctx, (size_t)G * S);
     IcpArgs *all_dev = arena<IcpArgs>(ctx, (size_t)G * S);
@@ -1583,7 +1625,7 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
         int cap_g = 1, rows_g = 1;
         for (int s_ = 0; s_ < S; s_++) {
             const int cap = src[g * S + s_]->cap > 0 ? src[g * S + s_]->cap : 1;
-            const int f_ = ((cap + LIN_BS - 1) / LIN_BS + 7) & ~7;
+            const int f_ = icp_grids(cap, LIN_BS).nbf;
             nbf = f_ > nbf ? f_ : nbf; cap_g = cap > cap_g ? cap : cap_g; rows_g = f_ > rows_g ? f_ : rows_g;
         }
         double *partials = arena<double>(ctx, (size_t)rows_g * NVP);
@@ -1596,9 +1638,8 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
             fill_args(a, src[k], tgt[k], max_dists[k], p, match, st + g, partials, 0);
             a.tile_rt = icp_group_tile(src[k]->cap > 0 ? src[k]->cap : 1, tile_pts);
             a.ref = ref; a.rbest = rbest; a.clist = clist;
-            double gg = gfrac * max_dists[k]; gg = gg < 0.01 ? 0.01 : (gg > 0.05 ? 0.05 : gg);
-            const double rs = max_dists[k] + icp_gap_for_level(tgt[k], levels[k], max_dists[k], gg);      // (as pcr_dev_gicp_group: the cap grows to what the level's cells cover)
-            a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)(rs - max_dists[k]);
+            // (as pcr_dev_gicp_group: the cap grows to what the level's cells cover)
+            icp_set_search_cap(a, max_dists[k], icp_gap_for_level(tgt[k], levels[k], max_dists[k], icp_base_gap(max_dists[k])));
             a.grid = views[k];
             a.ms_args = all_dev + (size_t)g * S; a.ms_self = dargs + g; a.ms_hist = hist + (size_t)g * S; a.ms_scales = S; a.ms_index = s_;
         }
@@ -1609,100 +1650,53 @@ int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *co
     // (pageable sources: staged before the calls return)
     PCR_HIP_CHECK(ctx, hipMemcpyAsync(all_dev, all.data(), sizeof(IcpArgs) * all.size(), hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP_CHECK(ctx, hipMemcpyAsync(dargs, first.data(), sizeof(IcpArgs) * (size_t)G, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(dinit, inits.data(), sizeof(IcpInit) * (size_t)G, hipMemcpyHostToDevice, ctx->stream));
-    PCR_LAUNCH(ctx, k_icp_init_g, dim3(G), dim3(64), 0, ctx->stream, st, (const IcpInit *)dinit);
-    static const int chunk_env = getenv("PCR_ICP_CHUNK") ? atoi(getenv("PCR_ICP_CHUNK")) : 8;
-    const int CHUNK = chunk_env < 1 ? 1 : (chunk_env > 32 ? 32 : chunk_env);
-    static const bool use_graph = !(getenv("PCR_ICP_GRAPH") && atoi(getenv("PCR_ICP_GRAPH")) == 0);
-    // (every tile of the group is 512 points: the <512> form of the kernel, one point per lane, instead of the <1024> form with its second point masked off)
-    static const bool form512 = !(getenv("PCR_ICP_FORM512") && atoi(getenv("PCR_ICP_FORM512")) == 0);
-    const int launch_tile = form512 ? LIN_BS : tile_pts;
-    auto enqueue_fused = [&]() { PCR_FUSED_LAUNCH(ctx, k_icp_fused_g, true, launch_tile, dim3(nbf, G), (const IcpArgs *)dargs); };
-    auto graph_for = [&](int len, hipGraphExec_t *outg) -> int {     // a chunk of `len` fused launches, captured once per (G, tile, grid width, length)
-        *outg = nullptr;
-        if (!use_graph) return PCR_OK;
-        const long long kv[6] = {0x47525053ll /* "GRPS" */, G, launch_tile, len, nbf, (long long)(uintptr_t)dargs_v};
-        std::string key((const char *)kv, sizeof kv);
-        for (auto &gr : ctx->icp_graphs) if (gr.key == key) { *outg = gr.exec; return PCR_OK; }
-        IcpGraph e; e.key = key;
-        struct Owner { IcpGraph *g; ~Owner() { if (g) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); } } } owner{&e};
-        PCR_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-        for (int k = 0; k < len; k++) enqueue_fused();
-        PCR_HIP_CHECK(ctx, hipStreamEndCapture(ctx->stream, &e.graph));
-        PCR_HIP_CHECK(ctx, hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
-        if (ctx->icp_graphs.size() >= 48) {
-            PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipGraphExecDestroy(ctx->icp_graphs[0].exec);
-            if (ctx->icp_graphs[0].graph) (void)hipGraphDestroy(ctx->icp_graphs[0].graph);
-            ctx->icp_graphs.erase(ctx->icp_graphs.begin());
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(buf.dinits, inits.data(), sizeof(IcpInit) * (size_t)G, hipMemcpyHostToDevice, ctx->stream));
+    PCR_LAUNCH(ctx, k_icp_init_g, dim3(G), dim3(64), 0, ctx->stream, st, (const IcpInit *)buf.dinits);
+    // (every tile of the group is 512 points: the <512> form of the kernel, one point per lane, instead of the <1024> form with its second point
+    // masked off: 2840 against 2760 pairs/s)
+    auto enqueue_fused = [&](int) { PCR_LAUNCH(ctx, (k_icp_fused_g<LIN_BS, true>), dim3(nbf, G), dim3(FUSED_BS), 0, ctx->stream, (const IcpArgs *)dargs); };
+    auto issue = [&](int, int c, bool) -> int {      // a chunk of c fused launches, captured once per (G, grid width, length)
+        IcpGraph *hit = nullptr;
+        if (sw.graph) {
+            const long long kv[6] = {0x47525053ll /* "GRPS" */, G, LIN_BS, c, nbf, (long long)(uintptr_t)dargs_v};
+            const std::string key((const char *)kv, sizeof kv);
+            hit = icp_graph_find(ctx, key);
+            if (!hit) PCR_TRY(icp_graph_capture(ctx, key, c, 0, enqueue_fused, &hit));
         }
-        owner.g = nullptr;
-        ctx->icp_graphs.push_back(std::move(e));
-        *outg = ctx->icp_graphs.back().exec;
+        if (hit) PCR_HIP_CHECK(ctx, hipGraphLaunch(hit->exec, ctx->stream));
+        else for (int i = 0; i < c; i++) enqueue_fused(i);
         return PCR_OK;
     };
-    const size_t slot_bytes = sizeof(IcpState) * (size_t)G;
-    if (2 * slot_bytes > ctx->pinned_cap) { ctx->err = "GICP group: pinned window too small"; return PCR_ENOMEM; }
-    IcpState *slots[2] = {(IcpState *)ctx->pinned, (IcpState *)(ctx->pinned + slot_bytes)};
-    int cur = 0, prev = -1, next_len = CHUNK, launched = 0, live_launches = 0, n_chunks = 0;
-    std::vector<int> chunk_first, chunk_last;
     const int max_it = p ? p->max_iteration : 30;
-    const long long launch_limit = (long long)S * ((long long)max_it + 2) + 4 * CHUNK + 64;
-    bool finished = false;
-    for (;;) {
-        const int c = next_len;
-        if (ctx->profiling) {
-            while ((int)ctx->prof_events.size() < 2 * (n_chunks + 1)) { hipEvent_t e; PCR_HIP_CHECK(ctx, hipEventCreate(&e)); ctx->prof_events.push_back(e); }
-            PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks], ctx->stream));
+    const long long launch_limit = (long long)S * ((long long)max_it + 2) + 4 * sw.chunk + 64;
+    IcpPump pump;
+    int live_launches = 0;
+    auto judge = [&](const IcpState *s, int upto, int *next) -> int {
+        bool all_done = true;
+        *next = 1;
+        for (int g = 0; g < G; g++) {
+            if (s[g].done) continue;                    // (done is set by the LAST scale only)
+            all_done = false;
+            const int l = icp_next_chunk(s[g], all[(size_t)g * S].rel_fit, all[(size_t)g * S].rel_rmse, sw.chunk, true);
+            *next = l > *next ? l : *next;
         }
-        hipGraphExec_t ge = nullptr;
-        PCR_TRY(graph_for(c, &ge));
-        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-        else for (int k = 0; k < c; k++) enqueue_fused();
-        if (ctx->profiling) PCR_HIP_CHECK(ctx, hipEventRecord(ctx->prof_events[2 * n_chunks + 1], ctx->stream));
-        chunk_first.push_back(launched); chunk_last.push_back(launched + c); n_chunks++;
-        launched += c;
-        PCR_HIP_CHECK(ctx, hipMemcpyAsync(slots[cur], st, slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP_CHECK(ctx, hipEventRecord(ctx->ev[cur], ctx->stream));
-        if (prev >= 0) {
-            PCR_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev[prev]));
-            bool all_done = true;
-            next_len = 1;
-            for (int g = 0; g < G; g++) {
-                const IcpState &sg = slots[prev][g];
-                if (sg.done) continue;                    // (done is set by the LAST scale only)
-                all_done = false;
-                const int l = icp_next_chunk(sg, all[(size_t)g * S].rel_fit, all[(size_t)g * S].rel_rmse, CHUNK, true);
-                next_len = l > next_len ? l : next_len;
-            }
-            if (all_done) { finished = true; break; }
-            live_launches = launched - c;                 // (the chunk just queued may still turn out to be needed: counted when the next read-back says so)
-        }
-        if (launched > launch_limit) { ctx->err = "GICP group loop (all scales) did not end"; return PCR_EHIP; }
-        prev = cur; cur ^= 1;
-    }
-    if (!finished) { ctx->err = "GICP group loop ended without a final state"; return PCR_EHIP; }
+        if (all_done) { *next = 0; return PCR_OK; }
+        live_launches = upto;                           // (the chunk just queued may still turn out to be needed: counted when the next read-back says so)
+        if (pump.launched > launch_limit) { ctx->err = "GICP group loop (all scales) did not end"; return PCR_EHIP; }
+        return PCR_OK;
+    };
+    PCR_TRY(pump.init(ctx, st, G));
+    PCR_TRY(pump.run(sw.chunk, INT_MAX, issue, judge));     // (no fixed total: a pair moves through its scales on the device; launch_limit guards the loop)
+    if (!pump.done) { ctx->err = "GICP group loop ended without a final state"; return PCR_EHIP; }
     std::vector<IcpState> hh((size_t)G * S);
     PCR_HIP_CHECK(ctx, hipMemcpyAsync(hh.data(), hist, sizeof(IcpState) * hh.size(), hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));      // (also drains the no-op tail: pinned slots, argument table and arena are reused)
     for (int k = 0; k < G * S; k++) {
-        const IcpState &sg = hh[k];
-        state_to_result(sg, &out[k]);
-        for (int q = 0; q < 16; q++) if (!std::isfinite(sg.T[q])) { ctx->err = "non-finite pose"; return PCR_ENUMERIC; }
-        if (ctx->profiling) {
-            ctx->prof[2] += (double)sg.t_live * 0.01; ctx->prof[3] += sg.launches; ctx->prof[4] += 48.0 * (double)sg.ns * (double)sg.launches; ctx->prof[11] += (double)sg.searched;
-            ctx->prof[6] += (double)sg.t_dbg[0] * 0.01; ctx->prof[7] += (double)sg.t_dbg[3] * 0.01; ctx->prof[14] += (double)sg.t_dbg[1] * 0.01;
-        }
+        state_to_result(hh[k], &out[k]);
+        for (int q = 0; q < 16; q++) if (!std::isfinite(hh[k].T[q])) { ctx->err = "non-finite pose"; return PCR_ENUMERIC; }
+        if (ctx->profiling) icp_prof_add_state(ctx, hh[k]);
     }
-    if (ctx->profiling) {
-        for (int c = 0; c < n_chunks; c++)
-            if (chunk_last[c] <= live_launches) {          // chunks during which some pair was still iterating: HIP-event time / launches = launch period of the group
-                float ms = 0;
-                PCR_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->prof_events[2 * c], ctx->prof_events[2 * c + 1]));
-                ctx->prof[0] += ms; ctx->prof[1] += chunk_last[c] - chunk_first[c];
-            }
-        ctx->prof[5] += launched; ctx->prof[13] += live_launches;
-    }
+    if (ctx->profiling) PCR_TRY(pump.add_profile(live_launches));      // live: chunks during which some pair was still iterating
     return PCR_OK;
 }
 
@@ -1711,8 +1705,7 @@ int pcr_dev_linearize_once(pcr_context *ctx, const DevCloud *src, const DevCloud
     if (!(max_dist > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
     ArenaMark mark(ctx);
     const int cap = src->cap > 0 ? src->cap : 1;
-    const int nbmax = (cap + LIN_BS - 1) / LIN_BS < LIN_MAX_BLOCKS ? (cap + LIN_BS - 1) / LIN_BS : LIN_MAX_BLOCKS;
-    const int nbnn = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT);
+    const int nbmax = icp_grids(cap, 0).nbmax, nbnn = icp_grids(cap, 0).nbnn;
     IcpState *st = arena<IcpState>(ctx, 1);
     double *partials = arena<double>(ctx, (size_t)nbmax * NVP);
     int32_t *match = match_dev ? match_dev : arena<int32_t>(ctx, cap);
@@ -1736,8 +1729,7 @@ int pcr_dev_evaluate(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt,
     if (!(max_dist > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
     ArenaMark mark(ctx);
     const int cap = src->cap > 0 ? src->cap : 1;
-    const int nbmax = (cap + LIN_BS - 1) / LIN_BS < LIN_MAX_BLOCKS ? (cap + LIN_BS - 1) / LIN_BS : LIN_MAX_BLOCKS;
-    const int nbnn = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT);
+    const int nbmax = icp_grids(cap, 0).nbmax, nbnn = icp_grids(cap, 0).nbnn;
     IcpState *st = arena<IcpState>(ctx, 1);
     double *partials = arena<double>(ctx, (size_t)nbmax * NVP);
     int32_t *match = match_dev ? match_dev : arena<int32_t>(ctx, cap);
@@ -1768,8 +1760,7 @@ int pcr_dev_evaluate_group(pcr_context *ctx, int G, const DevCloud *const *src, 
     int gmax = 1, gnn = 1;
     for (int g = 0; g < G; g++) {
         const int cap = src[g]->cap > 0 ? src[g]->cap : 1;
-        const int nbmax = (cap + LIN_BS - 1) / LIN_BS < LIN_MAX_BLOCKS ? (cap + LIN_BS - 1) / LIN_BS : LIN_MAX_BLOCKS;
-        const int nbnn = (cap + ICP_BS / OCT - 1) / (ICP_BS / OCT);
+        const int nbmax = icp_grids(cap, 0).nbmax, nbnn = icp_grids(cap, 0).nbnn;
         double *partials = arena<double>(ctx, (size_t)nbmax * NVP);
         if (!partials || !match_dev[g]) return PCR_ENOMEM;
         memset(&args[g], 0, sizeof(IcpArgs));
