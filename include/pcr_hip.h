@@ -81,6 +81,16 @@ typedef struct {
     int32_t max_iteration;
 } pcr_icp_params;
 
+/* == TransformationEstimationForColoredICP(lambda_geometric, kernel) + ICPConvergenceCriteria(...)  (pcr_registration_colored_icp below) */
+typedef struct {
+    double lambda_geometric;  /* weight of the geometric term, 0.968; a value outside [0, 1] is reset to 0.968 */
+    int32_t loss;             /* pcr_loss_kind of the robust kernel */
+    double loss_k;            /* GMLoss k */
+    double relative_fitness;
+    double relative_rmse;
+    int32_t max_iteration;
+} pcr_colored_icp_params;
+
 /* per-scale record of pcr_multiscale_gicp (what the roofline byte model needs) */
 typedef struct {
     int64_t n_voxel[2];       /* D_k: source, target after voxel_down_sample           */
@@ -117,6 +127,12 @@ int pcr_bounds(pcr_context *ctx, const float *xyz, int64_t n, double *bounds6);
  * order of the voxel index (Open3D's order is unspecified hash order).                      */
 int pcr_voxel_down_sample(pcr_context *ctx, const float *xyz, const float *normals_in, int64_t n, double voxel_size,
                           float *out_xyz, float *out_normals, int64_t *out_n);
+
+/* == PointCloud.voxel_down_sample of a cloud that also carries colours (N x 3 float32 in [0, 1], device; optional like the normals): out_colors
+ * is the arithmetic mean per voxel, summed in float64 in input order like the points.  out_xyz and out_normals are bit for bit what
+ * pcr_voxel_down_sample returns, in the same Morton order.                                                                             */
+int pcr_voxel_down_sample_ex(pcr_context *ctx, const float *xyz, const float *normals_in, const float *colors_in, int64_t n, double voxel_size,
+                             float *out_xyz, float *out_normals, float *out_colors, int64_t *out_n);
 
 /* == PointCloud.remove_statistical_outlier (ALL_FUNCTIONS.py:297-298). keep_mask: n bytes (device),
  * out_xyz optional compacted cloud (capacity n), out_index optional int64 indices (device).      */
@@ -156,6 +172,30 @@ int pcr_registration_generalized_icp_cov(pcr_context *ctx, const float *src_xyz,
 int pcr_registration_icp(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
                          int64_t n_tgt, double max_correspondence_distance, const double *init_T,
                          const pcr_icp_params *params, pcr_result *result, int32_t *correspondences);
+
+/* == registration_colored_icp(source, target, max_correspondence_distance, init, TransformationEstimationForColoredICP(lambda_geometric, kernel),
+ *    criteria) (Park, Zhou, Koltun, ICCV 2017; Open3D ColoredICP.cpp).  Open3D is not at hand and the reference never calls it, so this statement
+ *    is the specification.  The intensity of a point is I = (r + g + b) / 3, colours in [0, 1].
+ *    Colour gradient of target point p with normal n (as given, not normalised) and intensity I_p (pcr_color_gradient; the registration uses the
+ *    hybrid search radius = 2 * max_correspondence_distance, max_nn = 30): the search returns nn neighbours, the first is p itself; nn < 4: the
+ *    gradient is 0.  Otherwise, for every other neighbour q_k, k = 1 .. nn-1: q'_k = q_k - ((q_k - p).n) n, row A_{k-1} = q'_k - p,
+ *    b_{k-1} = I(q_k) - I_p; the last row is A_{nn-1} = (nn - 1) n with b = 0; the gradient d solves (A^T A) d = A^T b by LDLT.  The device keeps
+ *    the 6 + 3 moments in float64, centred on p, summed in the list's order (float64 d^2, then caller index: the k-d tree's order).
+ *    The loop is RegistrationICP's, as in pcr_registration_icp: search at init, then update / left-multiply / search, until |d fitness| <
+ *    relative_fitness and |d RMSE| < relative_rmse, or max_iteration; fitness and inlier_rmse are the geometric ones of the search.
+ *    Update: with lambda = lambda_geometric, s the transformed source point, t / n / d the target's point, normal and gradient and I_s, I_t the
+ *    intensities, every correspondence gives two rows: r_G = sqrt(lambda) (s - t).n, J_G = sqrt(lambda) [s x n, n]; and, with
+ *    s' = s - ((s - t).n) n and d_M = -d + (d.n) n, r_I = sqrt(1 - lambda) (I_s - (d.(s' - t) + I_t)), J_I = sqrt(1 - lambda) [s x d_M, d_M].  Each row is
+ *    weighted by the kernel's weight of its own scaled residual (L2 / L1 / GM as for point-to-plane); both go into one 6x6 system, solved and
+ *    turned into a pose exactly as the point-to-plane update (LDLT, Rz Ry Rx).  No correspondences: the update is the identity.
+ *    src_colors, tgt_normals and tgt_colors are required (PCR_EINVAL names what is missing).  correspondences optional device int32 [n_src x 2]. */
+int pcr_registration_colored_icp(pcr_context *ctx, const float *src_xyz, const float *src_colors, int64_t n_src, const float *tgt_xyz,
+                                 const float *tgt_normals, const float *tgt_colors, int64_t n_tgt, double max_correspondence_distance,
+                                 const double *init_T, const pcr_colored_icp_params *params, pcr_result *result, int32_t *correspondences);
+/* the colour gradients of a cloud alone (the statement above) over the neighbours of search_kind / knn / radius (PCR_SEARCH_KNN or
+ * PCR_SEARCH_HYBRID, knn in 1..32): gradient3 = n x 3 float32 (device), caller order.  Asynchronous on the context's stream. */
+int pcr_color_gradient(pcr_context *ctx, const float *xyz, const float *normals, const float *colors, int64_t n, int search_kind, int knn,
+                       double radius, float *gradient3);
 
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)

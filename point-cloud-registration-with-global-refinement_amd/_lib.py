@@ -37,6 +37,11 @@ class PcrIcpParams(C.Structure):
                 ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
 
 
+class PcrColoredIcpParams(C.Structure):
+    _fields_ = [("lambda_geometric", C.c_double), ("loss", C.c_int32), ("loss_k", C.c_double), ("relative_fitness", C.c_double),
+                ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
+
+
 class PcrRansacParams(C.Structure):
     _fields_ = [("ransac_n", C.c_int32), ("with_scaling", C.c_int32), ("max_iteration", C.c_int32), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("edge_length_threshold", C.c_double), ("distance_threshold", C.c_double),
@@ -93,6 +98,7 @@ EXPORTS = [
     "pcr_profile_enable", "pcr_profile_read", "pcr_registration_generalized_icp_cov", "pcr_register_pairs", "pcr_pool_profile",
     "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists",
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
+    "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
 ]
 
 _lib = None

@@ -30,7 +30,8 @@
 
 // _COV: per-point covariances given (GICP_robusto path); P2PL / P2P / P2P_SCALED: registration_icp with TransformationEstimationPointToPlane /
 // PointToPoint(with_scaling = false / true) -- k_icp_nn + k_icp_iter<MODE> only, never the fused or group forms
-enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2, ICP_MODE_P2PL = 3, ICP_MODE_P2P = 4, ICP_MODE_P2P_SCALED = 5 };
+// COLORED: registration_colored_icp -- k_icp_nn + k_icp_iter_colored, a sibling of k_icp_iter with its own argument block (IcpColorArgs)
+enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2, ICP_MODE_P2PL = 3, ICP_MODE_P2P = 4, ICP_MODE_P2P_SCALED = 5, ICP_MODE_COLORED = 6 };
 
 struct IcpState {
     double T[16];
@@ -780,6 +781,77 @@ template <int MODE> __global__ void __launch_bounds__(LIN_BS) k_icp_iter(IcpArgs
 // group form: blockIdx.y = pair.  A pair uses min(its own tile count, the grid's width) partial rows, which is what the one-pair launch
 // uses (its grid is min(tiles, LIN_MAX_BLOCKS) wide and the group's grid is the widest of those): same sums, same order.
 template <int MODE> __global__ void __launch_bounds__(LIN_BS) k_icp_iter_g(const IcpArgs *__restrict__ a) { d_icp_iter<MODE>(a[blockIdx.y]); }
+// ================================================================ colored ICP (TransformationEstimationForColoredICP; include/pcr_hip.h)
+// A sibling of k_icp_iter<ICP_MODE_P2PL>, not a mode of it: what the estimator adds -- lambda and three per-point arrays -- travels in a second
+// kernel argument, so IcpArgs keeps the layout the fused, by-value and group kernels read.  Per correspondence two rows go into the same
+// 21 + 6 float64 sums, the geometric one first: r_G = sqrt(lambda) (q - t).n, J_G = sqrt(lambda) [q x n; n] and, with q' = q - ((q - t).n) n and
+// d_M = -d + (d.n) n, r_I = sqrt(1 - lambda) (I_s - (d.(q' - t) + I_t)), J_I = sqrt(1 - lambda) [q x d_M; d_M]; each weighted by the kernel of its
+// own scaled residual.  Reduction, ticket, convergence test, LDLT and pose update are icp_finish's, as for point-to-plane.
+struct IcpColorArgs {
+    const float4 *tgt_grad;          // colour gradient d of every target point (k_color_gradient), Morton order
+    const double *tgt_int, *src_int; // intensities (r + g + b) / 3 of the target and source points, Morton order
+    double sqrt_lg, sqrt_lp;         // sqrt(lambda_geometric), sqrt(1 - lambda_geometric)
+};
+__device__ static inline void icp_row6(double w, const double *J, double r, double *acc) {
+    int t = 0;
+#pragma unroll
+    for (int p = 0; p < 6; p++) {
+        const double wj = w * J[p];
+#pragma unroll
+        for (int q = p; q < 6; q++) acc[t++] += wj * J[q];
+        acc[21 + p] += wj * r;
+    }
+}
+__device__ static inline void icp_point_colored(const IcpArgs &a, const IcpColorArgs &c, const double *T, int i, int cand, double *acc) {
+    if (cand < 0) return;
+    const float4 pf = a.src_pts[i];
+    const double px = pf.x, py = pf.y, pz = pf.z;
+    const double qx = T[0] * px + T[1] * py + T[2] * pz + T[3];
+    const double qy = T[4] * px + T[5] * py + T[6] * pz + T[7];
+    const double qz = T[8] * px + T[9] * py + T[10] * pz + T[11];
+    const float4 tf = a.tgt_pts[cand];
+    const double dx = qx - (double)tf.x, dy = qy - (double)tf.y, dz = qz - (double)tf.z;
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    if (!(d2 < a.max_dist2)) { a.match[i] = -(cand + 2); return; }      // beyond max_dist in float64: keep the candidate as next start hint
+    acc[28] += d2; acc[29] += 1.0;
+    const float4 tn = a.tgt_nrm[cand], tg = c.tgt_grad[cand];
+    const double nx = tn.x, ny = tn.y, nz = tn.z, gx = tg.x, gy = tg.y, gz = tg.z;
+    const double it = c.tgt_int[cand], is = c.src_int[i];
+    const double sd = dx * nx + dy * ny + dz * nz;                       // (q - t).n over the target normal AS STORED
+    double J[6];
+    J[0] = c.sqrt_lg * (qy * nz - qz * ny); J[1] = c.sqrt_lg * (qz * nx - qx * nz); J[2] = c.sqrt_lg * (qx * ny - qy * nx);
+    J[3] = c.sqrt_lg * nx; J[4] = c.sqrt_lg * ny; J[5] = c.sqrt_lg * nz;
+    const double rg = c.sqrt_lg * sd;
+    icp_row6(icp_weight(a.loss, a.loss_k, rg), J, rg, acc);
+    const double ex = dx - sd * nx, ey = dy - sd * ny, ez = dz - sd * nz;   // q' - t
+    const double gn = gx * nx + gy * ny + gz * nz;
+    const double mx = gn * nx - gx, my = gn * ny - gy, mz = gn * nz - gz;    // d_M
+    const double ri = c.sqrt_lp * (is - ((gx * ex + gy * ey + gz * ez) + it));
+    J[0] = c.sqrt_lp * (qy * mz - qz * my); J[1] = c.sqrt_lp * (qz * mx - qx * mz); J[2] = c.sqrt_lp * (qx * my - qy * mx);
+    J[3] = c.sqrt_lp * mx; J[4] = c.sqrt_lp * my; J[5] = c.sqrt_lp * mz;
+    icp_row6(icp_weight(a.loss, a.loss_k, ri), J, ri, acc);
+    acc[27] += rg * rg + ri * ri;
+}
+__global__ void __launch_bounds__(LIN_BS) k_icp_iter_colored(IcpArgs a, IcpColorArgs c) {
+    IcpState *st = a.state;
+    if (st->done) return;
+    const int ns = *a.ns_ptr;
+    int nb = (ns + LIN_BS - 1) / LIN_BS;
+    if (nb < 1) nb = 1;
+    if (nb > (int)gridDim.x) nb = gridDim.x;
+    if ((int)blockIdx.x >= nb) return;
+    const unsigned long long t_entry = wall_clock64();
+    const int launches = st->launches;
+    double T[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) T[k] = st->T[k];
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) acc[k] = 0.0;
+    for (int i = blockIdx.x * LIN_BS + threadIdx.x; i < ns; i += nb * LIN_BS) icp_point_colored(a, c, T, i, a.match[i], acc);
+    icp_finish<ICP_MODE_COLORED, LIN_BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);
+}
+
 // tile form (every GICP linearisation that is not fused into k_icp_fused): workgroup b owns the 512-point tile b, so the partial rows and
 // their order are those of k_icp_fused<512>; held at 128 VGPRs = two workgroups per CU (the strided loop of k_icp_iter takes 218 and is
 // capped at 128 workgroups: a cold launch over 1.6M points took 0.8-3 ms)
@@ -1303,12 +1375,14 @@ static void icp_prof_add_state(pcr_context *ctx, const IcpState &s) {
 // The one-pair loop of every estimator: mode = ICP_MODE_GICP (GICP_COV when both clouds carry covariances), or P2PL / P2P / P2P_SCALED
 // (pcr_dev_icp), which take the same searches and the same loop through k_icp_nn + k_icp_iter<mode>
 static int icp_loop(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,
-                    const pcr_gicp_params *p, int mode, pcr_result *out, int32_t *match_dev) {
+                    const pcr_gicp_params *p, int mode, pcr_result *out, int32_t *match_dev, const IcpColorArgs *col = nullptr) {
     if (!(max_dist > 0.0)) { ctx->err = "max_correspondence_distance <= 0"; return PCR_EINVAL; }
     const bool gicp = mode == ICP_MODE_GICP;
     const bool use_cov = gicp && src->cov6 && tgt->cov6;
     if (gicp && !use_cov && (!src->nrm || !tgt->nrm)) { ctx->err = "GICP needs normals (or covariances) on both clouds"; return PCR_EINVAL; }
     if (mode == ICP_MODE_P2PL && !tgt->nrm) { ctx->err = "point-to-plane ICP needs normals on the target"; return PCR_EINVAL; }
+    if (mode == ICP_MODE_COLORED && (!tgt->nrm || !col || !col->tgt_grad || !col->tgt_int || !col->src_int)) { ctx->err = "colored ICP needs target normals, gradients and both intensities"; return PCR_EINVAL; }
+    const IcpColorArgs ca = col ? *col : IcpColorArgs{};
     ArenaMark mark(ctx);
     const IcpSwitches &sw = icp_switches();
     const int cap = src->cap > 0 ? src->cap : 1;
@@ -1354,6 +1428,7 @@ static int icp_loop(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, 
         if (use_cov) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_GICP_COV>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
         else if (gicp) PCR_LAUNCH(ctx, k_icp_lin, dim3(n.nblin), dim3(LIN_BS), 0, ctx->stream, a);
         else if (mode == ICP_MODE_P2PL) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2PL>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
+        else if (mode == ICP_MODE_COLORED) PCR_LAUNCH(ctx, k_icp_iter_colored, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a, ca);
         else if (mode == ICP_MODE_P2P) PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
         else PCR_LAUNCH(ctx, k_icp_iter<ICP_MODE_P2P_SCALED>, dim3(n.nbmax), dim3(LIN_BS), 0, ctx->stream, a);
     };
@@ -1364,6 +1439,7 @@ static int icp_loop(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, 
         // (the estimator is part of the key: point-to-point and point-to-plane problems have byte-identical arguments)
         const int extra[8] = {n.nbnn, n.nbmax, use_cov ? 1 : 0, len, fused ? n.nbf + (tile_pts << 16) : 0, which, grid ? 1 : 0, mode};
         key.append((const char *)extra, sizeof extra);
+        if (mode == ICP_MODE_COLORED) key.append((const char *)&ca, sizeof ca);      // lambda and the three arrays are baked into the captured launches too
         IcpGraph *hit = icp_graph_find(ctx, key);
         if (!hit) {
             PCR_TRY(icp_graph_capture(ctx, key, len, 0, [&](int k) { enqueue(which == 0 ? k : len + k); }, &hit));
@@ -1418,6 +1494,20 @@ int pcr_dev_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, doub
     g.loss = mode == ICP_MODE_P2PL ? p->loss : PCR_LOSS_L2; g.loss_k = mode == ICP_MODE_P2PL ? p->loss_k : 1.0; g.epsilon = 1e-3;
     g.relative_fitness = p->relative_fitness; g.relative_rmse = p->relative_rmse; g.max_iteration = p->max_iteration;
     return icp_loop(ctx, src, tgt, max_dist, T0, &g, mode, out, match_dev);
+}
+
+int pcr_dev_colored_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0, const pcr_colored_icp_params *p,
+                        const double *src_int, const double *tgt_int, const float4 *tgt_grad, pcr_result *out, int32_t *match_dev) {
+    if (p->loss < PCR_LOSS_L2 || p->loss > PCR_LOSS_GM) { ctx->err = "unknown robust kernel (pcr_loss_kind)"; return PCR_EINVAL; }
+    const double lambda = (p->lambda_geometric >= 0.0 && p->lambda_geometric <= 1.0) ? p->lambda_geometric : 0.968;      // Open3D resets a value outside [0, 1]
+    pcr_gicp_params g;
+    memset(&g, 0, sizeof g);
+    g.loss = p->loss; g.loss_k = p->loss_k; g.epsilon = 1e-3;
+    g.relative_fitness = p->relative_fitness; g.relative_rmse = p->relative_rmse; g.max_iteration = p->max_iteration;
+    IcpColorArgs c;
+    memset(&c, 0, sizeof c);                 // (the struct's bytes are part of the graph key)
+    c.tgt_grad = tgt_grad; c.tgt_int = tgt_int; c.src_int = src_int; c.sqrt_lg = std::sqrt(lambda); c.sqrt_lp = std::sqrt(1.0 - lambda);
+    return icp_loop(ctx, src, tgt, max_dist, T0, &g, ICP_MODE_COLORED, out, match_dev, &c);
 }
 
 // ---- the GICP loops of a GROUP of pairs in lockstep: every launch serves all G problems (blockIdx.y = pair; argument structs and

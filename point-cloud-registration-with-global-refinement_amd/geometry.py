@@ -68,6 +68,7 @@ class PointCloud:
         self._xyz = None          # torch (N,3) float32 cuda
         self._nrm = None          # torch (N,3) float32 cuda
         self._cov = None          # torch (N,6) float32 cuda  (xx,xy,xz,yy,yz,zz)
+        self._col = None          # torch (N,3) float32 cuda  (r,g,b in [0, 1])
         if points is not None:
             self.points = points
 
@@ -83,6 +84,7 @@ class PointCloud:
         self._xyz = _dev_f32(value, 3)
         self._nrm = None
         self._cov = None
+        self._col = None
 
     @property
     def normals(self):
@@ -93,6 +95,16 @@ class PointCloud:
     @normals.setter
     def normals(self, value):
         self._nrm = _dev_f32(value, 3)
+
+    @property
+    def colors(self):
+        if self._col is None:
+            return np.zeros((0, 3), np.float64)
+        return self._col.detach().cpu().numpy().astype(np.float64)
+
+    @colors.setter
+    def colors(self, value):
+        self._col = _dev_f32(value, 3)
 
     @property
     def covariances(self):
@@ -116,11 +128,22 @@ class PointCloud:
     def has_covariances(self):
         return self._cov is not None and self._cov.shape[0] == len(self) and len(self) > 0
 
+    def has_colors(self):
+        return self._col is not None and self._col.shape[0] == len(self) and len(self) > 0
+
+    def paint_uniform_color(self, color):
+        """``PointCloud.paint_uniform_color`` (ALL_FUNCTIONS.py:23,155-156): every point gets the colour ``color`` = (r, g, b) in [0, 1]; returns self."""
+        torch = _torch()
+        rgb = torch.as_tensor(np.asarray(color, dtype=np.float32).reshape(3), device="cuda")
+        self._col = rgb.repeat(len(self), 1).contiguous()
+        return self
+
     def __deepcopy__(self, memo):
         out = PointCloud()
         out._xyz = None if self._xyz is None else self._xyz.clone()
         out._nrm = None if self._nrm is None else self._nrm.clone()
         out._cov = None if self._cov is None else self._cov.clone()
+        out._col = None if self._col is None else self._col.clone()
         return out
 
     def __repr__(self):
@@ -134,6 +157,9 @@ class PointCloud:
 
     def device_normals(self):
         return self._nrm
+
+    def device_colors(self):
+        return self._col
 
     # ---- methods -----------------------------------------------------------------------------
     def get_min_bound(self):
@@ -158,13 +184,22 @@ class PointCloud:
         has_n = self.has_normals()
         out_nrm = torch.empty((max(n, 1), 3), dtype=torch.float32, device="cuda") if has_n else None
         m = C.c_int64(0)
-        ctx.check(ctx.lib.pcr_voxel_down_sample(ctx.handle, _ptr(xyz), _ptr(self._nrm if has_n else None), C.c_int64(n),
-                                                C.c_double(voxel_size), _ptr(out_xyz), _ptr(out_nrm), C.byref(m)),
-                  "voxel_down_sample")
+        out_col = None
+        if self.has_colors():          # colours are averaged per voxel too (Open3D); points and normals are those of the call below
+            out_col = torch.empty((max(n, 1), 3), dtype=torch.float32, device="cuda")
+            ctx.check(ctx.lib.pcr_voxel_down_sample_ex(ctx.handle, _ptr(xyz), _ptr(self._nrm if has_n else None), _ptr(self._col), C.c_int64(n),
+                                                       C.c_double(voxel_size), _ptr(out_xyz), _ptr(out_nrm), _ptr(out_col), C.byref(m)),
+                      "voxel_down_sample")
+        else:
+            ctx.check(ctx.lib.pcr_voxel_down_sample(ctx.handle, _ptr(xyz), _ptr(self._nrm if has_n else None), C.c_int64(n),
+                                                    C.c_double(voxel_size), _ptr(out_xyz), _ptr(out_nrm), C.byref(m)),
+                      "voxel_down_sample")
         out = PointCloud()
         out._xyz = out_xyz[: m.value].contiguous()
         if has_n:
             out._nrm = out_nrm[: m.value].contiguous()
+        if out_col is not None:
+            out._col = out_col[: m.value].contiguous()
         return out
 
     def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
@@ -195,6 +230,8 @@ class PointCloud:
             out._nrm = self._nrm[idx].contiguous()
         if self.has_covariances():
             out._cov = self._cov[idx].contiguous()
+        if self.has_colors():
+            out._col = self._col[idx].contiguous()
         return out
 
     def random_down_sample(self, sampling_ratio: float, seed=None) -> "PointCloud":
@@ -235,7 +272,7 @@ class PointCloud:
         self._cov = out[:n].contiguous()
 
     def transform(self, T):
-        """In place, like Open3D (points, normals; covariances rotated)."""
+        """In place, like Open3D (points, normals; covariances rotated; colours untouched)."""
         torch = _torch()
         T = np.asarray(T, dtype=np.float64).reshape(4, 4)
         R = torch.as_tensor(T[:3, :3], dtype=torch.float64, device="cuda")

@@ -88,6 +88,84 @@ def read_pcd_xyz(path: str) -> np.ndarray:
     return np.ascontiguousarray(xyz[ok])
 
 
+def _read_pcd_records(path: str) -> np.ndarray:
+    """The records of a PCD file (``DATA binary`` or ``DATA ascii``) as a structured array, one field per ``FIELDS`` entry."""
+    with open(path, "rb") as f:
+        header = {}
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PCD header")
+            s = line.decode("ascii", "replace").strip()
+            if not s or s.startswith("#"):
+                continue
+            key, _, rest = s.partition(" ")
+            header[key.upper()] = rest.split()
+            if key.upper() == "DATA":
+                break
+        fields = header["FIELDS"]
+        sizes = [int(v) for v in header["SIZE"]]
+        types = header["TYPE"]
+        counts = [int(v) for v in header.get("COUNT", ["1"] * len(fields))]
+        npts = int(header["POINTS"][0]) if "POINTS" in header else int(header["WIDTH"][0]) * int(header["HEIGHT"][0])
+        kind = header["DATA"][0].lower()
+        dt = np.dtype([(name, _PCD_TYPES[(ty, sz)]) if cnt == 1 else (name, _PCD_TYPES[(ty, sz)], (cnt,))
+                       for name, sz, ty, cnt in zip(fields, sizes, types, counts)])
+        if kind == "binary":
+            raw = f.read(npts * dt.itemsize)
+            if len(raw) < npts * dt.itemsize:
+                raise ValueError(f"{path}: expected {npts} points, file is short")
+            return np.frombuffer(raw, dtype=dt, count=npts)
+        if kind != "ascii":
+            raise ValueError(f"{path}: unsupported PCD DATA kind {kind!r}")
+        arr = np.loadtxt(f, dtype=np.float64, ndmin=2)
+        rec = np.zeros(arr.shape[0], dtype=dt)
+        col = 0
+        for name, cnt in zip(fields, counts):
+            rec[name] = arr[:, col] if cnt == 1 else arr[:, col:col + cnt]
+            col += cnt
+        return rec
+
+
+def read_pcd(path: str):
+    """``(xyz, colors)`` of a PCD file: the points as ``read_pcd_xyz`` returns them and, when the file has PCL's packed ``rgb`` / ``rgba``
+    field (typed ``F 4`` or ``U 4``: the float's bit pattern is taken as a uint32, r = bits 16-23, g = 8-15, b = 0-7), the colours as an
+    (N, 3) float32 array in [0, 1], else ``None``.  Non-finite points are dropped from both arrays."""
+    rec = _read_pcd_records(path)
+    xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32)
+    ok = np.isfinite(xyz).all(axis=1)
+    colors = None
+    name = next((f for f in ("rgb", "rgba") if f in (rec.dtype.names or ())), None)
+    if name is not None:
+        field = np.ascontiguousarray(rec[name])
+        if field.dtype.itemsize != 4 or field.ndim != 1:
+            raise ValueError(f"{path}: the {name} field must be one 4-byte value per point")
+        bits = field.view(np.uint32) if field.dtype.kind == "f" else field.astype(np.uint32)
+        colors = np.stack([(bits >> 16) & 255, (bits >> 8) & 255, bits & 255], axis=1).astype(np.float32) / np.float32(255.0)
+        colors = np.ascontiguousarray(colors[ok])
+    return np.ascontiguousarray(xyz[ok]), colors
+
+
+def write_pcd(path: str, xyz: np.ndarray, colors=None) -> None:
+    """Write points and, when given, (N, 3) colours in [0, 1] as the binary ``x y z rgb`` layout the reference ships (``rgb`` typed ``F 4``:
+    the packed 0x00RRGGBB word stored under a float's name); without colours the file is ``write_pcd_xyz``'s."""
+    if colors is None:
+        return write_pcd_xyz(path, xyz)
+    xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
+    c8 = np.clip(np.rint(np.asarray(colors, dtype=np.float64).reshape(-1, 3) * 255.0), 0, 255).astype(np.uint32)
+    if c8.shape[0] != xyz.shape[0]:
+        raise ValueError("write_pcd: one colour per point is required")
+    n = xyz.shape[0]
+    rec = np.empty(n, dtype=[("xyz", "<f4", (3,)), ("rgb", "<u4")])
+    rec["xyz"] = xyz
+    rec["rgb"] = (c8[:, 0] << 16) | (c8[:, 1] << 8) | c8[:, 2]
+    hdr = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\n"
+           f"COUNT 1 1 1 1\nWIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(rec.tobytes())
+
+
 def write_pcd_xyz(path: str, xyz: np.ndarray) -> None:
     """Write an (N,3) array as the same binary PCD v0.7 layout the reference ships."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)

@@ -10,7 +10,11 @@ from . import registration as _r
 
 
 def _read_point_cloud(path):
-    return _g.PointCloud(_io.read_pcd_xyz(path))
+    xyz, colors = _io.read_pcd(path)
+    pc = _g.PointCloud(xyz)
+    if colors is not None:
+        pc.colors = colors
+    return pc
 
 
 geometry = SimpleNamespace(PointCloud=_g.PointCloud, KDTreeSearchParamKNN=_g.KDTreeSearchParamKNN,

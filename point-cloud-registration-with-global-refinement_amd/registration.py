@@ -57,6 +57,17 @@ class TransformationEstimationPointToPlane:
         self.kernel = kernel if kernel is not None else L2Loss()
 
 
+class TransformationEstimationForColoredICP:
+    """Colored ICP (Park, Zhou, Koltun, ICCV 2017): a point-to-plane term weighted ``lambda_geometric`` and a photometric term over the
+    target's colour gradients weighted ``1 - lambda_geometric``, both robustly weighted by ``kernel``.  As in Open3D a ``lambda_geometric``
+    outside [0, 1] is reset to 0.968."""
+
+    def __init__(self, lambda_geometric: float = 0.968, kernel: RobustKernel | None = None):
+        lam = float(lambda_geometric)
+        self.lambda_geometric = lam if 0.0 <= lam <= 1.0 else 0.968
+        self.kernel = kernel if kernel is not None else L2Loss()
+
+
 class ICPConvergenceCriteria:
     def __init__(self, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_iteration: int = 30):
         self.relative_fitness = float(relative_fitness)
@@ -184,6 +195,8 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
     ``pcr_registration_icp``, the same device loop with their own update."""
     if isinstance(estimation_method, TransformationEstimationForGeneralizedICP):
         return registration_generalized_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)
+    if isinstance(estimation_method, TransformationEstimationForColoredICP):
+        return registration_colored_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)
     estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
     if isinstance(estimation, TransformationEstimationPointToPoint):
         p = _lib.PcrIcpParams(_lib.ICP_POINT_TO_POINT, int(estimation.with_scaling), _lib.LOSS_L2, 1.0, 0.0, 0.0, 0)
@@ -208,6 +221,52 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
         ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), _ptr(target.device_normals() if target.has_normals() else None),
         C.c_int64(nt), C.c_double(max_correspondence_distance), Tp, C.byref(p), C.byref(res), _ptr(corr)), "registration_icp")
     return _result(res, corr)
+
+
+def registration_colored_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None, criteria=None):
+    """Open3D ``registration_colored_icp`` (``pcr_registration_colored_icp``, include/pcr_hip.h): the target's colour gradients over
+    ``KDTreeSearchParamHybrid(2 * max_correspondence_distance, 30)``, then the loop of ``registration_icp`` with the two-row update of
+    ``TransformationEstimationForColoredICP``.  ``fitness`` and ``inlier_rmse`` are the geometric ones of the correspondence search."""
+    estimation = TransformationEstimationForColoredICP() if estimation_method is None else estimation_method
+    if not isinstance(estimation, TransformationEstimationForColoredICP):
+        raise RuntimeError(f"registration_colored_icp: {type(estimation).__name__} is not TransformationEstimationForColoredICP")
+    criteria = criteria or ICPConvergenceCriteria()
+    if max_correspondence_distance <= 0:
+        raise RuntimeError("Invalid max_correspondence_distance.")
+    ns, nt = len(source), len(target)
+    if nt and not target.has_normals():
+        raise RuntimeError("ColoredICP requires pre-computed normal vectors for target PointCloud.")
+    if ns and not source.has_colors():
+        raise RuntimeError("ColoredICP requires pre-computed colors for source PointCloud.")
+    if nt and not target.has_colors():
+        raise RuntimeError("ColoredICP requires pre-computed colors for target PointCloud.")
+    p = _lib.PcrColoredIcpParams(float(estimation.lambda_geometric), int(estimation.kernel.kind), float(estimation.kernel.k),
+                                 float(criteria.relative_fitness), float(criteria.relative_rmse), int(criteria.max_iteration))
+    ctx = _lib.Context.current()
+    torch = _torch()
+    corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+    res = _lib.PcrResult()
+    T, Tp = _T(init)
+    ctx.check(ctx.lib.pcr_registration_colored_icp(
+        ctx.handle, _ptr(source.device_xyz()), _ptr(source.device_colors() if ns else None), C.c_int64(ns), _ptr(target.device_xyz()),
+        _ptr(target.device_normals() if nt else None), _ptr(target.device_colors() if nt else None), C.c_int64(nt),
+        C.c_double(max_correspondence_distance), Tp, C.byref(p), C.byref(res), _ptr(corr)), "registration_colored_icp")
+    return _result(res, corr)
+
+
+def color_gradient(cloud: PointCloud, search_param) -> np.ndarray:
+    """The colour gradients colored ICP takes of a target cloud (``pcr_color_gradient``): (N, 3) float32, one row per point, over the
+    neighbours of ``search_param`` (KNN or Hybrid, at most 32 neighbours).  The cloud needs normals and colours."""
+    if not cloud.has_normals() or not cloud.has_colors():
+        raise RuntimeError("color_gradient: the cloud needs normals and colors")
+    ctx = _lib.Context.current()
+    torch = _torch()
+    kind, knn, radius = search_param._spec()
+    n = len(cloud)
+    out = torch.zeros((max(n, 1), 3), dtype=torch.float32, device="cuda")
+    ctx.check(ctx.lib.pcr_color_gradient(ctx.handle, _ptr(cloud.device_xyz()), _ptr(cloud.device_normals()), _ptr(cloud.device_colors()), C.c_int64(n),
+                                         C.c_int(kind), C.c_int(knn), C.c_double(radius), _ptr(out)), "color_gradient")
+    return out[:n].cpu().numpy()
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
