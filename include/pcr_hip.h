@@ -148,6 +148,37 @@ int pcr_estimate_normals(pcr_context *ctx, const float *xyz, int64_t n, int sear
 int pcr_estimate_covariances(pcr_context *ctx, const float *xyz, int64_t n, int search_kind, int knn, double radius,
                              float *cov6);
 
+/* == PointCloud.compute_nearest_neighbor_distance (plot_cloud_knn_distances, ALL_FUNCTIONS.py:1077-1078).  dist: n float64 (device), caller order.
+ * dist[i] = the square root of the SECOND smallest squared distance from point i to the points of the same cloud, point i itself included
+ * (the second entry of Open3D's SearchKNN(p, 2)): a duplicated point gets 0, and with n < 2 every entry is 0.  The neighbour is selected by
+ * float32 d^2 like the other exact searches; the distance is then recomputed in float64 from the float32 coordinates of the point and the chosen
+ * neighbour -- differences, squares and sums in the order x, y, z, each rounded once -- and square-rooted in float64: exact for that neighbour,
+ * which is a true second nearest up to a float32 tie.  Asynchronous on the context's stream. */
+int pcr_nearest_neighbor_distance(pcr_context *ctx, const float *xyz, int64_t n, double *dist);
+
+/* == PointCloud.compute_point_cloud_distance(target) (Open3D ComputePointCloudDistance; the reference judges pairs with the capped
+ * evaluate_registration only).  dist: n_src float64 (device); dist[i] = distance from source point i to its nearest target point, the search
+ * unbounded; nearest (optional, n_src int32, device) = that target point's caller index.  Selection and precision as for
+ * pcr_nearest_neighbor_distance.  Among target points at the SAME float32 d^2 the one that comes first in the library's Morton order of the
+ * target is returned, which need not be the one with the lowest caller index (in both calls; the distance is that of the point returned).
+ * An empty target gives dist = 0 and nearest = -1; an empty source writes nothing.  Asynchronous. */
+int pcr_point_cloud_distance(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt,
+                             double *dist, int32_t *nearest);
+
+/* == PointCloud.remove_radius_outlier(nb_points, radius) (Open3D RemoveRadiusOutliers, the sibling of the filter at ALL_FUNCTIONS.py:297-298).
+ * nb_points < 1 or radius <= 0: PCR_EINVAL.  Point i is kept iff the number of points of the cloud with d^2 < radius^2 -- point i included, the
+ * test strict -- is GREATER than nb_points; d^2 in float64 on the float32 coordinates (the rule of the radius neighbourhoods of
+ * pcr_estimate_normals).  The count may stop once it has passed nb_points.  keep_mask: n bytes (device, optional), out_xyz optional compacted
+ * cloud (capacity n), out_index optional int64 indices (device), ascending: the layout of pcr_remove_statistical_outlier. */
+int pcr_remove_radius_outlier(pcr_context *ctx, const float *xyz, int64_t n, int nb_points, double radius,
+                              uint8_t *keep_mask, float *out_xyz, int64_t *out_index, int64_t *out_n);
+
+/* == PointCloud.compute_mean_and_covariance / get_center (extract_eigen_features, ALL_FUNCTIONS.py:1035, :1043; colorir_voxels :1022).
+ * mean3, cov9 (row-major 3x3) host, float64: the mean and the POPULATION covariance (divided by n) of the float32 points; n == 0 gives a zero
+ * mean and the identity.  Float64 sums in a fixed order (same bits on every run), the second moments taken about the mean.  cov9 may be
+ * NULL (get_center): the mean alone, the same bits, in one pass over the points instead of two. */
+int pcr_mean_and_covariance(pcr_context *ctx, const float *xyz, int64_t n, double *mean3, double *cov9);
+
 /* ---- registration ------------------------------------------------------------------ */
 /* == registration_generalized_icp (ALL_FUNCTIONS.py:304-311; 2_MGICP...py:155-162).
  * correspondences optional device int32 [n_src x 2]; filled with n_correspondences rows.       */

@@ -99,7 +99,17 @@ EXPORTS = [
     "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists",
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
+    "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
 ]
+
+# prototypes of the cloud queries (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+QUERY_PROTOTYPES = {
+    "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_remove_radius_outlier": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_int64)], C.c_int),
+    "pcr_mean_and_covariance": ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+}
 
 _lib = None
 _lock = threading.Lock()
@@ -137,6 +147,11 @@ def load():
             lib.pcr_set_stream.argtypes = [C.c_void_p, C.c_void_p]
             if hasattr(lib, "pcr_set_option"):       # (absent only from older diagnostic builds loaded through PCR_HIP_SO)
                 lib.pcr_set_option.argtypes = [C.c_char_p, C.c_longlong]
+            for name, (argtypes, restype) in QUERY_PROTOTYPES.items():
+                if not hasattr(lib, name):
+                    raise RuntimeError(f"{SO_PATH} does not export {name}: it was built from older sources (rebuild it; see include/pcr_hip.h)")
+                fn = getattr(lib, name)
+                fn.argtypes, fn.restype = argtypes, restype
             _lib = lib
     return _lib
 

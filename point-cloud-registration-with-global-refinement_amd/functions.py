@@ -101,6 +101,36 @@ def calculate_RMSE_and_fitness(lista_nuvens, T_circuito, distancia):
     return [r.inlier_rmse for r in results], [r.fitness for r in results]
 
 
+def extract_eigen_features(pc):
+    """ALL_FUNCTIONS.py:1033-1058 -> the 7-vector (lin, pla, esf, cur, ani, omn, eig_sum) of eigenvalue features of a cloud.  The points are
+    centred on ``get_center()`` and scaled by the larger norm of their per-axis maxima and minima; the singular values of the covariance of
+    THAT cloud (``compute_mean_and_covariance``) give eig_sum as they are and the six ratios after division by their norm -- ``ani`` as the
+    reference has it, s0 - s2 / s0, not (s0 - s2) / s0.  The scaled cloud is a stand-in cloud too, so its points are float32 (the reference
+    keeps float64 there): the features agree with the reference to float32 rounding of the points."""
+    offsets = np.asarray(pc.points) - pc.get_center()
+    extent = max(np.linalg.norm(offsets.max(axis=0)), np.linalg.norm(offsets.min(axis=0)))
+    _, cov = _g.PointCloud(offsets / extent).compute_mean_and_covariance()
+    sv = np.linalg.svd(cov, compute_uv=False)
+    s0, s1, s2 = sv / np.linalg.norm(sv)
+    return np.array([(s0 - s1) / s0,                  # lin
+                     (s1 - s2) / s0,                  # pla
+                     s2 / s0,                         # esf
+                     s2 / (s0 + s1 + s2),             # cur
+                     s0 - s2 / s0,                    # ani
+                     (s0 * s1 * s2) ** (1 / 3),       # omn
+                     sv[0] + sv[1] + sv[2]])          # eig_sum, of the singular values before they are normalised
+
+
+KNN_DISTANCE_LABELS = ("Voxel downsampling", "Hybrid downsampling")      # ALL_FUNCTIONS.py:1080, :1082
+
+
+def knn_distance_table(pc1, pc2):
+    """The data half of ``plot_cloud_knn_distances`` (ALL_FUNCTIONS.py:1076-1084): the nearest-neighbour distances of the two clouds
+    with the class label the reference gives each, as ``[(distances1, label1), (distances2, label2)]`` -- the two columns of its data
+    frame per cloud.  The box plot itself (pandas, seaborn) is not part of this package."""
+    return [(pc.compute_nearest_neighbor_distance(), label) for pc, label in zip((pc1, pc2), KNN_DISTANCE_LABELS)]
+
+
 # ------------------------------------------------------------------------------------ script variants
 class script1:
     """Private copies in 1_FGR_pairwise_registration_in_NCLT_dataset.py."""

@@ -3,8 +3,10 @@
 
 Reference call sites: ``voxel_down_sample`` ALL_FUNCTIONS.py:293-294, ``remove_statistical_outlier``
 :297-298, ``estimate_normals`` :182-183/:214-215/:301-302, ``estimate_covariances`` :216-217,
-``get_min_bound/get_max_bound`` :1093-1097, ``transform`` :46, ``copy.deepcopy`` :289-290.
-Every method dispatches to ``libpcr_hip.so``; nothing here computes on the CPU.
+``get_min_bound/get_max_bound`` :1093-1097, ``transform`` :46, ``copy.deepcopy`` :289-290,
+``compute_nearest_neighbor_distance`` :1077-1078, ``get_center`` :1022/:1035, ``compute_mean_and_covariance`` :1043.
+Every method that computes dispatches to ``libpcr_hip.so``; the host only builds index lists (``uniform_down_sample``, the ``invert`` form
+of ``select_by_index``) and moves rows with torch on the device.
 """
 from __future__ import annotations
 
@@ -215,6 +217,70 @@ class PointCloud:
                   "remove_statistical_outlier")
         index = idx[: m.value]
         return self.select_by_index(index), index.cpu().numpy().tolist()
+
+    def remove_radius_outlier(self, nb_points: int, radius: float):
+        """``PointCloud.remove_radius_outlier``: keeps the points with MORE than ``nb_points`` points of the cloud (themselves included)
+        strictly inside ``radius``; returns ``(PointCloud, list_of_indices)`` like the statistical filter, indices ascending."""
+        if nb_points < 1 or not (radius > 0.0):
+            raise RuntimeError("Illegal input parameters, number of points and radius must be positive")
+        ctx = _lib.Context.current()
+        torch = _torch()
+        n = len(self)
+        keep = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        idx = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        m = C.c_int64(0)
+        ctx.check(ctx.lib.pcr_remove_radius_outlier(ctx.handle, _ptr(self.device_xyz()), C.c_int64(n), C.c_int(int(nb_points)), C.c_double(radius),
+                                                    _ptr(keep), None, _ptr(idx), C.byref(m)), "remove_radius_outlier")
+        index = idx[: m.value]
+        return self.select_by_index(index), index.cpu().numpy().tolist()
+
+    def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
+        """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
+        if every_k_points < 1:
+            raise RuntimeError("Illegal sample rate, every_k_points must be a positive integer")
+        return self.select_by_index(_torch().arange(0, len(self), int(every_k_points), dtype=_torch().int64, device="cuda"))
+
+    def compute_nearest_neighbor_distance(self):
+        """``PointCloud.compute_nearest_neighbor_distance`` (ALL_FUNCTIONS.py:1077-1078): per point the distance to its nearest OTHER
+        point -- the second entry of a 2-NN search that finds the point itself first, so a duplicated point gets 0 --, float64, length n;
+        all 0 with fewer than two points."""
+        ctx = _lib.Context.current()
+        torch = _torch()
+        n = len(self)
+        out = torch.zeros(max(n, 1), dtype=torch.float64, device="cuda")
+        ctx.check(ctx.lib.pcr_nearest_neighbor_distance(ctx.handle, _ptr(self.device_xyz()), C.c_int64(n), _ptr(out)), "compute_nearest_neighbor_distance")
+        return out[:n].cpu().numpy()
+
+    def compute_point_cloud_distance(self, target: "PointCloud"):
+        """``PointCloud.compute_point_cloud_distance``: per point of this cloud the distance to the nearest point of ``target`` (no
+        distance cap, unlike ``evaluate_registration``), float64, length n; all 0 against an empty target."""
+        return self._point_cloud_distance(target)[0]
+
+    def _point_cloud_distance(self, target: "PointCloud"):
+        """-> (distances float64 (n,), nearest target index int32 (n,), -1 against an empty target)."""
+        ctx = _lib.Context.current()
+        torch = _torch()
+        n = len(self)
+        dist = torch.zeros(max(n, 1), dtype=torch.float64, device="cuda")
+        near = torch.full((max(n, 1),), -1, dtype=torch.int32, device="cuda")
+        ctx.check(ctx.lib.pcr_point_cloud_distance(ctx.handle, _ptr(self.device_xyz()), C.c_int64(n), _ptr(target.device_xyz()), C.c_int64(len(target)),
+                                                   _ptr(dist), _ptr(near)), "compute_point_cloud_distance")
+        return dist[:n].cpu().numpy(), near[:n].cpu().numpy()
+
+    def compute_mean_and_covariance(self):
+        """``PointCloud.compute_mean_and_covariance`` (ALL_FUNCTIONS.py:1043): ``(mean (3,), covariance (3, 3))`` in float64, the
+        covariance divided by n; an empty cloud gives a zero mean and the identity."""
+        ctx = _lib.Context.current()
+        mean, cov = (C.c_double * 3)(), (C.c_double * 9)()
+        ctx.check(ctx.lib.pcr_mean_and_covariance(ctx.handle, _ptr(self.device_xyz()), C.c_int64(len(self)), mean, cov), "compute_mean_and_covariance")
+        return np.array(mean, dtype=np.float64), np.array(cov, dtype=np.float64).reshape(3, 3)
+
+    def get_center(self):
+        """``PointCloud.get_center`` (ALL_FUNCTIONS.py:1022, :1035): the mean of the points, float64 (3,)."""
+        ctx = _lib.Context.current()
+        mean = (C.c_double * 3)()                 # no covariance asked for: one pass over the points
+        ctx.check(ctx.lib.pcr_mean_and_covariance(ctx.handle, _ptr(self.device_xyz()), C.c_int64(len(self)), mean, None), "get_center")
+        return np.array(mean, dtype=np.float64)
 
     def select_by_index(self, indices, invert: bool = False) -> "PointCloud":
         torch = _torch()
