@@ -14,80 +14,39 @@
 #define BS 256
 
 // ================================================================================== bounds
-__global__ void __launch_bounds__(BS) k_bounds_partial(const float *__restrict__ xyz, int64_t n, float *__restrict__ part) {
-    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-    for (int64_t i = blockIdx.x * (int64_t)BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
-        mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-        mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-    }
-    __shared__ float s[BS / PCR_WAVE][6];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 0; d < 3; d++) { mn[d] = pcr_wave_min(mn[d]); mx[d] = pcr_wave_max(mx[d]); }
-    if (lane == 0) { for (int d = 0; d < 3; d++) { s[w][d] = mn[d]; s[w][3 + d] = mx[d]; } }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = s[0][threadIdx.x];
-        for (int k = 1; k < BS / PCR_WAVE; k++) v = threadIdx.x < 3 ? fminf(v, s[k][threadIdx.x]) : fmaxf(v, s[k][threadIdx.x]);
-        part[blockIdx.x * 6 + threadIdx.x] = v;
-    }
-}
-__global__ void k_bounds_final(const float *__restrict__ part, int nb, float *__restrict__ out6) {
-    if (threadIdx.x < 6) {
-        float v = part[threadIdx.x];
-        for (int k = 1; k < nb; k++) v = threadIdx.x < 3 ? fminf(v, part[k * 6 + threadIdx.x]) : fmaxf(v, part[k * 6 + threadIdx.x]);
-        out6[threadIdx.x] = v;
-    }
-}
-
-int pcr_dev_bounds(pcr_context *ctx, const float *xyz, int64_t n, double *b6) {
-    if (n <= 0) { for (int i = 0; i < 6; i++) b6[i] = 0; return PCR_OK; }
-    ArenaMark mark(ctx);
-    const int nb = (int)((n + BS - 1) / BS < 256 ? (n + BS - 1) / BS : 256);
-    float *part = arena<float>(ctx, (size_t)nb * 6 + 6);
-    if (!part) return PCR_ENOMEM;
-    float *out6 = part + (size_t)nb * 6;
-    PCR_LAUNCH(ctx, k_bounds_partial, dim3(nb), dim3(BS), 0, ctx->stream, xyz, n, part);
-    PCR_LAUNCH(ctx, k_bounds_final, dim3(1), dim3(64), 0, ctx->stream, part, nb, out6);
-    float h[6];
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(h, out6, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 6; i++) b6[i] = (double)h[i];
-    return PCR_OK;
-}
-
 // bounds of `count` clouds: two launches (blockIdx.y = cloud), one copy, one synchronisation
 struct BoundsArgs { const float *xyz; int64_t n; float *part; float *out6; int nb; };
-__global__ void __launch_bounds__(BS) k_bounds_partial_g(const BoundsArgs *a_) {
-    const BoundsArgs &a = a_[blockIdx.y];
-    if ((int)blockIdx.x >= a.nb) return;
-    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-    for (int64_t i = blockIdx.x * (int64_t)BS + threadIdx.x; i < a.n; i += (int64_t)a.nb * BS) {
-        float x = a.xyz[i * 3], y = a.xyz[i * 3 + 1], z = a.xyz[i * 3 + 2];
-        mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-        mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-    }
-    __shared__ float s[BS / PCR_WAVE][6];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+struct OpBoundsPartial : PcrOp<BoundsArgs, BS> {
+    __device__ static inline void run(const BoundsArgs &a) {
+        if ((int)blockIdx.x >= a.nb) return;
+        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+        for (int64_t i = blockIdx.x * (int64_t)BS + threadIdx.x; i < a.n; i += (int64_t)a.nb * BS) {
+            float x = a.xyz[i * 3], y = a.xyz[i * 3 + 1], z = a.xyz[i * 3 + 2];
+            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
+            mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
+        }
+        __shared__ float s[BS / PCR_WAVE][6];
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int d = 0; d < 3; d++) { mn[d] = pcr_wave_min(mn[d]); mx[d] = pcr_wave_max(mx[d]); }
-    if (lane == 0) { for (int d = 0; d < 3; d++) { s[w][d] = mn[d]; s[w][3 + d] = mx[d]; } }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = s[0][threadIdx.x];
-        for (int k = 1; k < BS / PCR_WAVE; k++) v = threadIdx.x < 3 ? fminf(v, s[k][threadIdx.x]) : fmaxf(v, s[k][threadIdx.x]);
-        a.part[blockIdx.x * 6 + threadIdx.x] = v;
+        for (int d = 0; d < 3; d++) { mn[d] = pcr_wave_min(mn[d]); mx[d] = pcr_wave_max(mx[d]); }
+        if (lane == 0) { for (int d = 0; d < 3; d++) { s[w][d] = mn[d]; s[w][3 + d] = mx[d]; } }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            float v = s[0][threadIdx.x];
+            for (int k = 1; k < BS / PCR_WAVE; k++) v = threadIdx.x < 3 ? fminf(v, s[k][threadIdx.x]) : fmaxf(v, s[k][threadIdx.x]);
+            a.part[blockIdx.x * 6 + threadIdx.x] = v;
+        }
     }
-}
-__global__ void k_bounds_final_g(const BoundsArgs *a_) {
-    const BoundsArgs &a = a_[blockIdx.x];
-    if (threadIdx.x < 6) {
-        float v = a.part[threadIdx.x];
-        for (int k = 1; k < a.nb; k++) v = threadIdx.x < 3 ? fminf(v, a.part[k * 6 + threadIdx.x]) : fmaxf(v, a.part[k * 6 + threadIdx.x]);
-        a.out6[threadIdx.x] = v;
+};
+struct OpBoundsFinal : PcrOp<BoundsArgs, 64> {
+    __device__ static inline void run(const BoundsArgs &a) {
+        if (threadIdx.x < 6) {
+            float v = a.part[threadIdx.x];
+            for (int k = 1; k < a.nb; k++) v = threadIdx.x < 3 ? fminf(v, a.part[k * 6 + threadIdx.x]) : fmaxf(v, a.part[k * 6 + threadIdx.x]);
+            a.out6[threadIdx.x] = v;
+        }
     }
-}
+};
 int pcr_dev_bounds_batch(pcr_context *ctx, int count, const float *const *xyz, const int64_t *n, double *b6 /* count x 6, host */) {
     if (count < 1) return PCR_OK;
     ArenaMark mark(ctx);
@@ -102,15 +61,17 @@ int pcr_dev_bounds_batch(pcr_context *ctx, int count, const float *const *xyz, c
         if (!a[c].part) return PCR_ENOMEM;
         max_nb = nb > max_nb ? nb : max_nb;
     }
-    const BoundsArgs *d = pcr_desc_upload(ctx, a.data(), count);
-    if (!d) return PCR_ENOMEM;
-    PCR_LAUNCH(ctx, k_bounds_partial_g, dim3(max_nb, count), dim3(BS), 0, ctx->stream, d);
-    PCR_LAUNCH(ctx, k_bounds_final_g, dim3(count), dim3(64), 0, ctx->stream, d);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpBoundsPartial, a.data(), count, dim3(max_nb, count)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpBoundsFinal, a.data(), count, dim3(1, count)));
     std::vector<float> h((size_t)count * 6);
     PCR_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), out, sizeof(float) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < h.size(); i++) b6[i] = (double)h[i];
     return PCR_OK;
+}
+int pcr_dev_bounds(pcr_context *ctx, const float *xyz, int64_t n, double *b6) {
+    if (n <= 0) { for (int i = 0; i < 6; i++) b6[i] = 0; return PCR_OK; }
+    return pcr_dev_bounds_batch(ctx, 1, &xyz, &n, b6);
 }
 
 int pcr_read_count(pcr_context *ctx, const int *dev_n, int64_t *out) {
@@ -145,12 +106,7 @@ __device__ static inline int block_exclusive_scan(int v, int *total) {   // BS t
 // Optional flag producers fused into the counting pass (each saved a launch of its own): head flags of sorted keys
 // (voxel grid), or the SOR keep test on the mean neighbour distances.  The flags are stored for the later kernels.
 struct FlagSrc { const uint64_t *keys; const double *avg; const double *stats3; };
-#define PCR_MAX_BATCH 8          // problems whose argument structs travel in the kernel arguments (blockIdx.y picks the problem): the scales of
-                                 //   a multiscale registration.  Larger batches (the clouds and scales of a GROUP of pairs) read their argument structs
-                                 //   from device memory: every batched kernel has a by-value and a by-pointer entry point (pcr_batch_launch)
-#define PCR_MAX_GROUP_BATCH 256
 struct ScanArgs { uint8_t *flags; const int *n_ptr; int n_host; int *tile_cnt; int *pos; int *total; FlagSrc src; int n_tiles; };
-struct ScanBatch { ScanArgs a[PCR_MAX_BATCH]; };
 __device__ static inline void d_scan_tile_count(const ScanArgs &a) {
     if ((int)blockIdx.x >= a.n_tiles) return;
     const int n = a.n_ptr ? *a.n_ptr : a.n_host;
@@ -194,29 +150,8 @@ __device__ static inline void d_scan_tile_apply(const ScanArgs &a) {
     for (int j = 0; j < 4; j++) { if (base + j < n) a.pos[base + j] = ex; ex += f[j]; }
     if ((int)blockIdx.x == a.n_tiles - 1 && threadIdx.x == 0) *a.total = offset + tot;
 }
-__global__ void __launch_bounds__(BS) k_scan_tile_count(ScanArgs a) { d_scan_tile_count(a); }
-__global__ void __launch_bounds__(BS) k_scan_tile_apply(ScanArgs a) { d_scan_tile_apply(a); }
-__global__ void __launch_bounds__(BS) k_scan_tile_count_batch(ScanBatch b) { d_scan_tile_count(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_scan_tile_apply_batch(ScanBatch b) { d_scan_tile_apply(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_scan_tile_count_batchp(const ScanArgs *a) { d_scan_tile_count(a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_scan_tile_apply_batchp(const ScanArgs *a) { d_scan_tile_apply(a[blockIdx.y]); }
-
-// `count` problems in one launch: argument structs by value up to PCR_MAX_BATCH, else through the context's descriptor buffer
-// (pinned staging -> device, one small asynchronous copy on the launch stream)
-template <class B, class A, class KV, class KP>
-static int pcr_batch_launch(pcr_context *ctx, const char *file, int line, KV by_value, KP by_pointer, const A *args, int count, dim3 grid, dim3 block) {
-    if (count <= PCR_MAX_BATCH) {
-        B b; std::memset(&b, 0, sizeof b);
-        for (int k = 0; k < count; k++) b.a[k] = args[k];
-        pcr_launch(ctx, file, line, by_value, grid, block, 0, ctx->stream, b);
-    } else {
-        const A *dev = pcr_desc_upload(ctx, args, count);
-        if (!dev) return PCR_ENOMEM;
-        pcr_launch(ctx, file, line, by_pointer, grid, block, 0, ctx->stream, dev);
-    }
-    return PCR_OK;
-}
-#define PCR_BATCH_LAUNCH(ctx, B, kv, kp, args, count, grid, block) pcr_batch_launch<B>(ctx, __FILE__, __LINE__, kv, kp, args, count, grid, block)
+struct OpScanCount : PcrOp<ScanArgs, BS> { __device__ static inline void run(const ScanArgs &a) { d_scan_tile_count(a); } };
+struct OpScanApply : PcrOp<ScanArgs, BS> { __device__ static inline void run(const ScanArgs &a) { d_scan_tile_apply(a); } };
 
 static int scan_args(pcr_context *ctx, ScanArgs *a, uint8_t *flags, const int *n_ptr, int n_cap, int *pos, int *total_dev, FlagSrc src) {
     a->n_tiles = (n_cap + TILE - 1) / TILE;
@@ -225,23 +160,18 @@ static int scan_args(pcr_context *ctx, ScanArgs *a, uint8_t *flags, const int *n
     a->flags = flags; a->n_ptr = n_ptr; a->n_host = n_cap; a->pos = pos; a->total = total_dev; a->src = src;
     return PCR_OK;
 }
-static int flag_scan(pcr_context *ctx, uint8_t *flags, const int *n_ptr, int n_cap, int *pos, int *total_dev, FlagSrc src) {
-    ScanArgs a;
-    PCR_TRY(scan_args(ctx, &a, flags, n_ptr, n_cap, pos, total_dev, src));
-    PCR_LAUNCH(ctx, k_scan_tile_count, dim3(a.n_tiles), dim3(BS), 0, ctx->stream, a);
-    PCR_LAUNCH(ctx, k_scan_tile_apply, dim3(a.n_tiles), dim3(BS), 0, ctx->stream, a);
-    return PCR_OK;
-}
 static int flag_scan_batch(pcr_context *ctx, const ScanArgs *a, int count) {
     int mt = 0;
     for (int k = 0; k < count; k++) mt = a[k].n_tiles > mt ? a[k].n_tiles : mt;
     if (mt == 0) return PCR_OK;
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, ScanBatch, k_scan_tile_count_batch, k_scan_tile_count_batchp, a, count, dim3(mt, count), dim3(BS)));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, ScanBatch, k_scan_tile_apply_batch, k_scan_tile_apply_batchp, a, count, dim3(mt, count), dim3(BS)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpScanCount, a, count, dim3(mt, count)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpScanApply, a, count, dim3(mt, count)));
     return PCR_OK;
 }
 int pcr_dev_flag_scan(pcr_context *ctx, const uint8_t *flags, const int *n_ptr, int n_cap, int *pos, int *total_dev) {
-    return flag_scan(ctx, const_cast<uint8_t *>(flags), n_ptr, n_cap, pos, total_dev, FlagSrc{nullptr, nullptr, nullptr});
+    ScanArgs a;
+    PCR_TRY(scan_args(ctx, &a, const_cast<uint8_t *>(flags), n_ptr, n_cap, pos, total_dev, FlagSrc{nullptr, nullptr, nullptr}));
+    return flag_scan_batch(ctx, &a, 1);
 }
 
 // ================================================================================== voxel (K1)
@@ -306,7 +236,9 @@ int pcr_dev_voxel(pcr_context *ctx, const float *xyz, const float *nrm_in, int64
     const int nb = (ni + BS - 1) / BS;
     PCR_LAUNCH(ctx, k_voxel_keys, dim3(nb), dim3(BS), 0, ctx->stream, xyz, ni, ox, oy, oz, voxel, k0, v0);
     PCR_TRY(pcr_sort_pairs(ctx, temp, tb, k0, k1, v0, v1, n, end_bit));
-    PCR_TRY(flag_scan(ctx, flags, nullptr, ni, pos, out->n, FlagSrc{k1, nullptr, nullptr}));      // head flags produced inside the scan
+    ScanArgs sa;
+    PCR_TRY(scan_args(ctx, &sa, flags, nullptr, ni, pos, out->n, FlagSrc{k1, nullptr, nullptr}));      // head flags produced inside the scan
+    PCR_TRY(flag_scan_batch(ctx, &sa, 1));
     PCR_LAUNCH(ctx, k_voxel_mean, dim3(nb), dim3(BS), 0, ctx->stream, xyz, nrm_in, k1, v1, flags, pos, ni, out->pts, out->nrm, out->keys);
     return PCR_OK;
 }
@@ -365,10 +297,10 @@ __device__ static inline void d_voxel_mean_multi(const VoxArgs &a) {
     out_keys[idx] = key & ((1ull << a.shift) - 1ull);
     if (a.nrm_in && out_nrm) out_nrm[idx] = make_float4((float)(nx / c), (float)(ny / c), (float)(nz / c), 0.0f);
 }
-__global__ void __launch_bounds__(BS) k_voxel_keys_multi(VoxArgs a) { d_voxel_keys_multi(a); }
-__global__ void __launch_bounds__(BS) k_voxel_mean_multi(VoxArgs a) { d_voxel_mean_multi(a); }
-__global__ void __launch_bounds__(BS) k_voxel_keys_multi_g(const VoxArgs *a) { d_voxel_keys_multi(a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_voxel_mean_multi_g(const VoxArgs *a) { d_voxel_mean_multi(a[blockIdx.y]); }
+// (VoxArgs carries two tables of eight scales: six of them fit the kernel arguments, PcrOp::kByValue)
+struct OpVoxelKeys : PcrOp<VoxArgs, BS> { __device__ static inline void run(const VoxArgs &a) { d_voxel_keys_multi(a); } };
+struct OpVoxelMean : PcrOp<VoxArgs, BS> { __device__ static inline void run(const VoxArgs &a) { d_voxel_mean_multi(a); } };
+static_assert(OpVoxelKeys::kByValue == 6, "VoxArgs by value");
 
 // the voxel stage of `count` clouds x n_scales grids in ONE keys / sort / scan / mean pass each (blockIdx.y = cloud): count == 1 is
 // the per-cloud call.  outs: count x n_scales clouds (pts / keys / n / optional nrm allocated by the caller, cap >= n).  *done = false
@@ -422,19 +354,11 @@ static int voxel_multi_batch(pcr_context *ctx, int count, const float *const *xy
         PCR_TRY(scan_args(ctx, &sa[c], flags, nullptr, (int)ne[c], pos, total, FlagSrc{k1, nullptr, nullptr}));
     }
     const int nb = (int)((max_ne + BS - 1) / BS);
-    if (count == 1) {
-        PCR_LAUNCH(ctx, k_voxel_keys_multi, dim3(nb), dim3(BS), 0, ctx->stream, va[0]);
-        PCR_TRY(pcr_sort_pairs(ctx, temps[0], pcr_sort_temp_bytes(ne[0]), kin[0], kout[0], vin[0], vout[0], ne[0], end_bit));
-        PCR_TRY(flag_scan_batch(ctx, sa.data(), 1));
-        PCR_LAUNCH(ctx, k_voxel_mean_multi, dim3(nb), dim3(BS), 0, ctx->stream, va[0]);
-    } else {
-        const VoxArgs *dv = pcr_desc_upload(ctx, va.data(), count);
-        if (!dv) return PCR_ENOMEM;
-        PCR_LAUNCH(ctx, k_voxel_keys_multi_g, dim3(nb, count), dim3(BS), 0, ctx->stream, dv);
-        PCR_TRY(pcr_sort_pairs_batch(ctx, count, temps.data(), kin.data(), kout.data(), vin.data(), vout.data(), ne.data(), end_bit));
-        PCR_TRY(flag_scan_batch(ctx, sa.data(), count));
-        PCR_LAUNCH(ctx, k_voxel_mean_multi_g, dim3(nb, count), dim3(BS), 0, ctx->stream, dv);
-    }
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpVoxelKeys, va.data(), count, dim3(nb, count)));
+    if (count == 1) PCR_TRY(pcr_sort_pairs(ctx, temps[0], pcr_sort_temp_bytes(ne[0]), kin[0], kout[0], vin[0], vout[0], ne[0], end_bit));
+    else PCR_TRY(pcr_sort_pairs_batch(ctx, count, temps.data(), kin.data(), kout.data(), vin.data(), vout.data(), ne.data(), end_bit));
+    PCR_TRY(flag_scan_batch(ctx, sa.data(), count));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpVoxelMean, va.data(), count, dim3(nb, count)));
     *done = true;
     return PCR_OK;
 }
@@ -449,16 +373,29 @@ int pcr_dev_voxel_multi_batch(pcr_context *ctx, int count, const float *const *x
 }
 
 // ===================================================== Morton ordering of a raw cloud (K2, part 1)
-__global__ void __launch_bounds__(BS) k_raw_keys(const float *__restrict__ xyz, int n, float ox, float oy, float oz, float sx, float sy, float sz,
-                                                 uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
-    const int i = blockIdx.x * BS + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t ix = (uint32_t)fminf((xyz[i * 3] - ox) * sx, 65535.0f);
-    const uint32_t iy = (uint32_t)fminf((xyz[i * 3 + 1] - oy) * sy, 65535.0f);
-    const uint32_t iz = (uint32_t)fminf((xyz[i * 3 + 2] - oz) * sz, 65535.0f);
-    keys[i] = pcr_morton3(ix, iy, iz);
-    vals[i] = (uint32_t)i;
-}
+// Per cloud: lattice keys of the raw points (ONE unit for the three axes), then -- after the sort -- the points (and normals) in sorted order
+struct RawKeyArgs { const float *xyz; const float *nrm; int n; float ox, oy, oz, s; uint64_t *keys; uint32_t *vals; const uint32_t *perm; float4 *pts; float4 *nrm_out; int *n_dev; };
+struct OpRawKeys : PcrOp<RawKeyArgs, BS> {
+    __device__ static inline void run(const RawKeyArgs &a) {
+        const int i = blockIdx.x * BS + threadIdx.x;
+        if (i == 0) *a.n_dev = a.n;
+        if (i >= a.n) return;
+        const uint32_t ix = (uint32_t)fminf((a.xyz[i * 3] - a.ox) * a.s, 65535.0f);
+        const uint32_t iy = (uint32_t)fminf((a.xyz[i * 3 + 1] - a.oy) * a.s, 65535.0f);
+        const uint32_t iz = (uint32_t)fminf((a.xyz[i * 3 + 2] - a.oz) * a.s, 65535.0f);
+        a.keys[i] = pcr_morton3(ix, iy, iz);
+        a.vals[i] = (uint32_t)i;
+    }
+};
+struct OpGatherSorted : PcrOp<RawKeyArgs, BS> {
+    __device__ static inline void run(const RawKeyArgs &a) {
+        const int i = blockIdx.x * BS + threadIdx.x;
+        if (i >= a.n) return;
+        const uint32_t v = a.perm[i];
+        a.pts[i] = make_float4(a.xyz[v * 3], a.xyz[v * 3 + 1], a.xyz[v * 3 + 2], 0.0f);
+        if (a.nrm) a.nrm_out[i] = make_float4(a.nrm[v * 3], a.nrm[v * 3 + 1], a.nrm[v * 3 + 2], 0.0f);
+    }
+};
 __global__ void __launch_bounds__(BS) k_gather_f3_to_f4(const float *__restrict__ src, const uint32_t *__restrict__ perm, int n, float4 *__restrict__ dst) {
     const int i = blockIdx.x * BS + threadIdx.x;
     if (i >= n) return;
@@ -491,8 +428,7 @@ int pcr_dev_pack_f4_to_f3(pcr_context *ctx, const float4 *src, const int *n, int
 
 int pcr_dev_sort_cloud(pcr_context *ctx, const float *xyz, int64_t n, const double *b6, DevCloud *out, uint32_t *perm) {
     if (n > 0x7fffffff / 4) { ctx->err = "cloud too large"; return PCR_EINVAL; }
-    PCR_LAUNCH(ctx, k_set_int, dim3(1), dim3(1), 0, ctx->stream, out->n, (int)n);
-    if (n == 0) return PCR_OK;
+    if (n == 0) { PCR_LAUNCH(ctx, k_set_int, dim3(1), dim3(1), 0, ctx->stream, out->n, 0); return PCR_OK; }
     ArenaMark mark(ctx);
     uint64_t *k0 = arena<uint64_t>(ctx, n), *k1 = out->keys;
     uint32_t *v0 = arena<uint32_t>(ctx, n);
@@ -502,44 +438,22 @@ int pcr_dev_sort_cloud(pcr_context *ctx, const float *xyz, int64_t n, const doub
     // ONE lattice unit for the three axes (the largest extent over 2^16 cells): cubic Morton cells.  A unit per axis (round 1-2) made
     // the cells of an NCLT-shaped cloud (235 x 235 x 12 m) 20 x flatter than wide, and the curve then cuts a ground patch into contour
     // strips: 64 consecutive points had 408 distinct 30-NN neighbours instead of 209 (measured with per-wavefront counters of the k-NN kernel).
-    float s[3];
     double emax = 0.0;
     for (int d = 0; d < 3; d++) emax = b6[3 + d] - b6[d] > emax ? b6[3 + d] - b6[d] : emax;
-    for (int d = 0; d < 3; d++) {
-        const double e = emax;
-        s[d] = e > 0 ? (float)(65535.0 / e) : 0.0f;
-        out->key_org[d] = (float)b6[d]; out->key_unit[d] = e > 0 ? (float)(e / 65535.0) : 1.0f;
-    }
+    for (int d = 0; d < 3; d++) { out->key_org[d] = (float)b6[d]; out->key_unit[d] = emax > 0 ? (float)(emax / 65535.0) : 1.0f; }
+    RawKeyArgs r = {};
+    r.xyz = xyz; r.n = (int)n; r.ox = (float)b6[0]; r.oy = (float)b6[1]; r.oz = (float)b6[2]; r.s = emax > 0 ? (float)(65535.0 / emax) : 0.0f;
+    r.keys = k0; r.vals = v0; r.perm = perm; r.pts = out->pts; r.n_dev = out->n;
     const int nb = (int)((n + BS - 1) / BS);
-    PCR_LAUNCH(ctx, k_raw_keys, dim3(nb), dim3(BS), 0, ctx->stream, xyz, (int)n, (float)b6[0], (float)b6[1], (float)b6[2], s[0], s[1], s[2], k0, v0);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpRawKeys, &r, 1, dim3(nb)));      // (also stores the count)
     PCR_TRY(pcr_sort_pairs(ctx, temp, tb, k0, k1, v0, perm, n, 48));
-    PCR_LAUNCH(ctx, k_gather_f3_to_f4, dim3(nb), dim3(BS), 0, ctx->stream, xyz, perm, (int)n, out->pts);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpGatherSorted, &r, 1, dim3(nb)));
     return PCR_OK;
 }
 
 // ---- the same for `count` clouds in ONE pass (lockstep FGR groups): bounds (one read-back), keys, the batched radix sort, gathers and
 // all octrees in one batch of the six build kernels.  Per cloud the arithmetic of pcr_dev_sort_cloud: same lattice, same keys, same
 // stable order.  cs[c] must be allocated (pcr_alloc_cloud with a tree); perms[c]: sorted -> caller index.
-struct RawKeyArgs { const float *xyz; const float *nrm; int n; float ox, oy, oz, s; uint64_t *keys; uint32_t *vals; const uint32_t *perm; float4 *pts; float4 *nrm_out; int *n_dev; };
-__global__ void __launch_bounds__(BS) k_raw_keys_g(const RawKeyArgs *a_) {
-    const RawKeyArgs &a = a_[blockIdx.y];
-    const int i = blockIdx.x * BS + threadIdx.x;
-    if (i == 0) *a.n_dev = a.n;
-    if (i >= a.n) return;
-    const uint32_t ix = (uint32_t)fminf((a.xyz[i * 3] - a.ox) * a.s, 65535.0f);
-    const uint32_t iy = (uint32_t)fminf((a.xyz[i * 3 + 1] - a.oy) * a.s, 65535.0f);
-    const uint32_t iz = (uint32_t)fminf((a.xyz[i * 3 + 2] - a.oz) * a.s, 65535.0f);
-    a.keys[i] = pcr_morton3(ix, iy, iz);
-    a.vals[i] = (uint32_t)i;
-}
-__global__ void __launch_bounds__(BS) k_gather_sorted_g(const RawKeyArgs *a_) {
-    const RawKeyArgs &a = a_[blockIdx.y];
-    const int i = blockIdx.x * BS + threadIdx.x;
-    if (i >= a.n) return;
-    const uint32_t v = a.perm[i];
-    a.pts[i] = make_float4(a.xyz[v * 3], a.xyz[v * 3 + 1], a.xyz[v * 3 + 2], 0.0f);
-    if (a.nrm) a.nrm_out[i] = make_float4(a.nrm[v * 3], a.nrm[v * 3 + 1], a.nrm[v * 3 + 2], 0.0f);
-}
 int pcr_import_clouds_batch(pcr_context *ctx, int count, const float *const *xyz, const float *const *nrm, const int64_t *n, DevCloud *cs, uint32_t **perms) {
     if (count < 1) return PCR_OK;
     std::vector<double> b6((size_t)count * 6);
@@ -566,11 +480,9 @@ int pcr_import_clouds_batch(pcr_context *ctx, int count, const float *const *xyz
         const int nb = (int)((n[c] + BS - 1) / BS);
         max_nb = nb > max_nb ? nb : max_nb;
     }
-    const RawKeyArgs *d = pcr_desc_upload(ctx, a.data(), count);
-    if (!d) return PCR_ENOMEM;
-    PCR_LAUNCH(ctx, k_raw_keys_g, dim3(max_nb, count), dim3(BS), 0, ctx->stream, d);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpRawKeys, a.data(), count, dim3(max_nb, count)));
     PCR_TRY(pcr_sort_pairs_batch(ctx, count, temps.data(), kin.data(), kout.data(), vin.data(), vout.data(), nn.data(), 48));
-    PCR_LAUNCH(ctx, k_gather_sorted_g, dim3(max_nb, count), dim3(BS), 0, ctx->stream, d);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpGatherSorted, a.data(), count, dim3(max_nb, count)));
     std::vector<DevCloud *> cp((size_t)count);
     for (int c = 0; c < count; c++) cp[c] = &cs[c];
     return pcr_dev_build_bvh_batch(ctx, cp.data(), count);
@@ -701,14 +613,6 @@ __device__ static inline void d_oct_apply(const signed char *__restrict__ ls, co
 // F/G: tight boxes, bottom-up.  ONE OCTET (8 lanes) PER NODE: lane c reads point c, c + 8, ... of a leaf (coalesced 128-byte rows) or
 // child c of an inner node (one 256-byte read per octet); min / max over the octet by DPP.  (A thread per node walked its points or
 // children serially and, at level 1, wrote the fat-leaf record of up to ~400 points in one loop: 95 + 78 us per build in flight.)
-__device__ static inline float pcr_octet_minf(float v) {
-    v = fminf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
-    return v;
-}
-__device__ static inline float pcr_octet_maxf(float v) {
-    v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
-    return v;
-}
 __device__ static inline void d_oct_leaf_boxes(const float4 *__restrict__ pts, const OctMeta *__restrict__ meta, const int *__restrict__ child, float4 *__restrict__ boxes, int4 *__restrict__ up,
                                                        int4 *__restrict__ pinfo) {
     const int ol = threadIdx.x & 7;
@@ -786,32 +690,18 @@ __device__ static inline void d_oct_upper_boxes(const OctMeta *__restrict__ meta
     }
 }
 
-// ---- the six build kernels serve up to OCT_BATCH trees per launch: blockIdx.y picks the tree (the voxel clouds of all scales
+// ---- the six build kernels serve any number of trees per launch: blockIdx.y picks the tree (the voxel clouds of all scales
 // of a registration are built together: 6 launches instead of 6 per scale)
-#define OCT_BATCH PCR_MAX_BATCH
 struct OctBuildDesc {
     const uint64_t *keys; const int *n; signed char *ls; int *rows; OctMeta *meta; int *child; int *leaf_of;
     const float4 *pts; float4 *nodes; int4 *up; int4 *pinfo; int2 *l1; OctGeom g; int n_tiles, node_cap;
 };
-struct OctBuildBatch { OctBuildDesc a[OCT_BATCH]; };
-__device__ static inline void dd_oct_lstar(const OctBuildDesc &d) { if ((int)blockIdx.x >= d.n_tiles) return; d_oct_lstar(d.keys, d.n, d.ls, d.rows); }
-__device__ static inline void dd_oct_meta(const OctBuildDesc &d) { d_oct_meta(d.n, d.rows, d.n_tiles, d.node_cap, d.meta, d.child, d.g); }
-__device__ static inline void dd_oct_apply(const OctBuildDesc &d) { if ((int)blockIdx.x >= d.n_tiles) return; d_oct_apply(d.ls, d.meta, d.rows, d.child, d.leaf_of); }
-__device__ static inline void dd_oct_leaf(const OctBuildDesc &d) { d_oct_leaf_boxes(d.pts, d.meta, d.child, d.nodes, d.up, d.pinfo); }
-__device__ static inline void dd_oct_level1(const OctBuildDesc &d) { d_oct_level_boxes(d.meta, d.child, d.nodes, d.up, 1, d.pinfo, d.l1); }
-__device__ static inline void dd_oct_upper(const OctBuildDesc &d) { d_oct_upper_boxes(d.meta, d.child, d.nodes, d.up, 2); }
-__global__ void __launch_bounds__(BS) k_oct_lstar(OctBuildBatch b) { dd_oct_lstar(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(256) k_oct_meta(OctBuildBatch b) { dd_oct_meta(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_apply(OctBuildBatch b) { dd_oct_apply(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_leaf_boxes(OctBuildBatch b) { dd_oct_leaf(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_level_boxes(OctBuildBatch b) { dd_oct_level1(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(OCT_UPPER_BS) k_oct_upper_boxes(OctBuildBatch b) { dd_oct_upper(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_lstar_p(const OctBuildDesc *a) { dd_oct_lstar(a[blockIdx.y]); }
-__global__ void __launch_bounds__(256) k_oct_meta_p(const OctBuildDesc *a) { dd_oct_meta(a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_apply_p(const OctBuildDesc *a) { dd_oct_apply(a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_leaf_boxes_p(const OctBuildDesc *a) { dd_oct_leaf(a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_oct_level_boxes_p(const OctBuildDesc *a) { dd_oct_level1(a[blockIdx.y]); }
-__global__ void __launch_bounds__(OCT_UPPER_BS) k_oct_upper_boxes_p(const OctBuildDesc *a) { dd_oct_upper(a[blockIdx.y]); }
+struct OpOctLstar : PcrOp<OctBuildDesc, BS> { __device__ static inline void run(const OctBuildDesc &d) { if ((int)blockIdx.x >= d.n_tiles) return; d_oct_lstar(d.keys, d.n, d.ls, d.rows); } };
+struct OpOctMeta : PcrOp<OctBuildDesc, 256> { __device__ static inline void run(const OctBuildDesc &d) { d_oct_meta(d.n, d.rows, d.n_tiles, d.node_cap, d.meta, d.child, d.g); } };
+struct OpOctApply : PcrOp<OctBuildDesc, BS> { __device__ static inline void run(const OctBuildDesc &d) { if ((int)blockIdx.x >= d.n_tiles) return; d_oct_apply(d.ls, d.meta, d.rows, d.child, d.leaf_of); } };
+struct OpOctLeafBoxes : PcrOp<OctBuildDesc, BS> { __device__ static inline void run(const OctBuildDesc &d) { d_oct_leaf_boxes(d.pts, d.meta, d.child, d.nodes, d.up, d.pinfo); } };
+struct OpOctLevel1Boxes : PcrOp<OctBuildDesc, BS> { __device__ static inline void run(const OctBuildDesc &d) { d_oct_level_boxes(d.meta, d.child, d.nodes, d.up, 1, d.pinfo, d.l1); } };
+struct OpOctUpperBoxes : PcrOp<OctBuildDesc, OCT_UPPER_BS> { __device__ static inline void run(const OctBuildDesc &d) { d_oct_upper_boxes(d.meta, d.child, d.nodes, d.up, 2); } };
 
 int pcr_dev_build_bvh_batch(pcr_context *ctx, DevCloud *const *cs, int count) {
     if (count < 1) return PCR_OK;
@@ -837,13 +727,13 @@ int pcr_dev_build_bvh_batch(pcr_context *ctx, DevCloud *const *cs, int count) {
         if (nbl > max_nbl) max_nbl = nbl;
     }
     if (m == 0) return PCR_OK;
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_lstar, k_oct_lstar_p, b.data(), m, dim3(max_tiles, m), dim3(BS)));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_meta, k_oct_meta_p, b.data(), m, dim3(1, m), dim3(256)));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_apply, k_oct_apply_p, b.data(), m, dim3(max_tiles, m), dim3(BS)));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_leaf_boxes, k_oct_leaf_boxes_p, b.data(), m, dim3(max_nbl, m), dim3(BS)));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_level_boxes, k_oct_level_boxes_p, b.data(), m, dim3(max_nbl, m), dim3(BS)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctLstar, b.data(), m, dim3(max_tiles, m)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctMeta, b.data(), m, dim3(1, m)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctApply, b.data(), m, dim3(max_tiles, m)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctLeafBoxes, b.data(), m, dim3(max_nbl, m)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctLevel1Boxes, b.data(), m, dim3(max_nbl, m)));
     // levels >= 2 (n/64 nodes and fewer) in ONE workgroup per tree, level by level: a launch less than one grid per level
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OctBuildBatch, k_oct_upper_boxes, k_oct_upper_boxes_p, b.data(), m, dim3(1, m), dim3(OCT_UPPER_BS)));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpOctUpperBoxes, b.data(), m, dim3(1, m)));
     return PCR_OK;
 }
 int pcr_dev_build_bvh(pcr_context *ctx, DevCloud *c) { return pcr_dev_build_bvh_batch(ctx, &c, 1); }
@@ -922,11 +812,6 @@ int pcr_dev_build_grid_batch(pcr_context *ctx, const DevCloud *const *cs, const 
     }
     PCR_LAUNCH(ctx, k_grid_build, dim3((unsigned)((max_cap + BS - 1) / BS), (unsigned)d.size()), dim3(BS), 0, ctx->stream, dd);
     return PCR_OK;
-}
-
-static inline OctView oct_view(const DevCloud *c) {
-    OctView v; v.pts = c->pts; v.nodes = c->oct_nodes; v.up = c->oct_up; v.meta = c->oct_meta; v.leaf_of = c->leaf_of; v.keys = c->keys; v.pinfo = c->pinfo; v.l1rng = c->oct_l1;
-    return v;
 }
 
 // ====================================================================================== k-NN (K3)
@@ -1094,16 +979,13 @@ struct KnnArgs {
     int seed_span;                                       // Morton-index half-width of the seed range (-1: k)
     int *zero_a, *zero_b;                                // optional counters of LATER kernels, zeroed here (saves two memset launches)
     uint8_t *hard; int wave_budget;                      // wavefront kernel: optional, queries it gave up after wave_budget batches (1) or served (0)
-    int hard_piece;                                      // k_knn_list: 1 = the entries of hard_list are the first queries of 8-query pieces (k_radius_list), 0 = of 64-query wavefronts
+    int hard_piece;                                      // OpKnn<.., LIST>: 1 = the entries of hard_list are the first queries of 8-query pieces (OpRadiusList), 0 = of 64-query wavefronts
     int *hard_list, *hard_count;                         // ... and (hard_list != nullptr, instead of `hard`) the first query of every wavefront it gave up, appended with one atomic
-                                                         //   per wavefront; the octet kernel's list form (k_knn_list) serves exactly those
+                                                         //   per wavefront; the octet kernel's list form (OpKnn<.., LIST>) serves exactly those
     const uint8_t *keep; const int *pos;                 // optional: search only among points with keep[i] != 0; results and `todo`
                                                          //   are indexed by pos[i] (the compacted order) -- the cleaned cloud needs no tree of its own
 };
 
-__device__ static inline double octet_sum(double v) { return pcr_octet_sum(v); }
-
-struct KnnBatch { KnnArgs a[PCR_MAX_BATCH]; };
 // One wavefront = 8 Morton-consecutive queries g0 .. g0 + 7 (one per octet): the lambda `item` below.  LIST = false: wavefront w of workgroup b
 // serves queries (4 b + w) 8 ...; LIST = true: the queries of the wavefronts the one-query-per-lane kernel gave up (pcr_knn_wave.h: it appends
 // the first query of every such wavefront of 64 to a.hard_list, one atomic per wavefront) and nothing else -- a fixed, small grid whose
@@ -1202,7 +1084,7 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
                 if (d2 < a.r2cap) { s += sqrt(d2); c += 1.0; }
             }
         }
-        s = octet_sum(s); c = octet_sum(c);
+        s = pcr_octet_sum(s); c = pcr_octet_sum(c);
         if (ol == 0) a.avg[qi] = c > 0 ? s / c : -1.0;
         if (a.list_idx && SLOTS == 4) {
 #pragma unroll
@@ -1224,8 +1106,8 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
             }
         }
 #pragma unroll
-        for (int t = 0; t < 9; t++) cu[t] = octet_sum(cu[t]);
-        c = octet_sum(c);
+        for (int t = 0; t < 9; t++) cu[t] = pcr_octet_sum(cu[t]);
+        c = pcr_octet_sum(c);
         if (ol == 0) {
             double C6[6];
             if (c >= 3.0) {
@@ -1265,16 +1147,9 @@ __device__ static inline void d_knn_(const KnnArgs &a) {
     if (!LIST) item((int)blockIdx.x * OPB + wv * OCT);
     else for (int it = blockIdx.x * (KNN_BS / 64) + wv; it < n_items; it += gridDim.x * (KNN_BS / 64)) item(a.hard_piece ? a.hard_list[it] : a.hard_list[it >> 3] + (it & 7) * OCT);
 }
-template <int MODE, int SLOTS> __device__ static inline void d_knn(const KnnArgs &a) { d_knn_<MODE, SLOTS, false>(a); }
-template <int MODE, int SLOTS> __device__ static inline void d_knn_list(const KnnArgs &a) { d_knn_<MODE, SLOTS, true>(a); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn(KnnArgs a) { d_knn<MODE, SLOTS>(a); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list(KnnArgs a) { d_knn_list<MODE, SLOTS>(a); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list_batch(KnnBatch b) { d_knn_list<MODE, SLOTS>(b.a[blockIdx.y]); }
-// (the device-pointer forms inline the body by force: left to the inliner, whether it was inlined there depended on the order in which the
-// templates were instantiated, and a call out of line costs a stack frame and up to 100 VGPRs)
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_list_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn_list<MODE, SLOTS>(a[blockIdx.y]); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_batch(KnnBatch b) { d_knn<MODE, SLOTS>(b.a[blockIdx.y]); }
-template <int MODE, int SLOTS> __global__ void __launch_bounds__(KNN_BS) k_knn_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn<MODE, SLOTS>(a[blockIdx.y]); }
+template <int MODE, int SLOTS, bool LIST> struct OpKnn : PcrOp<KnnArgs, KNN_BS> {
+    __device__ static inline void run(const KnnArgs &a) { [[clang::always_inline]] d_knn_<MODE, SLOTS, LIST>(a); }
+};
 
 #include "pcr_knn_wave.h"
 
@@ -1302,15 +1177,21 @@ static int knn_wave_rows(pcr_context *ctx, KnnArgs &a, int cap) {
     a.list_idx = arena<int32_t>(ctx, (size_t)(cap > 0 ? cap : 1) * (size_t)a.k);
     return a.list_idx ? PCR_OK : PCR_ENOMEM;
 }
-template <int MODE> static int launch_knn_wave_only(pcr_context *ctx, KnnArgs *a, int count, int mc, int kmax);
 static int knn_wave_budget() { return pcr_options().knnw_budget.load(std::memory_order_relaxed); }      // batches of 64 candidates in pass 1 (mean 17, p99 43 at k = 30)
-template <int MODE> static int launch_knn_octet_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count);
 // grid of the list form: enough wavefronts for the usual ~1 % of hard wavefronts at once, striding when there are more
 static int knn_list_grid(int cap) { const int g = cap / (64 * 16); return g < 8 ? 8 : (g > 128 ? 128 : g); }
+// the octet kernel (LIST: its list form) with the register slots per lane the largest k of the batch asks for
+template <int MODE, bool LIST>
+static int launch_knn_octet_slots(pcr_context *ctx, const KnnArgs *a, int count, int kmax, dim3 grid) {
+    if (kmax <= 32) { using Op = OpKnn<MODE, 4, LIST>; return PCR_BATCH_LAUNCH(ctx, Op, a, count, grid); }
+    if (kmax <= 64) { using Op = OpKnn<MODE, 8, LIST>; return PCR_BATCH_LAUNCH(ctx, Op, a, count, grid); }
+    using Op = OpKnn<MODE, 25, LIST>; return PCR_BATCH_LAUNCH(ctx, Op, a, count, grid);
+}
+// the wavefront kernel over `count` searches (k <= 64 each), then the octet kernel's list form over the wavefronts that gave up
 template <int MODE>
 static int launch_knn_wave_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count, int mc, int kmax) {
     for (int k = 0; k < count; k++) PCR_TRY(knn_wave_rows<MODE>(ctx, a[k], caps[k]));
-    // the queries of the wavefronts that give up (budget, log) go to the octet kernel in a second launch, through a list (k_knn_list)
+    // the queries of the wavefronts that give up (budget, log) go to the octet kernel in a second launch, through a list
     const int budget = knn_wave_budget();
     const bool handover = MODE != KNN_MODE_DEBUG && kmax <= 64 && budget > 0;
     if (handover) {
@@ -1323,47 +1204,28 @@ static int launch_knn_wave_batch(pcr_context *ctx, KnnArgs *a, const int *caps, 
             if (!a[k].hard_list) return PCR_ENOMEM;
         }
     }
-    PCR_TRY(launch_knn_wave_only<MODE>(ctx, a, count, mc, kmax));
+    const dim3 grid((unsigned)(((size_t)mc + KW_BS - 1) / KW_BS), count);
+    if (kmax <= 20) { using Op = OpKnnWave<MODE, 20>; PCR_TRY(PCR_BATCH_LAUNCH(ctx, Op, a, count, grid)); }
+    else if (kmax <= 30) { using Op = OpKnnWave<MODE, 30>; PCR_TRY(PCR_BATCH_LAUNCH(ctx, Op, a, count, grid)); }
+    else { using Op = OpKnnWave<MODE, 64>; PCR_TRY(PCR_BATCH_LAUNCH(ctx, Op, a, count, grid)); }
     if (!handover) return PCR_OK;
     std::vector<KnnArgs> o(a, a + count);
     for (int k = 0; k < count; k++) { o[k].todo = nullptr; o[k].zero_a = nullptr; o[k].zero_b = nullptr; o[k].seed_span = -1; }
-    const dim3 grid(knn_list_grid(mc), count), block(KNN_BS);
-    if (kmax <= 32) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<MODE, 4>), (k_knn_list_batchp<MODE, 4>), o.data(), count, grid, block);
-    return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<MODE, 8>), (k_knn_list_batchp<MODE, 8>), o.data(), count, grid, block);
+    return launch_knn_octet_slots<MODE, true>(ctx, o.data(), count, kmax, dim3(knn_list_grid(mc), count));
 }
 template <int MODE>
-static int launch_knn_wave_only(pcr_context *ctx, KnnArgs *a, int count, int mc, int kmax) {
-    const dim3 grid((unsigned)(((size_t)mc + KW_BS - 1) / KW_BS), count), block(KW_BS);
-    if (kmax <= 20) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_wave_batch<MODE, 20>), (k_knn_wave_batchp<MODE, 20>), a, count, grid, block);
-    if (kmax <= 30) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_wave_batch<MODE, 30>), (k_knn_wave_batchp<MODE, 30>), a, count, grid, block);
-    return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_wave_batch<MODE, 64>), (k_knn_wave_batchp<MODE, 64>), a, count, grid, block);
-}
-template <int MODE>
-static int launch_knn_wave(pcr_context *ctx, int cap, KnnArgs a) {
-    PCR_TRY(knn_wave_rows<MODE>(ctx, a, cap));
-    const dim3 grid((unsigned)(((size_t)cap + KW_BS - 1) / KW_BS)), block(KW_BS);
-    const int budget = knn_wave_budget();
-    const bool handover = MODE != KNN_MODE_DEBUG && budget > 0;
-    if (handover) {
-        a.hard = nullptr; a.wave_budget = budget;
-        a.hard_count = arena<int>(ctx, 1); a.hard_list = arena<int>(ctx, (size_t)(cap > 0 ? cap : 1) / 64 + 1);
-        if (!a.hard_count || !a.hard_list) return PCR_ENOMEM;
-        PCR_HIP_CHECK(ctx, hipMemsetAsync(a.hard_count, 0, sizeof(int), ctx->stream));
+static int launch_knn_octet_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count) {
+    int mc = 0;
+    int kmax = 0;
+    for (int k = 0; k < count; k++) {
+        if (a[k].k < 1 || a[k].k > 200) { ctx->err = count == 1 ? "k out of range for the octet k-NN kernel (1..200)" : "batched k-NN: k must be in 1..200"; return PCR_EINVAL; }
+        a[k].seed_span = -1;
+        mc = caps[k] > mc ? caps[k] : mc; kmax = a[k].k > kmax ? a[k].k : kmax;
     }
-    if (a.k <= 20) PCR_LAUNCH(ctx, (k_knn_wave<MODE, 20>), grid, block, 0, ctx->stream, a);
-    else if (a.k <= 30) PCR_LAUNCH(ctx, (k_knn_wave<MODE, 30>), grid, block, 0, ctx->stream, a);
-    else PCR_LAUNCH(ctx, (k_knn_wave<MODE, 64>), grid, block, 0, ctx->stream, a);
-    if (handover) {                                  // the queries of the wavefronts that gave up: the octet kernel's list form, 8 per wavefront
-        KnnArgs o = a;
-        o.todo = nullptr; o.zero_a = nullptr; o.zero_b = nullptr; o.seed_span = -1;
-        const dim3 og(knn_list_grid(cap));
-        if (o.k <= 32) PCR_LAUNCH(ctx, (k_knn_list<MODE, 4>), og, dim3(KNN_BS), 0, ctx->stream, o);
-        else PCR_LAUNCH(ctx, (k_knn_list<MODE, 8>), og, dim3(KNN_BS), 0, ctx->stream, o);
-    }
-    return PCR_OK;
+    if (mc <= 0) return PCR_OK;
+    return launch_knn_octet_slots<MODE, false>(ctx, a, count, kmax, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS), count));
 }
-
-// `count` searches in ONE launch (blockIdx.y picks the problem; k <= 32): the SOR / normals searches of all scales of a cloud
+// `count` searches in ONE launch (blockIdx.y picks the problem): the SOR / normals searches of all scales of a cloud, or one search
 template <int MODE>
 static int launch_knn_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count) {
     long long total_pts = 0;
@@ -1378,37 +1240,13 @@ static int launch_knn_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int c
     }
     return launch_knn_octet_batch<MODE>(ctx, a, caps, count);
 }
+// one search per launch where the batched form would pick another kernel than the one-cloud call did (k > 32: the octet and the
+// wavefront kernel do not sum in the same order)
 template <int MODE>
-static int launch_knn_octet_batch(pcr_context *ctx, KnnArgs *a, const int *caps, int count) {
-    int mc = 0;
-    int kmax = 0;
-    for (int k = 0; k < count; k++) {
-        if (a[k].k < 1 || a[k].k > 200) { ctx->err = "batched k-NN: k must be in 1..200"; return PCR_EINVAL; }
-        a[k].seed_span = -1;
-        mc = caps[k] > mc ? caps[k] : mc; kmax = a[k].k > kmax ? a[k].k : kmax;
-    }
-    if (mc <= 0) return PCR_OK;
-    // register slots per lane by the largest k of the batch, exactly as the one-cloud launch picks them (launch_knn_cap): same arithmetic
-    const dim3 grid((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS), count), block(KNN_BS);
-    if (kmax <= 32) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_batch<MODE, 4>), (k_knn_batchp<MODE, 4>), a, count, grid, block);
-    if (kmax <= 64) return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_batch<MODE, 8>), (k_knn_batchp<MODE, 8>), a, count, grid, block);
-    return PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_batch<MODE, 25>), (k_knn_batchp<MODE, 25>), a, count, grid, block);
-}
-
-template <int MODE>
-static int launch_knn_cap(pcr_context *ctx, int cap, KnnArgs a) {
-    if (cap <= 0) return PCR_OK;
-    if (a.k < 1 || a.k > 200) { ctx->err = "k out of range for the octet k-NN kernel (1..200)"; return PCR_EINVAL; }
-    const dim3 grid((unsigned)(((size_t)cap * OCT + KNN_BS - 1) / KNN_BS)), block(KNN_BS);
-    a.seed_span = -1;
-    if (knn_wave_enabled(ctx, 1, cap) && knn_wave_fits(a)) { a.seed_span = -1; return launch_knn_wave<MODE>(ctx, cap, a); }
-    if (a.k <= 32) PCR_LAUNCH(ctx, k_knn<MODE, 4>, grid, block, 0, ctx->stream, a);
-    else if (a.k <= 64) PCR_LAUNCH(ctx, k_knn<MODE, 8>, grid, block, 0, ctx->stream, a);
-    else PCR_LAUNCH(ctx, k_knn<MODE, 25>, grid, block, 0, ctx->stream, a);
+static int launch_knn_each(pcr_context *ctx, KnnArgs *a, const int *caps, int count) {
+    for (int k = 0; k < count; k++) PCR_TRY(launch_knn_batch<MODE>(ctx, a + k, caps + k, 1));
     return PCR_OK;
 }
-template <int MODE>
-static int launch_knn(pcr_context *ctx, const DevCloud *c, KnnArgs a) { return launch_knn_cap<MODE>(ctx, c->cap, a); }
 
 static void knn_radius(KnnArgs &a, int search_kind, double radius) {
     if (search_kind == PCR_SEARCH_HYBRID && radius > 0) {
@@ -1423,7 +1261,7 @@ int pcr_dev_knn_debug(pcr_context *ctx, const DevCloud *c, int k, double radius,
     knn_radius(a, radius > 0 ? PCR_SEARCH_HYBRID : PCR_SEARCH_KNN, radius);
     if (radius > 0) a.r2cap_f = (float)(radius * radius);
     a.dbg_idx = idx; a.dbg_d2 = d2; a.dbg_cnt = counts;
-    return launch_knn<KNN_MODE_DEBUG>(ctx, c, a);
+    return launch_knn_batch<KNN_MODE_DEBUG>(ctx, &a, &c->cap, 1);
 }
 
 // ============================================================== pure radius neighbourhoods (KDTreeSearchParamRadius)
@@ -1467,8 +1305,8 @@ __global__ void __launch_bounds__(KNN_BS) k_radius_moments(RadArgs a) {
     oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return a.r2f; }, visit,
                      [](int, int) { return false; }, ol);
 #pragma unroll
-    for (int t = 0; t < 9; t++) cu[t] = octet_sum(cu[t]);
-    c = octet_sum(c);
+    for (int t = 0; t < 9; t++) cu[t] = pcr_octet_sum(cu[t]);
+    c = pcr_octet_sum(c);
     if (live && ol == 0) {
         double C6[6];
         if (c >= 3.0) {
@@ -1496,7 +1334,7 @@ __global__ void __launch_bounds__(KNN_BS) k_radius_moments(RadArgs a) {
 // sorted insertion (99 VALU instructions per round): 13.6 % of the FGR stage.  Here an octet APPENDS what it finds (same float32 test against
 // r^2 as the k-best kernel, same shared walk with the fixed bound): row = the query's in-ball points in walk order, cnt = their number.  A
 // piece of 8 queries in which one ball holds more than k points is listed (one atomic per piece) and redone by the k-best kernel's list form
-// (k_knn_list with hard_piece), which writes the k nearest in its slot layout; cnt = -1 tells the readers to scan all k slots of such a row.
+// (OpKnn<.., LIST> with hard_piece), which writes the k nearest in its slot layout; cnt = -1 tells the readers to scan all k slots of such a row.
 struct RadListArgs {
     OctView t; const int *n_ptr; float r2f; int k;
     int32_t *idx; int32_t *cnt;                  // rows of k int32 per query; entries per row (-1: row in the k-best kernel's slot layout, scan all k)
@@ -1511,7 +1349,7 @@ struct RadListArgs {
 // row -- smallest by (float64 d^2, caller index), the order of the reference's k-d tree (oracle/kdtree.c cmp_item), so that a tie at the k-th
 // place falls as it does there; the caller index comes from RadListArgs::perm (the points' w is 0).  Both walks test the same float32
 // expressions, so they see the same points.  A boundary bin of more than RL_EDGE points (many equal distances), or a ball of more than 65 535
-// points (a 16-bit bin counter may have wrapped into its neighbour), sends the piece to the k-best kernel, and k_radius_fix below then decides
+// points (a 16-bit bin counter may have wrapped into its neighbour), sends the piece to the k-best kernel, and OpRadiusFix below then decides
 // the k-th place of its rows by the same (float64 d^2, caller index) rule: the lists are the same set on every path.
 #define RL_BINS 128            // (two 16-bit counters per LDS word; a ball of more than 0xffff points is the k-best kernel's)
 #define RL_EDGE 20
@@ -1622,8 +1460,7 @@ __device__ static inline void d_radius_list(const RadListArgs &a) {
     if (live && ol == 0) a.cnt[qi] = over ? -1 : cnt;
     if (over && lane == 0) a.over_list[atomicAdd(a.over_count, 1)] = g0;
 }
-__global__ void __launch_bounds__(KNN_BS) k_radius_list(RadListArgs a) { d_radius_list(a); }
-__global__ void __launch_bounds__(KNN_BS) k_radius_list_g(const RadListArgs *a) { d_radius_list(a[blockIdx.y]); }
+struct OpRadiusList : PcrOp<RadListArgs, KNN_BS> { __device__ static inline void run(const RadListArgs &a) { d_radius_list(a); } };
 
 // The k-th place of the pieces the k-best kernel listed (spilled boundary bins, the 16-bit counter guard, every overfull piece under select = 0).
 // That kernel keeps the first of equal float32 distances its walk meets: right for SOR and normals, which never look at which one, but FPFH's
@@ -1775,8 +1612,7 @@ __device__ static inline void d_radius_fix(const RadListArgs &a) {
                          [](int, int) { return false; }, ol);
     }
 }
-__global__ void __launch_bounds__(KNN_BS) k_radius_fix(RadListArgs a) { d_radius_fix(a); }
-__global__ void __launch_bounds__(KNN_BS) k_radius_fix_g(const RadListArgs *a) { d_radius_fix(a[blockIdx.y]); }
+struct OpRadiusFix : PcrOp<RadListArgs, KNN_BS> { __device__ static inline void run(const RadListArgs &a) { d_radius_fix(a); } };
 // `count` clouds in one launch triple: the append kernel, the k-best list form over the listed pieces, the k-th place of those pieces.  Rows
 // idx[c]: cap x k int32, cnt[c]: cap int32; perms[c]: sorted -> caller index.  (Hybrid search only: radius > 0.)
 int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, const uint32_t *const *perms, int count, int k, double radius, int32_t *const *idx, int32_t *const *cnt) {
@@ -1807,23 +1643,13 @@ int pcr_dev_radius_lists_batch(pcr_context *ctx, const DevCloud *const *cs, cons
     }
     const int m = (int)ra.size();
     if (m == 0) return PCR_OK;
-    const RadListArgs *d = nullptr;
-    if (m == 1) {
-        PCR_LAUNCH(ctx, k_radius_list, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS)), dim3(KNN_BS), 0, ctx->stream, ra[0]);
-    } else {
-        d = pcr_desc_upload(ctx, ra.data(), m);
-        if (!d) return PCR_ENOMEM;
-        PCR_LAUNCH(ctx, k_radius_list_g, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS), m), dim3(KNN_BS), 0, ctx->stream, d);
-    }
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpRadiusList, ra.data(), m, dim3((unsigned)(((size_t)mc * OCT + KNN_BS - 1) / KNN_BS), m)));
     // the overfull pieces: as many wavefronts as a dense cloud may list (every piece), striding
     int lg = mc / (OCT * (KNN_BS / 64) * 4); lg = lg < 8 ? 8 : (lg > 2048 ? 2048 : lg);
-    const dim3 grid(lg, m), block(KNN_BS);
-    if (k <= 32) PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 4>), (k_knn_list_batchp<KNN_MODE_DEBUG, 4>), ka.data(), m, grid, block));
-    else if (k <= 64) PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 8>), (k_knn_list_batchp<KNN_MODE_DEBUG, 8>), ka.data(), m, grid, block));
-    else PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_DEBUG, 25>), (k_knn_list_batchp<KNN_MODE_DEBUG, 25>), ka.data(), m, grid, block));
+    const dim3 grid(lg, m);
+    PCR_TRY((launch_knn_octet_slots<KNN_MODE_DEBUG, true>(ctx, ka.data(), m, k, grid)));
     // ... and their k-th place by (float64 d^2, caller index)
-    if (m == 1) PCR_LAUNCH(ctx, k_radius_fix, grid, block, 0, ctx->stream, ra[0]);
-    else PCR_LAUNCH(ctx, k_radius_fix_g, grid, block, 0, ctx->stream, d);
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpRadiusFix, ra.data(), m, grid));
     return PCR_OK;
 }
 
@@ -1840,7 +1666,6 @@ struct NflArgs {
     uint8_t *todo; int *todo_count;
     int *piece_list, *piece_count;                   // optional: first point (un-cleaned index) of every 8-point piece that holds a todo point -- the work list of the fallback search
 };
-struct NflBatch { NflArgs a[PCR_MAX_BATCH]; };
 // A wavefront serves 64 points: octet o takes points base + 8 o + r in rounds r = 0..7 (list filtering, farthest-survivor drops, raw
 // moments: 8 lanes per point as before), lane r of the octet keeps the moments of round r, and after the eighth round ALL 64 lanes
 // run the analytic eigen solver at once -- it is ~2/3 of this kernel's instructions and used to run with one live lane per octet.
@@ -1901,15 +1726,15 @@ __device__ static inline void d_normals_from_lists(const NflArgs &a) {
             }
         }
 #pragma unroll
-        for (int t = 0; t < 9; t++) cu[t] = octet_sum(cu[t]);
-        c = octet_sum(c);
+        for (int t = 0; t < 9; t++) cu[t] = pcr_octet_sum(cu[t]);
+        c = pcr_octet_sum(c);
         if (ol == r) {                                  // this lane solves the point of round r
             my_exact = exact; my_j = j; my_c = c;
 #pragma unroll
             for (int t = 0; t < 9; t++) my_cu[t] = cu[t];
         }
     }
-    // the fallback search serves exactly the listed pieces (k_knn_list, hard_piece): the full-range launch with the todo mask started a wavefront
+    // the fallback search serves exactly the listed pieces (OpKnn<.., LIST>, hard_piece): the full-range launch with the todo mask started a wavefront
     // per 8 points of the whole cloud to find the ~2 % that hold one (8.9 % of the headline run's kernel time)
     if (a.piece_list && piece_todo && ol == 0) a.piece_list[atomicAdd(a.piece_count, 1)] = base + oct_id * OCT;
     if (!my_exact) return;
@@ -1930,9 +1755,7 @@ __device__ static inline void d_normals_from_lists(const NflArgs &a) {
     a.normals[my_j] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.0f);
 }
 
-__global__ void __launch_bounds__(KNN_BS) k_normals_from_lists(NflArgs a) { d_normals_from_lists(a); }
-__global__ void __launch_bounds__(KNN_BS) k_normals_from_lists_batch(NflBatch b) { d_normals_from_lists(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(KNN_BS) k_normals_from_lists_batchp(const NflArgs *a) { d_normals_from_lists(a[blockIdx.y]); }
+struct OpNormalsFromLists : PcrOp<NflArgs, KNN_BS> { __device__ static inline void run(const NflArgs &a) { d_normals_from_lists(a); } };
 
 // ============================================================================ SOR (K4)
 // mean / Bessel std of the per-point mean neighbour distance in ONE pass over <= 128 workgroups: shifted moments
@@ -1940,7 +1763,6 @@ __global__ void __launch_bounds__(KNN_BS) k_normals_from_lists_batchp(const NflA
 // tree, write-through partial rows + ticket, the last workgroup gathers them with sc1 loads (no fence) and finishes.
 #define SOR_STAT_BLOCKS 128
 struct SorStatArgs { const double *avg; const int *n_ptr; double std_ratio; double *out3; double *partials /* SOR_STAT_BLOCKS x 4 */; unsigned int *ticket; };
-struct SorStatBatch { SorStatArgs a[PCR_MAX_BATCH]; };
 __device__ static inline void d_sor_stats(const SorStatArgs &aa) {
     const double *__restrict__ avg = aa.avg; const int *__restrict__ n_ptr = aa.n_ptr; const double std_ratio = aa.std_ratio;
     double *__restrict__ out3 = aa.out3; double *__restrict__ partials = aa.partials; unsigned int *__restrict__ ticket = aa.ticket;
@@ -1983,15 +1805,12 @@ __device__ static inline void d_sor_stats(const SorStatArgs &aa) {
         *ticket = 0u;
     }
 }
-__global__ void __launch_bounds__(256) k_sor_stats(SorStatArgs a) { d_sor_stats(a); }
-__global__ void __launch_bounds__(256) k_sor_stats_batch(SorStatBatch b) { d_sor_stats(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(256) k_sor_stats_batchp(const SorStatArgs *a) { d_sor_stats(a[blockIdx.y]); }
+struct OpSorStats : PcrOp<SorStatArgs, 256> { __device__ static inline void run(const SorStatArgs &a) { d_sor_stats(a); } };
 
 struct CompactArgs {
     const float4 *pts, *nrm; const uint8_t *flags; const int *pos; const int *n_ptr; float4 *out_pts, *out_nrm;
     const uint64_t *keys; uint64_t *out_keys; int *cnt_in_out, *cnt_kept_out; const int *kept_n;
 };
-struct CompactBatch { CompactArgs a[PCR_MAX_BATCH]; };
 __device__ static inline void d_compact_cloud(const CompactArgs &a) {
     const int i = blockIdx.x * BS + threadIdx.x;
     if (i == 0) { if (a.cnt_in_out) *a.cnt_in_out = *a.n_ptr; if (a.cnt_kept_out) *a.cnt_kept_out = *a.kept_n; }    // counts for the host, one copy later
@@ -2001,9 +1820,7 @@ __device__ static inline void d_compact_cloud(const CompactArgs &a) {
     a.out_keys[o] = a.keys[i];
     if (a.nrm && a.out_nrm) a.out_nrm[o] = a.nrm[i];
 }
-__global__ void __launch_bounds__(BS) k_compact_cloud(CompactArgs a) { d_compact_cloud(a); }
-__global__ void __launch_bounds__(BS) k_compact_cloud_batch(CompactBatch b) { d_compact_cloud(b.a[blockIdx.y]); }
-__global__ void __launch_bounds__(BS) k_compact_cloud_batchp(const CompactArgs *a) { d_compact_cloud(a[blockIdx.y]); }
+struct OpCompactCloud : PcrOp<CompactArgs, BS> { __device__ static inline void run(const CompactArgs &a) { d_compact_cloud(a); } };
 
 // The SOR chain of `count` clouds in ONE launch per stage (blockIdx.y picks the cloud): k-NN + k-best lists, statistics, keep flags
 // inside the two-kernel scan, compaction, normals of the cleaned cloud from the lists, exact fallback search for the incomplete lists.
@@ -2021,11 +1838,11 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
     std::memset(kbv.data(), 0, sizeof(KnnArgs) * (size_t)count); std::memset(fbv.data(), 0, sizeof(KnnArgs) * (size_t)count);
     std::memset(sbv.data(), 0, sizeof(SorStatArgs) * (size_t)count); std::memset(cbv.data(), 0, sizeof(ScanArgs) * (size_t)count);
     std::memset(mbv.data(), 0, sizeof(CompactArgs) * (size_t)count); std::memset(nbv.data(), 0, sizeof(NflArgs) * (size_t)count);
-    struct { KnnArgs *a; } kb{kbv.data()}, fb{fbv.data()}; struct { SorStatArgs *a; } sb{sbv.data()}; struct { ScanArgs *a; } cb{cbv.data()};
-    struct { CompactArgs *a; } mb{mbv.data()}; struct { NflArgs *a; } nb_{nbv.data()};
+    KnnArgs *const kb = kbv.data(), *const fb = fbv.data(); SorStatArgs *const sb = sbv.data(); ScanArgs *const cb = cbv.data();
+    CompactArgs *const mb = mbv.data(); NflArgs *const nb_ = nbv.data();
     std::vector<int> capsv((size_t)count); int *caps = capsv.data(); int m = 0;
     bool any_todo = false, fuse_all = true;
-    // work lists of the fallback normals (pieces of 8 points that hold a todo point, filled by k_normals_from_lists): one counter per problem, zeroed together
+    // work lists of the fallback normals (pieces of 8 points that hold a todo point, filled by OpNormalsFromLists): one counter per problem, zeroed together
     int *piece_counts = (fallback_here && normal_k > 0 && normal_k <= 32) ? arena<int>(ctx, count) : nullptr;
     if (piece_counts) PCR_HIP_CHECK(ctx, hipMemsetAsync(piece_counts, 0, sizeof(int) * (size_t)count, ctx->stream));
     for (int k = 0; k < count; k++) {
@@ -2041,23 +1858,23 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
         uint8_t *flags = q.keep_sorted ? q.keep_sorted : arena<uint8_t>(ctx, in->cap);
         int *pos = arena<int>(ctx, in->cap);
         if (!avg || !stats3 || !stat_partials || !stat_ticket || !flags || !pos) return PCR_ENOMEM;
-        // normals of the cleaned cloud straight from this pass's lists when they can be exact (see k_normals_from_lists)
+        // normals of the cleaned cloud straight from this pass's lists when they can be exact (see OpNormalsFromLists)
         const bool fuse = normal_k > 0 && q.todo_out && nb_neighbors <= 32 && normal_k <= nb_neighbors;
-        const int pitch = nb_neighbors <= 32 ? 32 : 64;           // k-best rows: input of k_normals_from_lists (pitch 32) and the working rows of the wavefront search
+        const int pitch = nb_neighbors <= 32 ? 32 : 64;           // k-best rows: input of OpNormalsFromLists (pitch 32) and the working rows of the wavefront search
         int32_t *lidx = (fuse || nb_neighbors <= 64) ? arena<int32_t>(ctx, (size_t)in->cap * pitch) : nullptr;
         if ((fuse || nb_neighbors <= 64) && !lidx) return PCR_ENOMEM;
-        KnnArgs &a = kb.a[m];
+        KnnArgs &a = kb[m];
         a.t = oct_view(in); a.n_ptr = in->n; a.k = nb_neighbors; a.avg = avg; a.list_idx = lidx; a.list_pitch = pitch;
         a.zero_a = (int *)stat_ticket; a.zero_b = (fuse && q.todo_out) ? q.todo_count : nullptr;      // zeroed by the search kernel for the kernels after it
         a.seed_span = -1;
         knn_radius(a, PCR_SEARCH_KNN, 0);
-        sb.a[m] = SorStatArgs{avg, in->n, std_ratio, stats3, stat_partials, stat_ticket};
-        PCR_TRY(scan_args(ctx, &cb.a[m], flags, in->n, in->cap, pos, out->n, FlagSrc{nullptr, avg, stats3}));      // keep flags produced inside the scan
-        mb.a[m] = CompactArgs{in->pts, in->nrm, flags, pos, in->n, out->pts, out->nrm, in->keys, out->keys, q.cnt_in_out, q.cnt_kept_out, out->n};
+        sb[m] = SorStatArgs{avg, in->n, std_ratio, stats3, stat_partials, stat_ticket};
+        PCR_TRY(scan_args(ctx, &cb[m], flags, in->n, in->cap, pos, out->n, FlagSrc{nullptr, avg, stats3}));      // keep flags produced inside the scan
+        mb[m] = CompactArgs{in->pts, in->nrm, flags, pos, in->n, out->pts, out->nrm, in->keys, out->keys, q.cnt_in_out, q.cnt_kept_out, out->n};
         if (q.todo_out) {
             any_todo = true;
             if (fuse) {
-                NflArgs &f = nb_.a[m];
+                NflArgs &f = nb_[m];
                 f.pts = in->pts; f.n_ptr = in->n; f.lidx = lidx; f.keep = flags; f.pos = pos; f.k_list = nb_neighbors; f.k_nrm = normal_k;
                 f.prior = q.prior_out; f.normals = out->nrm_final; f.todo = q.todo_out; f.todo_count = q.todo_count;
             } else {
@@ -2067,7 +1884,7 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
             if (fallback_here && normal_k > 0) {
                 // the incomplete lists are searched right here, over the INPUT cloud's tree restricted to the kept points: the
                 // cleaned cloud then needs no tree of its own (7 launches less; only a GICP target needs one)
-                KnnArgs &b = fb.a[m];
+                KnnArgs &b = fb[m];
                 // (lists that cannot serve -- normal_k > nb_neighbors: config 5's 64-NN normals -- leave EVERY kept point to this search: no todo
                 // mask then, so that it may run as the one-query-per-lane kernel; with the mask of all ones it ran as the octet kernel over the
                 // whole cloud, 25 % of config 5's kernel time)
@@ -2077,7 +1894,7 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
                 if (fuse && piece_counts) {
                     int *pl = arena<int>(ctx, (size_t)in->cap / OCT + 1);
                     if (!pl) return PCR_ENOMEM;
-                    nb_.a[m].piece_list = pl; nb_.a[m].piece_count = piece_counts + m;
+                    nb_[m].piece_list = pl; nb_[m].piece_count = piece_counts + m;
                     b.hard_list = pl; b.hard_count = piece_counts + m; b.hard_piece = 1;
                 }
             }
@@ -2088,27 +1905,23 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
     if (m == 0) return PCR_OK;
     int mc = 0;
     for (int k = 0; k < m; k++) mc = caps[k] > mc ? caps[k] : mc;
-    if (m == 1 && nb_neighbors > 32) {      // the single-cloud call with a long list: the wide-slot kernels
-        DevCloud tmp; tmp.cap = caps[0];
-        PCR_TRY(launch_knn<KNN_MODE_SOR>(ctx, &tmp, kb.a[0]));
-    } else {
-        if (nb_neighbors > 32) { ctx->err = "batched SOR: nb_neighbors must be <= 32"; return PCR_EINVAL; }
-        PCR_TRY(launch_knn_batch<KNN_MODE_SOR>(ctx, kb.a, caps, m));
-    }
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, SorStatBatch, k_sor_stats_batch, k_sor_stats_batchp, sb.a, m, dim3(SOR_STAT_BLOCKS, m), dim3(256)));
-    PCR_TRY(flag_scan_batch(ctx, cb.a, m));
-    PCR_TRY(PCR_BATCH_LAUNCH(ctx, CompactBatch, k_compact_cloud_batch, k_compact_cloud_batchp, mb.a, m, dim3((mc + BS - 1) / BS, m), dim3(BS)));
+    // (one cloud may ask for a long list: the wide-slot kernels; the batched chain is the 32-slot one)
+    if (m > 1 && nb_neighbors > 32) { ctx->err = "batched SOR: nb_neighbors must be <= 32"; return PCR_EINVAL; }
+    PCR_TRY(launch_knn_batch<KNN_MODE_SOR>(ctx, kb, caps, m));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpSorStats, sb, m, dim3(SOR_STAT_BLOCKS, m)));
+    PCR_TRY(flag_scan_batch(ctx, cb, m));
+    PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpCompactCloud, mb, m, dim3((mc + BS - 1) / BS, m)));
     if (any_todo) {
-        if (fuse_all) PCR_TRY(PCR_BATCH_LAUNCH(ctx, NflBatch, k_normals_from_lists_batch, k_normals_from_lists_batchp, nb_.a, m, dim3((unsigned)(((size_t)mc + KNN_BS - 1) / KNN_BS), m), dim3(KNN_BS)));
-        else for (int k = 0; k < m; k++) if (nb_.a[k].pts) PCR_LAUNCH(ctx, k_normals_from_lists, dim3((unsigned)(((size_t)caps[k] + KNN_BS - 1) / KNN_BS)), dim3(KNN_BS), 0, ctx->stream, nb_.a[k]);
+        if (fuse_all) PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpNormalsFromLists, nb_, m, dim3((unsigned)(((size_t)mc + KNN_BS - 1) / KNN_BS), m)));
+        else for (int k = 0; k < m; k++) if (nb_[k].pts) PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpNormalsFromLists, nb_ + k, 1, dim3((unsigned)(((size_t)caps[k] + KNN_BS - 1) / KNN_BS))));
         if (fallback_here && normal_k > 0) {
             bool listed = fuse_all && piece_counts != nullptr;
-            for (int k = 0; k < m; k++) listed = listed && fb.a[k].hard_list != nullptr;
+            for (int k = 0; k < m; k++) listed = listed && fb[k].hard_list != nullptr;
             if (listed) {       // every problem's todo points come as a list of pieces: the octet kernel's list form, a fixed small grid striding over them
-                const dim3 grid(knn_list_grid(mc), m), block(KNN_BS);
-                PCR_TRY(PCR_BATCH_LAUNCH(ctx, KnnBatch, (k_knn_list_batch<KNN_MODE_NORMALS, 4>), (k_knn_list_batchp<KNN_MODE_NORMALS, 4>), fb.a, m, grid, block));
-            } else if (normal_k <= 32) PCR_TRY(launch_knn_batch<KNN_MODE_NORMALS>(ctx, fb.a, caps, m));
-            else for (int k = 0; k < m; k++) { DevCloud tmp; tmp.cap = caps[k]; PCR_TRY(launch_knn<KNN_MODE_NORMALS>(ctx, &tmp, fb.a[k])); }
+                using Op = OpKnn<KNN_MODE_NORMALS, 4, true>;
+                PCR_TRY(PCR_BATCH_LAUNCH(ctx, Op, fb, m, dim3(knn_list_grid(mc), m)));
+            } else if (normal_k <= 32) PCR_TRY(launch_knn_batch<KNN_MODE_NORMALS>(ctx, fb, caps, m));
+            else PCR_TRY(launch_knn_each<KNN_MODE_NORMALS>(ctx, fb, caps, m));
         }
     }
     return PCR_OK;
@@ -2136,18 +1949,17 @@ int pcr_dev_normals_batch(pcr_context *ctx, DevCloud *const *cs, int count, int 
     if (knn < 1) { ctx->err = "knn < 1"; return PCR_EINVAL; }
     if (count > PCR_MAX_GROUP_BATCH) { ctx->err = "normals batch size"; return PCR_EINVAL; }
     std::vector<KnnArgs> bv((size_t)(count > 0 ? count : 1)); std::memset(bv.data(), 0, sizeof(KnnArgs) * bv.size());
-    struct { KnnArgs *a; } b{bv.data()}; std::vector<int> capsv((size_t)(count > 0 ? count : 1)); int *caps = capsv.data(); int m = 0;
+    KnnArgs *const b = bv.data(); std::vector<int> capsv((size_t)(count > 0 ? count : 1)); int *caps = capsv.data(); int m = 0;
     for (int k = 0; k < count; k++) {
         if (cs[k]->cap <= 0) continue;
-        KnnArgs &a = b.a[m];
+        KnnArgs &a = b[m];
         a.t = oct_view(cs[k]); a.n_ptr = cs[k]->n; a.k = knn; a.prior = priors ? priors[k] : nullptr; a.normals = normals_out[k]; a.todo = todos ? todos[k] : nullptr; a.seed_span = -1;
         knn_radius(a, search_kind, radius);
         caps[m++] = cs[k]->cap;
     }
     if (m == 0) return PCR_OK;
-    if (knn <= 32) return launch_knn_batch<KNN_MODE_NORMALS>(ctx, b.a, caps, m);
-    for (int k = 0; k < m; k++) { DevCloud tmp; tmp.cap = caps[k]; PCR_TRY(launch_knn<KNN_MODE_NORMALS>(ctx, &tmp, b.a[k])); }
-    return PCR_OK;
+    if (knn <= 32) return launch_knn_batch<KNN_MODE_NORMALS>(ctx, b, caps, m);
+    return launch_knn_each<KNN_MODE_NORMALS>(ctx, b, caps, m);
 }
 // the k-best lists of `count` clouds in one launch of the octet kernel (the FPFH neighbour lists of a lockstep FGR group): per cloud
 // exactly pcr_dev_knn_debug
@@ -2192,7 +2004,7 @@ int pcr_dev_normals(pcr_context *ctx, DevCloud *c, int search_kind, int knn, dou
     KnnArgs a = {};
     a.t = oct_view(c); a.n_ptr = c->n; a.k = knn; a.prior = prior; a.normals = normals_out; a.cov6 = cov6_out; a.todo = todo;
     knn_radius(a, search_kind, radius);
-    return launch_knn<KNN_MODE_NORMALS>(ctx, c, a);
+    return launch_knn_batch<KNN_MODE_NORMALS>(ctx, &a, &c->cap, 1);
 }
 
 size_t pcr_scratch_bytes_for(int64_t n) {

@@ -61,6 +61,15 @@ __device__ static inline float pcr_octet_min(float v) {
     i = min(i, pcr_dpp_i<PCR_DPP_HMIRROR>(i));
     return __int_as_float(i);
 }
+// ... and for any float (box corners: negative coordinates), by fminf / fmaxf
+__device__ static inline float pcr_octet_minf(float v) {
+    v = fminf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
+    return v;
+}
+__device__ static inline float pcr_octet_maxf(float v) {
+    v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
+    return v;
+}
 __device__ static inline int pcr_octet_sum_i(int v) {
     v += pcr_dpp_i<PCR_DPP_XOR1>(v); v += pcr_dpp_i<PCR_DPP_XOR2>(v); v += pcr_dpp_i<PCR_DPP_HMIRROR>(v);
     return v;

@@ -58,19 +58,11 @@ struct KwShared {
     KwStack stk;
 };
 
-__device__ static inline float kw_octet_fmin(float v) {
-    v = fminf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fminf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
-    return v;
-}
-__device__ static inline float kw_octet_fmax(float v) {
-    v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR1>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_XOR2>(v)); v = fmaxf(v, pcr_dpp_f<PCR_DPP_HMIRROR>(v));
-    return v;
-}
 __device__ static inline float kw_wave_fmin(float v) {
-    return pcr_xoct_min(kw_octet_fmin(v));             // (across the octets inside the VALU: row_ror:8 + the permlane swaps of gfx950, no ds_bpermute)
+    return pcr_xoct_min(pcr_octet_minf(v));             // (across the octets inside the VALU: row_ror:8 + the permlane swaps of gfx950, no ds_bpermute)
 }
 __device__ static inline float kw_wave_fmax(float v) {
-    return pcr_xoct_max(kw_octet_fmax(v));
+    return pcr_xoct_max(pcr_octet_maxf(v));
 }
 // squared distance between two boxes, same operation order as pcr_box_d2 (monotone: never above the box distance of a point inside g)
 __device__ static inline float kw_boxbox_d2(const float4 lo, const float4 hi, const float *glo, const float *ghi) {
@@ -99,7 +91,7 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
     float sghi[3] = {live ? qx : -3.4e38f, live ? qy : -3.4e38f, live ? qz : -3.4e38f};
     float glo[3], ghi[3];
 #pragma unroll
-    for (int d = 0; d < 3; d++) { sglo[d] = kw_octet_fmin(sglo[d]); sghi[d] = kw_octet_fmax(sghi[d]); }
+    for (int d = 0; d < 3; d++) { sglo[d] = pcr_octet_minf(sglo[d]); sghi[d] = pcr_octet_maxf(sghi[d]); }
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         glo[d] = pcr_xoct_min(sglo[d]); ghi[d] = pcr_xoct_max(sghi[d]);
@@ -512,8 +504,7 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
 
 // 4 wavefronts per SIMD up to K = 32 (128 VGPRs, 18 spilled; in the default bench, groups of 6 x 4 in flight: 3 wavefronts, 144 VGPRs and no
 // spill 617 pairs/s, 4 wavefronts 643, 5 wavefronts, 96 VGPRs and 64 spilled 588)
-#define KW_OCC(K) __attribute__((amdgpu_waves_per_eu(K <= 32 ? 4 : 2, K <= 32 ? 4 : 3)))
-template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave(KnnArgs a) { d_knn_wave<MODE, K>(a); }
-template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_batch(KnnBatch b) { d_knn_wave<MODE, K>(b.a[blockIdx.y]); }
-// (device-pointer form: the body inlined by force, as in k_knn_batchp)
-template <int MODE, int K> __global__ void __launch_bounds__(KW_BS) KW_OCC(K) k_knn_wave_batchp(const KnnArgs *a) { [[clang::always_inline]] d_knn_wave<MODE, K>(a[blockIdx.y]); }
+template <int MODE, int K> struct OpKnnWave : PcrOp<KnnArgs, KW_BS> {
+    static constexpr int kWavesMin = K <= 32 ? 4 : 2, kWavesMax = K <= 32 ? 4 : 3;
+    __device__ static inline void run(const KnnArgs &a) { [[clang::always_inline]] d_knn_wave<MODE, K>(a); }
+};

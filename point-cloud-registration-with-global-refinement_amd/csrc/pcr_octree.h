@@ -22,6 +22,7 @@
 // return as one byte of a wave ballot; pending siblings live in a per-octet LDS stack (<= 16 levels).
 #pragma once
 #include "pcr_device.h"
+#include "pcr_batch.h"
 
 #define OCT 8
 #define OCT_MAXL 16          // stored levels (leaf level .. root)
@@ -49,6 +50,10 @@ struct OctView {             // what a kernel needs to walk a tree
                              // (the leaf when the tree has one level) -- the "fat leaf" a warm-started search scans first
     const int2 *l1rng;       // level-1 node -> (first point, point count)
 };
+static inline OctView oct_view(const DevCloud *c) {
+    OctView v; v.pts = c->pts; v.nodes = c->oct_nodes; v.up = c->oct_up; v.meta = c->oct_meta; v.leaf_of = c->leaf_of; v.keys = c->keys; v.pinfo = c->pinfo; v.l1rng = c->oct_l1;
+    return v;
+}
 
 __host__ __device__ static inline uint32_t pcr_compact21(uint64_t x) {
     x &= 0x1249249249249249ull;

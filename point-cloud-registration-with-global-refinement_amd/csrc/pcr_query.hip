@@ -11,11 +11,6 @@
 #define QRY_BS 256
 #define QRY_FAR 3.4e38f
 
-static inline OctView qry_view(const DevCloud *c) {
-    OctView v; v.pts = c->pts; v.nodes = c->oct_nodes; v.up = c->oct_up; v.meta = c->oct_meta; v.leaf_of = c->leaf_of; v.keys = c->keys; v.pinfo = c->pinfo; v.l1rng = c->oct_l1;
-    return v;
-}
-
 // distance of two float32 points in float64: differences, products and sums rounded one by one (no fused multiply-add), so that the
 // value is the one a host recomputation in the same order gives, bit for bit
 __device__ static inline double qry_dist_f64(float qx, float qy, float qz, const float4 p) {
@@ -85,7 +80,7 @@ __global__ void __launch_bounds__(QRY_BS) k_nn_distance(NnDistArgs a) {
 
 static int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, double *dist_caller) {
     if (c->cap <= 0) return PCR_OK;
-    NnDistArgs a; a.t = qry_view(c); a.perm = perm; a.dist = dist_caller;
+    NnDistArgs a; a.t = oct_view(c); a.perm = perm; a.dist = dist_caller;
     PCR_LAUNCH(ctx, k_nn_distance, dim3((unsigned)(((size_t)c->cap * OCT + QRY_BS - 1) / QRY_BS)), dim3(QRY_BS), 0, ctx->stream, a);
     return PCR_OK;
 }
@@ -146,7 +141,7 @@ __global__ void __launch_bounds__(QRY_BS) k_cloud_distance(CloudDistArgs a) {
 
 static int pcr_dev_cloud_distance(pcr_context *ctx, const float *src_xyz, int64_t n_src, const DevCloud *tgt, const uint32_t *tgt_perm, double *dist, int32_t *nearest) {
     if (n_src <= 0 || tgt->cap <= 0) return PCR_OK;
-    CloudDistArgs a; a.t = qry_view(tgt); a.perm = tgt_perm; a.src = src_xyz; a.n_src = (int)n_src; a.dist = dist; a.nearest = nearest;
+    CloudDistArgs a; a.t = oct_view(tgt); a.perm = tgt_perm; a.src = src_xyz; a.n_src = (int)n_src; a.dist = dist; a.nearest = nearest;
     PCR_LAUNCH(ctx, k_cloud_distance, dim3((unsigned)(((size_t)n_src * OCT + QRY_BS - 1) / QRY_BS)), dim3(QRY_BS), 0, ctx->stream, a);
     return PCR_OK;
 }
@@ -192,7 +187,7 @@ __global__ void __launch_bounds__(QRY_BS) k_radius_count(RadCountArgs a) {
 
 static int pcr_dev_radius_count(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, int nb_points, double radius, uint8_t *keep_caller) {
     if (c->cap <= 0) return PCR_OK;
-    RadCountArgs a; a.t = qry_view(c); a.perm = perm; a.r2 = radius * radius; a.r2f = (float)(a.r2 * (1.0 + 1e-6)); a.nb_points = nb_points; a.keep = keep_caller;
+    RadCountArgs a; a.t = oct_view(c); a.perm = perm; a.r2 = radius * radius; a.r2f = (float)(a.r2 * (1.0 + 1e-6)); a.nb_points = nb_points; a.keep = keep_caller;
     PCR_LAUNCH(ctx, k_radius_count, dim3((unsigned)(((size_t)c->cap * OCT + QRY_BS - 1) / QRY_BS)), dim3(QRY_BS), 0, ctx->stream, a);
     return PCR_OK;
 }

@@ -135,6 +135,46 @@ def test_knn_wave_equals_octet(P, small_pair, knn_form, k, radius, n):
         assert len(set(v.tolist())) == len(v)
 
 
+def _strided(small_pair, n):
+    """n distinct points of the source scan, evenly strided over the file."""
+    src = small_pair["source"].astype(np.float32)
+    return src[np.linspace(0, len(src) - 1, n).astype(np.int64)].copy()
+
+
+@pytest.mark.parametrize("n", [1, 7, 65, 300])
+@pytest.mark.parametrize("k", [33, 65, 200])
+def test_knn_octet_wide_slots_are_exact(P, oracle, small_pair, knn_form, k, n):
+    """The octet kernel with 8 and 25 register slots per lane (k > 32, k > 64) runs as a batch of one: its rows against the oracle's
+    exact search on clouds of fewer points than one octet, of one wavefront of queries plus one, and of fewer points than k.  On these
+    inputs the oracle's k-th and (k+1)-th distances differ by at least 1.6e-6 relative (13 float32 ulps; the float32 d^2 is good to 3)
+    and no row holds two equal distances, so the k-best SETS must be equal; empty slots are (-1, inf)."""
+    knn_form(0)
+    pts = _strided(small_pair, n)
+    idx, d2, cnt = _debug_knn(P, pts, k)
+    ridx, rd2, rcnt = oracle.knn(pts, pts, k)
+    m = min(k, n)
+    assert (rcnt == m).all() and (cnt == m).all()
+    order = np.lexsort((idx, d2), axis=1)                     # device rows are an unordered k-best set; inf (empty) sorts last
+    idx = np.take_along_axis(idx, order, 1); d2 = np.take_along_axis(d2, order, 1)
+    assert (idx[:, m:] == -1).all() and np.isinf(d2[:, m:]).all()
+    assert np.allclose(d2[:, :m], rd2[:, :m], rtol=2e-6, atol=1e-12)
+    assert np.array_equal(np.sort(idx[:, :m], axis=1), np.sort(ridx[:, :m], axis=1))
+
+
+def test_normals_knn65_match_oracle_on_300_points(P, oracle, small_pair, knn_form):
+    """estimate_normals with knn = 65 (the 25-slot octet kernel, one cloud = a batch of one) against the oracle, at the tolerance of
+    test_normals_knn_match_oracle."""
+    knn_form(0)
+    pts = _strided(small_pair, 300)
+    pc = P.PointCloud(pts)
+    pc.estimate_normals(P.KDTreeSearchParamKNN(knn=65))
+    ref = oracle.estimate_normals(pc.points, oracle.SEARCH_KNN, 65)
+    dots = (pc.normals * ref).sum(1)
+    print("knn65 normals: min dot", dots.min(), "below 1 - 1e-5:", (dots < 1 - 1e-5).sum())
+    assert (dots > 1 - 1e-5).mean() > 0.999, (dots < 1 - 1e-5).sum()
+    assert (np.abs(dots) > 1 - 1e-3).mean() > 0.9999
+
+
 def test_knn_wave_hands_hard_wavefronts_to_the_octet_kernel(P, oracle, small_pair, knn_form):
     """A wavefront of the one-query-per-lane search gives up after `knnw_budget` candidate batches and leaves its 64 queries to the octet
     kernel (default 40 batches: ~1 % of the wavefronts).  With a budget of 3 most wavefronts give up, with 8 about half: the outlier

@@ -46,7 +46,7 @@ for pass in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 4 --inflight 1 --group 1 > "$d.log" 2> "$d.err" || exit 1
   echo "pmc pass [$pass] done"
 done
-# the same three passes on the DEFAULT path (lockstep groups of six: k_knn_wave_batchp, k_icp_fused_b<1024>), 12 pairs per step
+# the same three passes on the DEFAULT path (lockstep groups of six: k_batch_pointer<OpKnnWave>, k_icp_fused_b<1024>), 12 pairs per step
 for pass in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   d=$OUT/pmcg_$(echo $pass | tr ' ' '_')
   rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --pairs-per-step 12 --inflight 2 > "$d.log" 2> "$d.err" || exit 1
@@ -55,18 +55,18 @@ done
 python3 - "$OUT" "$ROOT/profiles/${TAG}" <<'PY'
 import csv, glob, json, sys, collections
 out, dst = sys.argv[1], sys.argv[2]
-def norm(name):                      # whatever the tile, the search form and the argument form
+def norm(name):                      # whatever the tile, the search form and the argument form.  The cloud stages are the entry points of pcr_batch.h,
+                                     # k_batch_value<Op> (argument structs by value) and k_batch_pointer<Op> (by pointer); the labels are the ones the tracked files use
     if "k_icp_fused" in name: return "k_icp_fused"
     if name.startswith("void k_icp_nn<") or name.startswith("k_icp_nn("): return "k_icp_nn"
     if "k_icp_nn_g" in name: return "k_icp_nn_g"
     if "k_icp_lin_g" in name: return "k_icp_lin_g"
-    if "k_normals_from_lists_batchp" in name: return "k_normals_from_lists_batchp"
-    if name.startswith("void k_knn_wave_batchp<0, 30>"): return "k_knn_wave_batchp<SOR,30>"
-    if name.startswith("void k_knn_list_batchp<0, 4>"): return "k_knn_list_batchp<SOR,4>"
-    if name.startswith("void k_knn_batchp<1, 4>"): return "k_knn_batchp<NORMALS,4>"
-    if name.startswith("void k_knn_list_batchp<1, 4>"): return "k_knn_list_batchp<NORMALS,4>"
-    return {"void k_icp_iter<0>(IcpArgs)": "k_icp_iter<GICP>", "void k_knn_batch<0, 4>(KnnBatch)": "k_knn_batch<SOR,4>", "void k_knn_batch<1, 4>(KnnBatch)": "k_knn_batch<NORMALS,4>",
-            "k_normals_from_lists_batch(NflBatch)": "k_normals_from_lists_batch", "k_grid_build(GridBuildDesc const*)": "k_grid_build"}.get(name, name.split("(")[0])
+    for op, label in (("k_batch_pointer<OpNormalsFromLists>", "k_normals_from_lists_batchp"), ("k_batch_pointer<OpKnnWave<0, 30>", "k_knn_wave_batchp<SOR,30>"),
+                      ("k_batch_pointer<OpKnn<0, 4, true>", "k_knn_list_batchp<SOR,4>"), ("k_batch_pointer<OpKnn<1, 4, false>", "k_knn_batchp<NORMALS,4>"),
+                      ("k_batch_pointer<OpKnn<1, 4, true>", "k_knn_list_batchp<NORMALS,4>"), ("k_batch_value<OpKnn<0, 4, false>", "k_knn_batch<SOR,4>"),
+                      ("k_batch_value<OpKnn<1, 4, false>", "k_knn_batch<NORMALS,4>"), ("k_batch_value<OpNormalsFromLists>", "k_normals_from_lists_batch")):
+        if op in name: return label
+    return {"void k_icp_iter<0>(IcpArgs)": "k_icp_iter<GICP>", "k_grid_build(GridBuildDesc const*)": "k_grid_build"}.get(name, name.split("(")[0])
 def load(pat):
     f = glob.glob(f"{out}/{pat}/**/*counter_collection.csv", recursive=True)[0]
     d = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -108,7 +108,8 @@ f = glob.glob(f"{out}/pmc_valu/**/*counter_collection.csv", recursive=True)[0]
 d = collections.defaultdict(lambda: collections.defaultdict(list))
 for r in csv.DictReader(open(f)):
     d[r["Kernel_Name"]][r["Counter_Name"]].append((float(r["Counter_Value"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
-npairs = max(1.0, len(d["void k_knn_batch<0, 4>(KnnBatch)"]["SQ_INSTS_VALU"]) / 2)          # two batched SOR searches per pair
+sor = [k for k in d if "k_batch_value<OpKnn<0, 4, false>" in k]                              # the octet 30-NN search of the outlier filter, argument structs by value
+npairs = max(1.0, len(d[sor[0]]["SQ_INSTS_VALU"]) / 2 if sor else 1.0)                       # two batched SOR searches per pair
 rows = sorted(((sum(x[0] for x in v["SQ_INSTS_VALU"]), k, len(v["SQ_INSTS_VALU"]), sum(x[1] for x in v["SQ_INSTS_VALU"])) for k, v in d.items()), reverse=True)
 tot = sum(r[0] for r in rows)
 PEAK = 256 * 4 * 2400 / 4.0                                                                  # wave64 VALU instructions per us: 1024 SIMDs, 4 cycles each at 2.4 GHz -- the MEASURED rate of
