@@ -179,6 +179,28 @@ int pcr_remove_radius_outlier(pcr_context *ctx, const float *xyz, int64_t n, int
  * NULL (get_center): the mean alone, the same bits, in one pass over the points instead of two. */
 int pcr_mean_and_covariance(pcr_context *ctx, const float *xyz, int64_t n, double *mean3, double *cov9);
 
+/* == geometry.keypoint.compute_iss_keypoints (Open3D ComputeISSKeypoints, cpp/open3d/geometry/Keypoint.cpp; not called by the reference scripts,
+ * the usual stage in front of a global registration).  Per point i: the neighbourhood with d^2 < salient_radius^2 (point i included, the test
+ * strict, d^2 in float64 on the float32 coordinates: the rule of the other radius calls); fewer than min_neighbors members, or an all-zero
+ * covariance, give saliency 0; otherwise l1 >= l2 >= l3 are the eigenvalues of the members' covariance (divided by their count, float64) and
+ * the saliency is l3 when l2 / l1 < gamma_21 and l3 / l2 < gamma_32, else 0.  A point with saliency > 0 is a keypoint when its neighbourhood
+ * at non_max_radius has at least min_neighbors members and none of them suppresses it.
+ *   SUPPRESSION (a deliberate deviation): member j suppresses point i iff s_j > s_i + G with G = 1e-11 salient_radius^2; Open3D tests
+ *   s_j > s_i.  Points with the same neighbourhood have the same saliency in exact arithmetic and Open3D keeps all of them on the exact tie;
+ *   float64 sums taken in another order differ in the last bits (at most about 1e-12 salient_radius^2), and the strict test would then drop
+ *   one of such a pair at random.  G is about 1e-7 of a typical l3.
+ *   DEFAULT RADII: if salient_radius == 0 or non_max_radius == 0, BOTH are replaced (Open3D): resolution = the mean over all points of
+ *   pcr_nearest_neighbor_distance (summed in float64 in a fixed order), salient_radius = 6 resolution, non_max_radius = 4 resolution.
+ * Negative or non-finite radii, min_neighbors < 1, a non-finite gamma, a null cloud with n > 0: PCR_EINVAL.  n == 0: *out_n = 0.
+ * Device, each optional: keep_mask (n bytes), out_xyz (capacity n x 3), out_index (capacity n int64, ascending: the layout of
+ * pcr_remove_radius_outlier; Open3D's own order depends on its thread schedule), saliency (n float64, caller order), eigenvalues3 (n x 3 float64,
+ * descending; zeros where the neighbourhood was too small).  Host: out_n, radii_used2 (optional: the salient and the non-max radius used).
+ * Two runs give the same bits.                                                                                                          */
+int pcr_iss_keypoints(pcr_context *ctx, const float *xyz, int64_t n, double salient_radius, double non_max_radius,
+                      double gamma_21, double gamma_32, int min_neighbors,
+                      uint8_t *keep_mask, float *out_xyz, int64_t *out_index, int64_t *out_n,
+                      double *saliency, double *eigenvalues3, double *radii_used2);
+
 /* ---- registration ------------------------------------------------------------------ */
 /* == registration_generalized_icp (ALL_FUNCTIONS.py:304-311; 2_MGICP...py:155-162).
  * correspondences optional device int32 [n_src x 2]; filled with n_correspondences rows.       */

@@ -352,3 +352,38 @@ class PointCloud:
                 C3 = R @ C3 @ R.T
                 self._cov = torch.stack([C3[:, 0, 0], C3[:, 0, 1], C3[:, 0, 2], C3[:, 1, 1], C3[:, 1, 2], C3[:, 2, 2]], 1).float().contiguous()
         return self
+
+
+# ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
+def _iss_keypoints(input: PointCloud, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """``pcr_iss_keypoints`` with every output -> ``(indices (torch int64, device, ascending), mask (n,) bool, saliency (n,) float64,
+    eigenvalues (n, 3) float64 descending, (salient radius, non-max radius) used)``; the arrays on the host."""
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n = len(input)
+    keep = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    idx = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+    sal = torch.zeros(max(n, 1), dtype=torch.float64, device="cuda")
+    eig = torch.zeros((max(n, 1), 3), dtype=torch.float64, device="cuda")
+    m = C.c_int64(0)
+    radii = (C.c_double * 2)()
+    ctx.check(ctx.lib.pcr_iss_keypoints(ctx.handle, _ptr(input.device_xyz()), C.c_int64(n), C.c_double(salient_radius), C.c_double(non_max_radius),
+                                        C.c_double(gamma_21), C.c_double(gamma_32), C.c_int(int(min_neighbors)), _ptr(keep), None, _ptr(idx),
+                                        C.byref(m), _ptr(sal), _ptr(eig), radii), "compute_iss_keypoints")
+    return idx[: m.value], keep[:n].cpu().numpy().astype(bool), sal[:n].cpu().numpy(), eig[:n].cpu().numpy(), (float(radii[0]), float(radii[1]))
+
+
+def iss_keypoint_indices(input: PointCloud, salient_radius: float = 0.0, non_max_radius: float = 0.0, gamma_21: float = 0.975,
+                         gamma_32: float = 0.975, min_neighbors: int = 5) -> np.ndarray:
+    """The rows ``compute_iss_keypoints`` selects, int64, ascending: what picks the feature rows of the keypoints
+    (``Feature.select_by_index``) next to ``input.select_by_index``."""
+    return _iss_keypoints(input, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)[0].cpu().numpy()
+
+
+def compute_iss_keypoints(input: PointCloud, salient_radius: float = 0.0, non_max_radius: float = 0.0, gamma_21: float = 0.975,
+                          gamma_32: float = 0.975, min_neighbors: int = 5) -> PointCloud:
+    """``o3d.geometry.keypoint.compute_iss_keypoints``: the ISS keypoints of ``input`` as a cloud (normals, colours and covariances
+    travel with the points, in the input's order).  With either radius 0 both come from the cloud's resolution (6 x and 4 x the mean
+    nearest-neighbour distance).  A neighbour suppresses a point only when its saliency is larger by more than
+    ``1e-11 salient_radius**2`` (include/pcr_hip.h): points that share one neighbourhood are all kept, as Open3D keeps them on an exact tie."""
+    return input.select_by_index(_iss_keypoints(input, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)[0])

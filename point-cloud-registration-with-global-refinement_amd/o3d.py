@@ -19,7 +19,8 @@ def _read_point_cloud(path):
 
 geometry = SimpleNamespace(PointCloud=_g.PointCloud, KDTreeSearchParamKNN=_g.KDTreeSearchParamKNN,
                            KDTreeSearchParamRadius=_g.KDTreeSearchParamRadius,
-                           KDTreeSearchParamHybrid=_g.KDTreeSearchParamHybrid)
+                           KDTreeSearchParamHybrid=_g.KDTreeSearchParamHybrid,
+                           keypoint=SimpleNamespace(compute_iss_keypoints=_g.compute_iss_keypoints))
 utility = SimpleNamespace(Vector3dVector=lambda a: _np.asarray(a, dtype=_np.float64).reshape(-1, 3))
 io = SimpleNamespace(read_point_cloud=_read_point_cloud)
 pipelines = SimpleNamespace(registration=_r)

@@ -132,6 +132,18 @@ class Feature:
     def num(self):
         return int(self._dev.shape[0])
 
+    def select_by_index(self, indices, invert: bool = False) -> "Feature":
+        """``Feature.select_by_index`` (Open3D >= 0.18): the feature rows of the points ``indices``, in that order -- a gather on the
+        device, like ``PointCloud.select_by_index``; ``invert`` keeps the other rows in their order."""
+        torch = _torch()
+        idx = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices, dtype=np.int64), device="cuda")
+        idx = idx.to(device="cuda", dtype=torch.int64).reshape(-1)
+        if invert:
+            mask = torch.ones(self.num(), dtype=torch.bool, device="cuda")
+            mask[idx] = False
+            idx = torch.nonzero(mask).reshape(-1)
+        return Feature(self._dev[idx].contiguous())
+
 
 def _params(estimation, criteria) -> _lib.PcrGicpParams:
     return _lib.PcrGicpParams(int(estimation.kernel.kind), float(estimation.kernel.k), float(estimation.epsilon),
