@@ -201,6 +201,28 @@ int pcr_iss_keypoints(pcr_context *ctx, const float *xyz, int64_t n, double sali
                       uint8_t *keep_mask, float *out_xyz, int64_t *out_index, int64_t *out_n,
                       double *saliency, double *eigenvalues3, double *radii_used2);
 
+/* == PointCloud.cluster_dbscan (Open3D PointCloud::ClusterDBSCAN, cpp/open3d/geometry/PointCloudCluster.cpp; not called by the reference scripts,
+ * the usual stage between the outlier filters and a registration).  Open3D's sequential flood fill gives a result that the input alone
+ * determines; these six rules restate it, and the labels are Open3D's row by row, not a renaming of them:
+ *   1. NEIGHBOURHOOD: j is a neighbour of i iff d^2(i, j) < eps^2 -- strict, in float64 on the float32 coordinates, the point itself a member
+ *      (the test of pcr_remove_radius_outlier and pcr_iss_keypoints).  d^2 = dx dx, += dy dy, += dz dz, every difference, square and sum
+ *      rounded on its own (no fused multiply-add): a host recomputation in that order gives the same bits, so an exact tie d^2 == eps^2 is
+ *      decided (not a neighbour).  eps^2 is the float64 product eps * eps.
+ *   2. CORE: i is a core point iff its neighbourhood, itself included, has at least min_points members.
+ *   3. CLUSTERS: the connected components of the graph on the core points whose edges are the core-core neighbour pairs.
+ *   4. NUMBERING: clusters are numbered 0, 1, ... in ascending order of the smallest CALLER index among their core points (Open3D seeds a
+ *      cluster at the first unvisited core point in index order; the smallest-index core point of a component cannot have been reached
+ *      from an earlier seed).
+ *   5. BORDER: a non-core point with at least one core neighbour gets the SMALLEST label among its core neighbours' clusters (Open3D's flood
+ *      fills run in label order and relabel a point only from "unvisited" or "noise": the first cluster to reach the point keeps it).
+ *   6. NOISE: every other point gets -1.
+ * (sklearn.cluster.DBSCAN follows rules 2-6 with d <= eps.)
+ * Device: xyz, labels (n int32, caller order), core_mask (optional, n bytes: 1 = core point).  Host: out_n_clusters (optional; without it the
+ * call does not wait for the device).  n < 0 or over the int limit, a null xyz or labels with n > 0, eps not finite or <= 0,
+ * min_points < 1: PCR_EINVAL with a message.  n == 0: PCR_OK and 0 clusters.  Two runs give the same labels.                      */
+int pcr_cluster_dbscan(pcr_context *ctx, const float *xyz, int64_t n, double eps, int min_points,
+                       int32_t *labels, uint8_t *core_mask, int64_t *out_n_clusters);
+
 /* ---- registration ------------------------------------------------------------------ */
 /* == registration_generalized_icp (ALL_FUNCTIONS.py:304-311; 2_MGICP...py:155-162).
  * correspondences optional device int32 [n_src x 2]; filled with n_correspondences rows.       */

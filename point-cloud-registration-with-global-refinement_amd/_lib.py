@@ -100,10 +100,10 @@ EXPORTS = [
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
-    "pcr_iss_keypoints",
+    "pcr_iss_keypoints", "pcr_cluster_dbscan",
 ]
 
-# prototypes of the cloud queries and the keypoint detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector and the clustering (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -112,6 +112,7 @@ QUERY_PROTOTYPES = {
     "pcr_mean_and_covariance": ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
     "pcr_iss_keypoints": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)], C.c_int),
+    "pcr_cluster_dbscan": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)], C.c_int),
 }
 
 _lib = None

@@ -131,6 +131,19 @@ def knn_distance_table(pc1, pc2):
     return [(pc.compute_nearest_neighbor_distance(), label) for pc, label in zip((pc1, pc2), KNN_DISTANCE_LABELS)]
 
 
+def remove_small_clusters(cloud, eps, min_points, min_cluster_size):
+    """DBSCAN (``cluster_dbscan(eps, min_points)``) as a filter, not in the reference: keeps the points whose cluster has at least
+    ``min_cluster_size`` members -- the large static structures of a scan, without the small movable ones -- and drops the noise.  Returns
+    ``(PointCloud, indices)``; the indices are a device int64 tensor, ascending.  Labels, counts and selection stay on the device."""
+    import torch
+    labels, _, n_clusters = _g._cluster_dbscan(cloud, eps, min_points)
+    labels = labels.long()
+    sizes = torch.bincount(labels[labels >= 0], minlength=max(n_clusters, 1))
+    keep = (labels >= 0) & (sizes[labels.clamp(min=0)] >= int(min_cluster_size))
+    indices = torch.nonzero(keep).reshape(-1)
+    return cloud.select_by_index(indices), indices
+
+
 # ------------------------------------------------------------------------------------ script variants
 class script1:
     """Private copies in 1_FGR_pairwise_registration_in_NCLT_dataset.py."""

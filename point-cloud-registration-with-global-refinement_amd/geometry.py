@@ -234,6 +234,12 @@ class PointCloud:
         index = idx[: m.value]
         return self.select_by_index(index), index.cpu().numpy().tolist()
 
+    def cluster_dbscan(self, eps: float, min_points: int, print_progress: bool = False):
+        """``PointCloud.cluster_dbscan``: the DBSCAN label of every point, numpy int32 of length n (Open3D returns an ``IntVector`` that users
+        wrap in ``np.asarray``); -1 is noise, clusters are numbered from 0 in the order of their first core point.  The labels are Open3D's,
+        row by row (the rules: include/pcr_hip.h).  ``print_progress`` is accepted and ignored."""
+        return _cluster_dbscan(self, eps, min_points)[0].cpu().numpy()
+
     def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
         """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
         if every_k_points < 1:
@@ -352,6 +358,20 @@ class PointCloud:
                 C3 = R @ C3 @ R.T
                 self._cov = torch.stack([C3[:, 0, 0], C3[:, 0, 1], C3[:, 0, 2], C3[:, 1, 1], C3[:, 1, 2], C3[:, 2, 2]], 1).float().contiguous()
         return self
+
+
+def _cluster_dbscan(cloud: PointCloud, eps: float, min_points: int):
+    """``pcr_cluster_dbscan`` -> ``(labels (n,) torch int32 on the device, core mask (n,) torch bool on the device, number of clusters)``:
+    the form a pipeline that stays on the device builds on (``functions.remove_small_clusters``)."""
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n = len(cloud)
+    labels = torch.full((max(n, 1),), -1, dtype=torch.int32, device="cuda")
+    core = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    m = C.c_int64(0)
+    ctx.check(ctx.lib.pcr_cluster_dbscan(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), C.c_double(eps), C.c_int(int(min_points)), _ptr(labels),
+                                         _ptr(core), C.byref(m)), "cluster_dbscan")
+    return labels[:n], core[:n].bool(), int(m.value)
 
 
 # ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
