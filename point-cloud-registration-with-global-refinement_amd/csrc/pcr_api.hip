@@ -268,6 +268,19 @@ __global__ void k_emit_kept(const float *__restrict__ xyz, const uint8_t *__rest
     if (out_xyz) { out_xyz[o * 3] = xyz[i * 3]; out_xyz[o * 3 + 1] = xyz[i * 3 + 1]; out_xyz[o * 3 + 2] = xyz[i * 3 + 2]; }
     if (out_index) out_index[o] = i;
 }
+// tail of the calls that select rows by a mask in caller order: the kept rows ascending (select_by_index semantics) and their count
+int pcr_emit_kept_rows(pcr_context *ctx, const float *xyz, int64_t n, const uint8_t *keep_caller, float *out_xyz, int64_t *out_index, int64_t *out_n) {
+    int *pos = arena<int>(ctx, n);
+    int *total = arena<int>(ctx, 1);
+    if (!pos || !total) return PCR_ENOMEM;
+    PCR_TRY(pcr_dev_flag_scan(ctx, keep_caller, nullptr, (int)n, pos, total));
+    if (out_xyz || out_index)
+        PCR_LAUNCH(ctx, k_emit_kept, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, xyz, keep_caller, (const int *)pos, (int)n, out_xyz, out_index);
+    int64_t kept = 0;
+    PCR_TRY(pcr_read_count(ctx, total, &kept));
+    if (out_n) *out_n = kept;
+    return PCR_OK;
+}
 
 extern "C" int pcr_remove_statistical_outlier(pcr_context *ctx, const float *xyz, int64_t n, int nb_neighbors, double std_ratio,
                                               uint8_t *keep_mask, float *out_xyz, int64_t *out_index, int64_t *out_n) {
@@ -282,19 +295,10 @@ extern "C" int pcr_remove_statistical_outlier(pcr_context *ctx, const float *xyz
     PCR_TRY(pcr_alloc_cloud(ctx, &kept, (int)n, false, false));
     uint8_t *keep_sorted = arena<uint8_t>(ctx, n);
     uint8_t *keep_caller = keep_mask ? keep_mask : arena<uint8_t>(ctx, n);
-    int *pos = arena<int>(ctx, n);
-    int *total = arena<int>(ctx, 1);
-    if (!keep_sorted || !keep_caller || !pos || !total) return PCR_ENOMEM;
+    if (!keep_sorted || !keep_caller) return PCR_ENOMEM;
     PCR_TRY(pcr_dev_sor(ctx, &c, nb_neighbors, std_ratio, &kept, keep_sorted, nullptr));
-    const int nb = (int)((n + 255) / 256);
-    PCR_LAUNCH(ctx, k_keep_to_caller, dim3(nb), dim3(256), 0, ctx->stream, keep_sorted, perm, (int)n, keep_caller);
-    // emit the kept points in CALLER order (select_by_index semantics)
-    PCR_TRY(pcr_dev_flag_scan(ctx, keep_caller, nullptr, (int)n, pos, total));
-    if (out_xyz || out_index) PCR_LAUNCH(ctx, k_emit_kept, dim3(nb), dim3(256), 0, ctx->stream, xyz, keep_caller, pos, (int)n, out_xyz, out_index);
-    int64_t m = 0;
-    PCR_TRY(pcr_read_count(ctx, total, &m));
-    if (out_n) *out_n = m;
-    return PCR_OK;
+    PCR_LAUNCH(ctx, k_keep_to_caller, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, keep_sorted, perm, (int)n, keep_caller);
+    return pcr_emit_kept_rows(ctx, xyz, n, keep_caller, out_xyz, out_index, out_n);
     });
 }
 

@@ -1251,7 +1251,7 @@ static int launch_knn_each(pcr_context *ctx, KnnArgs *a, const int *caps, int co
 static void knn_radius(KnnArgs &a, int search_kind, double radius) {
     if (search_kind == PCR_SEARCH_HYBRID && radius > 0) {
         a.r2cap = radius * radius;
-        a.r2cap_f = (float)(a.r2cap * (1.0 + 1e-6));     // float32 walk slightly wide, exact float64 test in the epilogue
+        a.r2cap_f = pcr_wide_r2f(a.r2cap);               // float32 walk slightly wide, exact float64 test in the epilogue
     } else { a.r2cap = 1e300; a.r2cap_f = 3.4e38f; }
 }
 
@@ -1265,45 +1265,25 @@ int pcr_dev_knn_debug(pcr_context *ctx, const DevCloud *c, int k, double radius,
 }
 
 // ============================================================== pure radius neighbourhoods (KDTreeSearchParamRadius)
-// All points with d^2 < r^2 contribute to the moments directly (no k-best): same shared walk, fixed bound.
+// All points with d^2 < r^2 contribute to the moments directly (no k-best): the fixed-radius walk of pcr_octree.h, every query to its end.
 struct RadArgs {
     OctView t; const int *n_ptr; float r2f; double r2;
     const float4 *prior; float4 *normals; float *cov6;
 };
 __global__ void __launch_bounds__(KNN_BS) k_radius_moments(RadArgs a) {
-    constexpr int OPB = KNN_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[KNN_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
-    const double qx = q.x, qy = q.y, qz = q.z;
+    oct_group_frame<KNN_BS>(a.t, [&](const OctGroupQuery &g) {
+    const int qi = g.qi, ol = g.ol; const bool live = g.live;
     double cu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, c = 0;
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (live && idx < first + count) {
-                const float4 p = a.t.pts[idx];
-                if (pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < a.r2f) {
-                    const double x = p.x, y = p.y, z = p.z;
-                    const double dx = x - qx, dy = y - qy, dz = z - qz;
-                    if (dx * dx + dy * dy + dz * dz < a.r2) {
-                        cu[0] += x; cu[1] += y; cu[2] += z;
-                        cu[3] += x * x; cu[4] += x * y; cu[5] += x * z; cu[6] += y * y; cu[7] += y * z; cu[8] += z * z;
-                        c += 1.0;
-                    }
-                }
-            }
+    // active = live: every query walks to its end
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return live; }, [&](int idx) {
+        const float4 p = a.t.pts[idx];
+        if (oct_ball_member<false>(g.q, p, a.r2f, a.r2)) {
+            const double x = p.x, y = p.y, z = p.z;
+            cu[0] += x; cu[1] += y; cu[2] += z;
+            cu[3] += x * x; cu[4] += x * y; cu[5] += x * z; cu[6] += y * y; cu[7] += y * z; cu[8] += z * z;
+            c += 1.0;
         }
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return a.r2f; }, visit,
-                     [](int, int) { return false; }, ol);
+    });
 #pragma unroll
     for (int t = 0; t < 9; t++) cu[t] = pcr_octet_sum(cu[t]);
     c = pcr_octet_sum(c);
@@ -1326,6 +1306,7 @@ __global__ void __launch_bounds__(KNN_BS) k_radius_moments(RadArgs a) {
             a.normals[qi] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.0f);
         }
     }
+    });
 }
 
 // ============================================== neighbour lists under a radius cap (the Hybrid(r, max_nn) lists of FPFH, round 4)
@@ -1353,15 +1334,6 @@ struct RadListArgs {
 // the k-th place of its rows by the same (float64 d^2, caller index) rule: the lists are the same set on every path.
 #define RL_BINS 128            // (two 16-bit counters per LDS word; a ball of more than 0xffff points is the k-best kernel's)
 #define RL_EDGE 20
-// squared distance as the reference's k-d tree forms it (float64 differences of the float32 coordinates, products and sums rounded one by one)
-__device__ static inline double pcr_d2_f64_unfused(const float4 q, const float4 p) {
-#pragma clang fp contract(off)
-    const double ex = (double)q.x - (double)p.x, ey = (double)q.y - (double)p.y, ez = (double)q.z - (double)p.z;
-    double d2 = ex * ex;
-    d2 += ey * ey;
-    d2 += ez * ez;
-    return d2;
-}
 __device__ static inline void d_radius_list(const RadListArgs &a) {
     constexpr int OPB = KNN_BS / OCT;
     __shared__ OctMeta m;
@@ -1994,7 +1966,7 @@ int pcr_dev_normals(pcr_context *ctx, DevCloud *c, int search_kind, int knn, dou
         if (!(radius > 0)) { ctx->err = "radius <= 0"; return PCR_EINVAL; }
         if (c->cap <= 0) return PCR_OK;
         RadArgs r;
-        r.t = oct_view(c); r.n_ptr = c->n; r.r2 = radius * radius; r.r2f = (float)(r.r2 * (1.0 + 1e-6));
+        r.t = oct_view(c); r.n_ptr = c->n; r.r2 = radius * radius; r.r2f = pcr_wide_r2f(r.r2);
         r.prior = prior; r.normals = normals_out; r.cov6 = cov6_out;
         PCR_LAUNCH(ctx, k_radius_moments, dim3((unsigned)(((size_t)c->cap * OCT + KNN_BS - 1) / KNN_BS)), dim3(KNN_BS), 0, ctx->stream, r);
         return PCR_OK;

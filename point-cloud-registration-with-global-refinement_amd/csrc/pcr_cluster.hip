@@ -2,8 +2,7 @@
 // Reference behaviour: Open3D PointCloud::ClusterDBSCAN (cpp/open3d/geometry/PointCloudCluster.cpp); the reference scripts do not call it,
 // Open3D users put it between the outlier filters and a registration.  The six rules (neighbourhood, core, clusters, numbering, border,
 // noise) are stated next to the entry point in include/pcr_hip.h; they fix every label, so the result is Open3D's, not a renaming of it.
-// Three kernels walk the Morton-sorted octree of pcr_octree.h with the shared walk of k_radius_count / k_iss_saliency (oct_search_group):
-// the core count, the union of the core-core pairs in a lock-free union-find, and the border labels.  Everything between the kernels is
+// Three kernels are fixed-radius walks of the Morton-sorted octree (oct_group_frame / oct_ball_walk, pcr_octree.h): the core count, the union of the core-core pairs in a lock-free union-find, and the border labels.  Everything between the kernels is
 // in SORTED order, next to pts; only the outputs go through perm to the caller's rows.  Nothing here touches the other units' kernels.
 #include <cmath>
 #include "pcr_octree.h"
@@ -11,50 +10,23 @@
 #define DBS_BS 256
 #define DBS_NONE 0x7fffffff
 
-// membership of p in the neighbourhood of q: float32 screen against a slightly wide r^2, then d^2 < r^2 (strict) in float64 on the float32
-// coordinates -- differences, squares and sums rounded one by one (no fused multiply-add), so that a host recomputation in the order
-// x, y, z gives the same bits and an exact tie d^2 == r^2 is decided (not a member), not left to rounding.  Symmetric in p and q.
-__device__ static inline bool dbs_member(const float4 q, const float4 p, float r2f, double r2) {
-#pragma clang fp contract(off)
-    if (!(pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < r2f)) return false;
-    const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
-    double d2 = dx * dx;
-    d2 += dy * dy;
-    d2 += dz * dz;
-    return d2 < r2;
-}
+// Membership of p in the neighbourhood of q is oct_ball_member<true> in all three walks: d^2 < eps^2 (strict) with d^2 formed without fused
+// multiply-adds, so that a host recomputation in the order x, y, z gives the same bits and an exact tie d^2 == eps^2 is decided (not a
+// member), not left to rounding.
 
 // ============================================================================================================ core points
-// The walk of k_radius_count with the threshold min_points: a query whose count has reached min_points is finished (only "at least
-// min_points" matters), its bound drops to 0 and the wavefront's walk ends when all its queries are.  Writes the core flag of the sorted
-// row and sets up the row's union-find entries: parent = itself, smallest caller index of its tree = none yet.
+// The walk at eps with a counter: a query whose count has reached min_points is finished (only "at least min_points" matters).  Writes the
+// core flag of the sorted row and sets up the row's union-find entries: parent = itself, smallest caller index of its tree = none yet.
 struct DbsCoreArgs { OctView t; float r2f; double r2; int min_points; uint8_t *core; int *parent; int *min_caller; };
 __global__ void __launch_bounds__(DBS_BS) k_dbscan_core(DbsCoreArgs a) {
-    constexpr int OPB = DBS_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[DBS_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
+    oct_group_frame<DBS_BS>(a.t, [&](const OctGroupQuery &g) {
     int cnt = 0, total = 0;                                   // this lane's count; the octet's (octet-uniform, refreshed after every range)
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (live && total < a.min_points && idx < first + count) {
-                if (dbs_member(q, a.t.pts[idx], a.r2f, a.r2)) cnt++;
-            }
-        }
-        total = pcr_octet_sum_i(cnt);
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return total >= a.min_points ? 0.0f : a.r2f; }, visit,
-                     [](int, int) { return false; }, ol);
-    if (live && ol == 0) { a.core[qi] = total >= a.min_points ? 1 : 0; a.parent[qi] = qi; a.min_caller[qi] = DBS_NONE; }
+    // active until the count has reached min_points: total changes in the per-range step only, as active() must
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return g.live && total < a.min_points; },
+                  [&](int idx) { if (oct_ball_member<true>(g.q, a.t.pts[idx], a.r2f, a.r2)) cnt++; },
+                  [&]() { total = pcr_octet_sum_i(cnt); });
+    if (g.live && g.ol == 0) { a.core[g.qi] = total >= a.min_points ? 1 : 0; a.parent[g.qi] = g.qi; a.min_caller[g.qi] = DBS_NONE; }
+    });
 }
 
 // ============================================================================================= union-find over the core-core pairs
@@ -116,34 +88,21 @@ __device__ static inline int dbs_unite(int *parent, int a, int b, int pb) {
 // in between needs another lane.
 struct DbsUnionArgs { OctView t; float r2f; double r2; const uint8_t *core; int *parent; };
 __global__ void __launch_bounds__(DBS_BS) k_dbscan_union(DbsUnionArgs a) {
-    constexpr int OPB = DBS_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[DBS_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const bool cq = live && a.core[qi] != 0;                  // octet-uniform
+    oct_group_frame<DBS_BS>(a.t, [&](const OctGroupQuery &g) {
+    const int qi = g.qi;
+    const bool cq = g.live && a.core[qi] != 0;                // octet-uniform
     if (__ballot(cq) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
     int from = qi;                                            // a row of qi's tree, <= qi: the last root this lane saw
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (cq && idx < first + count && idx < qi) {
-                // the three loads are independent and go out together; a row that is not core, or hangs under `from` already, needs no test
-                const float4 p = a.t.pts[idx];
-                const int c = a.core[idx], pb = dbs_load(a.parent + idx);
-                if (c != 0 && pb != from && dbs_member(q, p, a.r2f, a.r2)) from = dbs_unite(a.parent, from, idx, pb);
-            }
+    // active = cq, fixed for the whole walk
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return cq; }, [&](int idx) {
+        if (idx < qi) {
+            // the three loads are independent and go out together; a row that is not core, or hangs under `from` already, needs no test
+            const float4 p = a.t.pts[idx];
+            const int c = a.core[idx], pb = dbs_load(a.parent + idx);
+            if (c != 0 && pb != from && oct_ball_member<true>(g.q, p, a.r2f, a.r2)) from = dbs_unite(a.parent, from, idx, pb);
         }
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return cq ? a.r2f : 0.0f; }, visit,
-                     [](int, int) { return false; }, ol);
+    });
+    });
 }
 
 // ======================================================================================================== roots and numbering
@@ -191,33 +150,17 @@ __global__ void __launch_bounds__(DBS_BS) k_dbscan_core_labels(const int *__rest
 // fills run in label order and relabel a point only from "unvisited" or "noise", so the first cluster to reach a border point keeps it.
 struct DbsBorderArgs { OctView t; const uint32_t *perm; float r2f; double r2; const uint8_t *core; const int *label_sorted; int32_t *labels; };
 __global__ void __launch_bounds__(DBS_BS) k_dbscan_border(DbsBorderArgs a) {
-    constexpr int OPB = DBS_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[DBS_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const bool bq = live && a.core[qi] == 0;                  // octet-uniform
+    oct_group_frame<DBS_BS>(a.t, [&](const OctGroupQuery &g) {
+    const bool bq = g.live && a.core[g.qi] == 0;              // octet-uniform
     if (__ballot(bq) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
     int best = DBS_NONE;
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (bq && idx < first + count) {
-                if (a.core[idx] != 0 && dbs_member(q, a.t.pts[idx], a.r2f, a.r2)) best = min(best, a.label_sorted[idx]);     // the flag first: a non-core row gives no label
-            }
-        }
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return bq ? a.r2f : 0.0f; }, visit,
-                     [](int, int) { return false; }, ol);
+    // active = bq, fixed for the whole walk
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return bq; }, [&](int idx) {
+        if (a.core[idx] != 0 && oct_ball_member<true>(g.q, a.t.pts[idx], a.r2f, a.r2)) best = min(best, a.label_sorted[idx]);     // the flag first: a non-core row gives no label
+    });
     best = pcr_octet_min_i(best);
-    if (bq && ol == 0) a.labels[a.perm[qi]] = best == DBS_NONE ? -1 : best;
+    if (bq && g.ol == 0) a.labels[a.perm[g.qi]] = best == DBS_NONE ? -1 : best;
+    });
 }
 
 // ====================================================================================================== C ABI
@@ -239,7 +182,7 @@ extern "C" int pcr_cluster_dbscan(pcr_context *ctx, const float *xyz, int64_t n,
     if (!core || !flag || !parent || !root || !min_caller || !pos || !label_sorted || !total) return PCR_ENOMEM;
     const dim3 walk((unsigned)(((size_t)c.cap * OCT + DBS_BS - 1) / DBS_BS)), rows((unsigned)((n + DBS_BS - 1) / DBS_BS));
     const double r2 = eps * eps;
-    const float r2f = (float)(r2 * (1.0 + 1e-6));
+    const float r2f = pcr_wide_r2f(r2);
     DbsCoreArgs ca; ca.t = oct_view(&c); ca.r2 = r2; ca.r2f = r2f; ca.min_points = min_points; ca.core = core; ca.parent = parent; ca.min_caller = min_caller;
     PCR_LAUNCH(ctx, k_dbscan_core, walk, dim3(DBS_BS), 0, ctx->stream, ca);
     DbsUnionArgs ua; ua.t = ca.t; ua.r2 = r2; ua.r2f = r2f; ua.core = core; ua.parent = parent;

@@ -33,6 +33,17 @@ __device__ static inline float pcr_box_d2(const float4 lo, const float4 hi, floa
     return pcr_d2(dx, dy, dz);
 }
 
+// squared distance of two float32 points in float64 as the reference's k-d tree forms it: differences, products and sums rounded one by
+// one (no fused multiply-add), so that a host recomputation in the order x, y, z gives the same bits.  Symmetric in p and q.
+__device__ static inline double pcr_d2_f64_unfused(const float4 q, const float4 p) {
+#pragma clang fp contract(off)
+    const double ex = (double)q.x - (double)p.x, ey = (double)q.y - (double)p.y, ez = (double)q.z - (double)p.z;
+    double d2 = ex * ex;
+    d2 += ey * ey;
+    d2 += ez * ez;
+    return d2;
+}
+
 // ------------------------------------------------------------------------------ 8-lane (octet) DPP ops
 // Data-parallel-primitive moves stay inside the VALU (no LDS crossbar, no lgkmcnt wait), unlike __shfl_xor which
 // compiles to ds_bpermute.  quad_perm covers xor 1 / xor 2, row_half_mirror (lane i <-> 7-i of each 8) joins the

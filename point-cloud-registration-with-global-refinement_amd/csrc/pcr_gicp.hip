@@ -1233,7 +1233,7 @@ static double icp_base_gap(double max_dist) {
 }
 static void icp_set_search_cap(IcpArgs &a, double max_dist, double g) {
     const double rs = max_dist + g;
-    a.r2s = (float)(rs * rs * (1.0 + 1e-6)); a.rs_minus_r = (float)(rs - max_dist);
+    a.r2s = pcr_wide_r2f(rs * rs); a.rs_minus_r = (float)(rs - max_dist);
 }
 
 // Arguments and start poses of a lockstep group: a per-context buffer whose device address is FIXED for the life of the context (the captured

@@ -237,8 +237,11 @@ int pcr_alloc_cloud(pcr_context *ctx, DevCloud *c, int cap, bool with_nrm, bool 
 // Morton-sorted copy of a caller cloud (+ optional normals) with its octree; perm maps sorted -> caller index
 int pcr_import_cloud(pcr_context *ctx, const float *xyz, const float *nrm, int64_t n, DevCloud *c, uint32_t **perm_out, bool force_nrm);
 
-// compaction of a caller-order cloud by a keep mask and its flag scan (defined in pcr_api.hip for pcr_remove_statistical_outlier; the radius filter launches it too): 256 threads per workgroup
-__global__ void k_emit_kept(const float *__restrict__ xyz, const uint8_t *__restrict__ keep, const int *__restrict__ pos, int n, float *__restrict__ out_xyz, int64_t *__restrict__ out_index);
+// compaction of a caller-order cloud by a keep mask (device, n rows; pcr_api.hip): scan of the mask, the kept rows' coordinates and / or indices
+// where asked for (device), the count on the host (one synchronisation).  Scratch from the arena.
+int pcr_emit_kept_rows(pcr_context *ctx, const float *xyz, int64_t n, const uint8_t *keep_caller, float *out_xyz, int64_t *out_index, int64_t *out_n);
+// distance of every point of a sorted cloud to its nearest other point, float64, to the caller's rows (pcr_query.hip); enqueues only
+int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, double *dist_caller);
 
 int pcr_registro_fgr_impl(pcr_context *ctx, const float *src_xyz, const float *src_prior, int64_t ns, const float *tgt_xyz, const float *tgt_prior, int64_t nt,
                           const pcr_fgr_params *p, float *src_normals_out, float *tgt_normals_out, pcr_result *result, int32_t *correspondences);

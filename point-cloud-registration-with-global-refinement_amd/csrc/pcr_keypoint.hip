@@ -2,8 +2,7 @@
 // Reference behaviour: Open3D geometry::keypoint::ComputeISSKeypoints (cpp/open3d/geometry/Keypoint.cpp); the reference scripts do not
 // call it, Open3D users put it in front of a global registration so that the feature search runs over a few percent of the points.
 // The rules (radius membership, the suppression guard G, the default radii) are stated next to the entry point in include/pcr_hip.h.
-// Both kernels walk the Morton-sorted octree of pcr_octree.h with the shared walk of k_radius_moments / k_radius_count (oct_search_group);
-// nothing here touches those kernels.
+// Both kernels are fixed-radius walks of the Morton-sorted octree (oct_group_frame / oct_ball_walk, pcr_octree.h).
 #include <cmath>
 #include "pcr_octree.h"
 
@@ -76,11 +75,9 @@ __device__ static inline bool iss_eigenvalues3(const double *C6, double *ev) {
 }
 
 // ======================================================================================================== saliency
-// The walk of k_radius_moments with another epilogue: one query per octet, the 8 Morton-consecutive queries of a wavefront share one walk;
-// float32 screen against a slightly wide r^2, membership in float64 on the float32 coordinates (d^2 < r^2, strict, the point itself a
-// member).  The moments are those of (p - q), the offset from the QUERY: the covariance does not depend on the origin, the terms are at
-// most r^2 instead of the squares of coordinates hundreds of metres from the origin (SURVEY.md hard part 3), and a neighbourhood of
-// coincident points gives exactly zero.  saliency = the smallest eigenvalue when l2 / l1 < gamma_21 and l3 / l2 < gamma_32, else 0;
+// The fixed-radius walk at salient_radius, every query to its end (the point itself a member).  The moments are those of (p - q), the
+// offset from the QUERY: the covariance does not depend on the origin, the terms are at most r^2 instead of the squares of coordinates
+// hundreds of metres from the origin (SURVEY.md hard part 3), and a neighbourhood of coincident points gives exactly zero.  saliency = the smallest eigenvalue when l2 / l1 < gamma_21 and l3 / l2 < gamma_32, else 0;
 // 0 too with fewer than min_neighbors members or an all-zero covariance.
 struct IssSalArgs {
     OctView t; const uint32_t *perm; float r2f; double r2; double gamma_21, gamma_32; int min_neighbors;
@@ -88,39 +85,20 @@ struct IssSalArgs {
     double *sal_caller, *eig_caller;          // optional caller rows: saliency (n), eigenvalues descending (n x 3)
 };
 __global__ void __launch_bounds__(ISS_BS) k_iss_saliency(IssSalArgs a) {
-    constexpr int OPB = ISS_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[ISS_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
-    const double qx = q.x, qy = q.y, qz = q.z;
+    oct_group_frame<ISS_BS>(a.t, [&](const OctGroupQuery &g) {
+    const int qi = g.qi, ol = g.ol; const bool live = g.live; const float4 q = g.q;
     double cu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int cnt = 0;
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (live && idx < first + count) {
-                const float4 p = a.t.pts[idx];
-                if (pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < a.r2f) {
-                    const double dx = (double)p.x - qx, dy = (double)p.y - qy, dz = (double)p.z - qz;
-                    if (dx * dx + dy * dy + dz * dz < a.r2) {
-                        cu[0] += dx; cu[1] += dy; cu[2] += dz;
-                        cu[3] += dx * dx; cu[4] += dx * dy; cu[5] += dx * dz; cu[6] += dy * dy; cu[7] += dy * dz; cu[8] += dz * dz;
-                        cnt++;
-                    }
-                }
-            }
+    // active = live: every query walks to its end
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return live; }, [&](int idx) {
+        const float4 p = a.t.pts[idx];
+        if (oct_ball_member<false>(q, p, a.r2f, a.r2)) {
+            const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
+            cu[0] += dx; cu[1] += dy; cu[2] += dz;
+            cu[3] += dx * dx; cu[4] += dx * dy; cu[5] += dx * dz; cu[6] += dy * dy; cu[7] += dy * dz; cu[8] += dz * dz;
+            cnt++;
         }
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return a.r2f; }, visit,
-                     [](int, int) { return false; }, ol);
+    });
 #pragma unroll
     for (int t = 0; t < 9; t++) cu[t] = pcr_octet_sum(cu[t]);
     cnt = pcr_octet_sum_i(cnt);
@@ -140,52 +118,29 @@ __global__ void __launch_bounds__(ISS_BS) k_iss_saliency(IssSalArgs a) {
         if (a.sal_caller) a.sal_caller[row] = sal;
         if (a.eig_caller) { a.eig_caller[row * 3] = ev[2]; a.eig_caller[row * 3 + 1] = ev[1]; a.eig_caller[row * 3 + 2] = ev[0]; }
     }
+    });
 }
 
 // ============================================================================================= non-maximum suppression
-// The same walk at non_max_radius for the queries with saliency > 0: count the members, and look for one that suppresses the query,
-// s_j > s_i + G.  A query that is suppressed, or whose saliency is 0, is finished: its bound drops to 0 (as in k_radius_count), and the
-// wavefront's walk ends when its eight queries are.  The walk opens the nearest cells first, so most queries meet a stronger neighbour in
-// their own leaf.  keypoint = saliency > 0, at least min_neighbors members, no suppressor; the flag goes to the caller's row of the mask.
+// The fixed-radius walk at non_max_radius for the queries with saliency > 0 (a wavefront without one does not walk): count the members,
+// and look for one that suppresses the query, s_j > s_i + G.  A query that is suppressed is finished.  The walk opens the nearest cells
+// first, so most queries meet a stronger neighbour in their own leaf.  keypoint = saliency > 0, at least min_neighbors members, no
+// suppressor; the flag goes to the caller's row of the mask.
 struct IssNmsArgs { OctView t; const uint32_t *perm; float r2f; double r2; const double *sal_sorted; double guard; int min_neighbors; uint8_t *keep; };
 __global__ void __launch_bounds__(ISS_BS) k_iss_nonmax(IssNmsArgs a) {
-    constexpr int OPB = ISS_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[ISS_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
-    const double qx = q.x, qy = q.y, qz = q.z;
-    const double s = live ? a.sal_sorted[qi] : 0.0;
-    const bool cand = live && s > 0.0;                        // octet-uniform
+    oct_group_frame<ISS_BS>(a.t, [&](const OctGroupQuery &g) {
+    const double s = g.live ? a.sal_sorted[g.qi] : 0.0;
+    const bool cand = g.live && s > 0.0;                      // octet-uniform
     const double bar = s + a.guard;
-    int cnt = 0, total = 0, beaten = 0;                       // this lane's count; the octet's count and verdict (octet-uniform, refreshed after every range)
+    int cnt = 0, hit = 0, total = 0, beaten = 0;              // this lane's count and find; the octet's count and verdict (octet-uniform, refreshed after every range)
     if (__ballot(cand) != 0ull) {
-        auto visit = [&](int first, int count) {
-            int hit = 0;
-            for (int base = first; base < first + count; base += OCT) {
-                const int idx = base + ol;
-                if (cand && !beaten && idx < first + count) {
-                    const float4 p = a.t.pts[idx];
-                    if (pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < a.r2f) {
-                        const double dx = (double)p.x - qx, dy = (double)p.y - qy, dz = (double)p.z - qz;
-                        if (dx * dx + dy * dy + dz * dz < a.r2) { cnt++; hit |= a.sal_sorted[idx] > bar ? 1 : 0; }
-                    }
-                }
-            }
-            total = pcr_octet_sum_i(cnt);
-            beaten |= pcr_octet_sum_i(hit) != 0 ? 1 : 0;
-        };
-        const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-        oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return (cand && !beaten) ? a.r2f : 0.0f; }, visit,
-                         [](int, int) { return false; }, ol);
+        // active until a suppressor is found: beaten changes in the per-range step only, as active() must
+        oct_ball_walk(a.t, g, a.r2f, [&]() { return cand && !beaten; },
+                      [&](int idx) { if (oct_ball_member<false>(g.q, a.t.pts[idx], a.r2f, a.r2)) { cnt++; hit |= a.sal_sorted[idx] > bar ? 1 : 0; } },
+                      [&]() { total = pcr_octet_sum_i(cnt); beaten = pcr_octet_sum_i(hit) != 0 ? 1 : 0; });
     }
-    if (live && ol == 0) a.keep[a.perm[qi]] = (cand && !beaten && total >= a.min_neighbors) ? 1 : 0;
+    if (g.live && g.ol == 0) a.keep[a.perm[g.qi]] = (cand && !beaten && total >= a.min_neighbors) ? 1 : 0;
+    });
 }
 
 // ============================================================================================ default radii (resolution)
@@ -214,18 +169,13 @@ __global__ void k_iss_sum_final(const double *__restrict__ slabs, int nb, double
     }
 }
 
-// the nearest-neighbour distance kernel of pcr_query.hip (its argument record restated: the kernel is launched from here too)
-struct NnDistArgs { OctView t; const uint32_t *perm; double *dist; };
-__global__ void __launch_bounds__(256) k_nn_distance(NnDistArgs a);
-
 // resolution = the mean over all points of the distance to the nearest other point (0 for a point without one), on the host; one synchronisation
 static int iss_resolution(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, int64_t n, double *resolution) {
     ArenaMark mark(ctx);
     const int nb = (int)((n + ISS_BS - 1) / ISS_BS < ISS_SUM_MAX_BLOCKS ? (n + ISS_BS - 1) / ISS_BS : ISS_SUM_MAX_BLOCKS);
     double *dist = arena<double>(ctx, n), *slabs = arena<double>(ctx, nb), *out = arena<double>(ctx, 1);
     if (!dist || !slabs || !out) return PCR_ENOMEM;
-    NnDistArgs a; a.t = oct_view(c); a.perm = perm; a.dist = dist;
-    PCR_LAUNCH(ctx, k_nn_distance, dim3((unsigned)(((size_t)c->cap * OCT + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    PCR_TRY(pcr_dev_nn_distance(ctx, c, perm, dist));
     PCR_LAUNCH(ctx, k_iss_sum_partial, dim3(nb), dim3(ISS_BS), 0, ctx->stream, (const double *)dist, (int)n, slabs);
     PCR_LAUNCH(ctx, k_iss_sum_final, dim3(1), dim3(64), 0, ctx->stream, (const double *)slabs, nb, out);
     double sum = 0.0;
@@ -261,23 +211,14 @@ extern "C" int pcr_iss_keypoints(pcr_context *ctx, const float *xyz, int64_t n, 
     }
     double *sal_sorted = arena<double>(ctx, n);
     uint8_t *keep_caller = keep_mask ? keep_mask : arena<uint8_t>(ctx, n);
-    int *pos = arena<int>(ctx, n);
-    int *total = arena<int>(ctx, 1);
-    if (!sal_sorted || !keep_caller || !pos || !total) return PCR_ENOMEM;
+    if (!sal_sorted || !keep_caller) return PCR_ENOMEM;
     const dim3 grid((unsigned)(((size_t)c.cap * OCT + ISS_BS - 1) / ISS_BS));
-    IssSalArgs sa; sa.t = oct_view(&c); sa.perm = perm; sa.r2 = salient_radius * salient_radius; sa.r2f = (float)(sa.r2 * (1.0 + 1e-6));
+    IssSalArgs sa; sa.t = oct_view(&c); sa.perm = perm; sa.r2 = salient_radius * salient_radius; sa.r2f = pcr_wide_r2f(sa.r2);
     sa.gamma_21 = gamma_21; sa.gamma_32 = gamma_32; sa.min_neighbors = min_neighbors; sa.sal_sorted = sal_sorted; sa.sal_caller = saliency; sa.eig_caller = eigenvalues3;
     PCR_LAUNCH(ctx, k_iss_saliency, grid, dim3(ISS_BS), 0, ctx->stream, sa);
-    IssNmsArgs na; na.t = sa.t; na.perm = perm; na.r2 = non_max_radius * non_max_radius; na.r2f = (float)(na.r2 * (1.0 + 1e-6));
+    IssNmsArgs na; na.t = sa.t; na.perm = perm; na.r2 = non_max_radius * non_max_radius; na.r2f = pcr_wide_r2f(na.r2);
     na.sal_sorted = sal_sorted; na.guard = ISS_G_FACTOR * sa.r2; na.min_neighbors = min_neighbors; na.keep = keep_caller;
     PCR_LAUNCH(ctx, k_iss_nonmax, grid, dim3(ISS_BS), 0, ctx->stream, na);
-    // the keypoints in CALLER order, ascending (select_by_index semantics), as the outlier filters emit their kept points
-    PCR_TRY(pcr_dev_flag_scan(ctx, keep_caller, nullptr, (int)n, pos, total));
-    if (out_xyz || out_index)
-        PCR_LAUNCH(ctx, k_emit_kept, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, xyz, (const uint8_t *)keep_caller, (const int *)pos, (int)n, out_xyz, out_index);
-    int64_t kept = 0;
-    PCR_TRY(pcr_read_count(ctx, total, &kept));
-    if (out_n) *out_n = kept;
-    return PCR_OK;
+    return pcr_emit_kept_rows(ctx, xyz, n, keep_caller, out_xyz, out_index, out_n);      // the keypoints in CALLER order, ascending
     });
 }

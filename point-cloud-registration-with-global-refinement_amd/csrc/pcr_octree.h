@@ -550,3 +550,65 @@ __device__ static inline void oct_search_group(const OctView &t, const OctMeta &
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// FRAME of a kernel that runs one query per octet over the cloud's OWN points with the group search: workgroups of BS threads,
+// query qi = the octet's index in the grid (Morton order), the 8 queries of a wavefront share one walk started at the leaf of the
+// wavefront's first query g0.  The frame owns the LDS (tree record, one stack per wavefront), returns for a wavefront without a
+// live query and hands everything else to body(g).  All 64 lanes of a wavefront that reaches body run it.
+struct OctGroupQuery {
+    const OctMeta &m; OctGroupStack &stk;
+    int n, qi, ol;            // points; this octet's query; lane in the octet
+    bool live;                // qi < n (octet-uniform)
+    float4 q;                 // pts[qi] (pts[0] when not live)
+    int g0;                   // first query of the wavefront: live whenever body runs
+};
+template <int BS, class Body>
+__device__ static inline void oct_group_frame(const OctView &t, Body body) {
+    constexpr int OPB = BS / OCT;
+    __shared__ OctMeta m;
+    __shared__ OctGroupStack gstk[BS / 64];
+    if (threadIdx.x == 0) m = *t.meta;
+    __syncthreads();
+    const int qi = blockIdx.x * OPB + (threadIdx.x >> 3);
+    const bool live = qi < m.n;
+    if (__ballot(live) == 0ull) return;
+    const OctGroupQuery g = {m, gstk[threadIdx.x >> 6], m.n, qi, (int)(threadIdx.x & 7), live, t.pts[live ? qi : 0],
+                             (int)(blockIdx.x * OPB + (threadIdx.x >> 6) * OCT)};
+    body(g);
+}
+
+// float32 radius of the walk's screen: slightly wide, so that no point the float64 decision d^2 < r^2 admits is screened out
+static inline float pcr_wide_r2f(double r2) { return (float)(r2 * (1.0 + 1e-6)); }
+
+// Is p inside the ball of q?  The float32 screen against r2f = pcr_wide_r2f(r2), then d^2 < r^2 (strict) in float64 on the float32
+// coordinates.  UNFUSED: d^2 with every product and sum rounded on its own (pcr_d2_f64_unfused), so that an exact tie d^2 == r^2 is
+// decided as a host recomputation decides it; otherwise the compiler is free to contract the sum.  Which kernel uses which form is
+// frozen: the other form decides a pair within one ulp of r^2 the other way.
+template <bool UNFUSED>
+__device__ static inline bool oct_ball_member(const float4 q, const float4 p, float r2f, double r2) {
+    if (!(pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < r2f)) return false;
+    if (UNFUSED) return pcr_d2_f64_unfused(q, p) < r2;
+    const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
+    return dx * dx + dy * dy + dz * dz < r2;
+}
+
+// FIXED-RADIUS WALK of the queries of a frame: cand(idx) runs in the lane that holds point idx of every range the walk scans, while
+// active() holds; after_range() runs in all lanes once per range (octet reductions of what cand collected).  active() must be
+// octet-uniform, false in an octet that is not live, and may only change inside after_range(): a query whose active() has dropped is
+// finished -- its bound is 0 -- and the walk ends when the wavefront's eight queries are.  No leaf is skipped.
+template <class ActiveFn, class CandFn, class AfterFn>
+__device__ static inline void oct_ball_walk(const OctView &t, const OctGroupQuery &g, float r2f, ActiveFn active, CandFn cand, AfterFn after_range) {
+    auto visit = [&](int first, int count) {                   // wave-uniform range
+        for (int base = first; base < first + count; base += OCT) {
+            const int idx = base + g.ol;
+            if (active() && idx < first + count) cand(idx);
+        }
+        after_range();
+    };
+    oct_search_group(t, g.m, g.stk, g.live, t.leaf_of[g.g0], g.q.x, g.q.y, g.q.z, [&]() { return active() ? r2f : 0.0f; }, visit,
+                     [](int, int) { return false; }, g.ol);
+}
+template <class ActiveFn, class CandFn>
+__device__ static inline void oct_ball_walk(const OctView &t, const OctGroupQuery &g, float r2f, ActiveFn active, CandFn cand) {
+    oct_ball_walk(t, g, r2f, active, cand, []() {});
+}

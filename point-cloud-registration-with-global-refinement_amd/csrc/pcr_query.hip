@@ -11,16 +11,9 @@
 #define QRY_BS 256
 #define QRY_FAR 3.4e38f
 
-// distance of two float32 points in float64: differences, products and sums rounded one by one (no fused multiply-add), so that the
-// value is the one a host recomputation in the same order gives, bit for bit
-__device__ static inline double qry_dist_f64(float qx, float qy, float qz, const float4 p) {
-#pragma clang fp contract(off)
-    const double ex = (double)qx - (double)p.x, ey = (double)qy - (double)p.y, ez = (double)qz - (double)p.z;
-    double d2 = ex * ex;
-    d2 += ey * ey;
-    d2 += ez * ez;
-    return sqrt(d2);
-}
+// distance of two float32 points in float64, from the squared distance without fused multiply-adds: the value a host recomputation in the
+// same order gives, bit for bit
+__device__ static inline double qry_dist_f64(float qx, float qy, float qz, const float4 p) { return sqrt(pcr_d2_f64_unfused(make_float4(qx, qy, qz, 0.0f), p)); }
 
 // ====================================================== nearest-neighbour distance (ComputeNearestNeighborDistance)
 // The 2-best search of every point over its own tree: one query per octet, the 8 Morton-consecutive queries of a wavefront share one
@@ -30,18 +23,8 @@ __device__ static inline double qry_dist_f64(float qx, float qy, float qz, const
 // once per query (seed range and walk are disjoint), so the point itself cannot fill both places.
 struct NnDistArgs { OctView t; const uint32_t *perm; double *dist; };
 __global__ void __launch_bounds__(QRY_BS) k_nn_distance(NnDistArgs a) {
-    constexpr int OPB = QRY_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[QRY_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;                 // first query of the wavefront (live, or the ballot above was empty)
+    oct_group_frame<QRY_BS>(a.t, [&](const OctGroupQuery &g) {
+    const int n = g.n, qi = g.qi, ol = g.ol, g0 = g.g0; const bool live = g.live; const float4 q = g.q;
     const int glast = g0 + OCT - 1 < n - 1 ? g0 + OCT - 1 : n - 1;
     const int plo = g0 - OCT < 0 ? 0 : g0 - OCT, phi = glast + OCT > n - 1 ? n - 1 : glast + OCT;
     bool seeding = true;
@@ -68,7 +51,7 @@ __global__ void __launch_bounds__(QRY_BS) k_nn_distance(NnDistArgs a) {
     };
     visit(plo, phi - plo + 1);
     seeding = false;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return bound; }, visit,
+    oct_search_group(a.t, g.m, g.stk, live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return bound; }, visit,
                      [&](int f, int c) { return f >= plo && f + c - 1 <= phi; }, ol);
     const bool holder = rest_is_second();
     const float h0 = d0, h1 = d1; const int j0 = i0, j1 = i1;
@@ -76,9 +59,10 @@ __global__ void __launch_bounds__(QRY_BS) k_nn_distance(NnDistArgs a) {
     const float sec = pcr_octet_min(v);
     const int nb = pcr_octet_min_i((v == sec && vi >= 0) ? vi : 0x7fffffff);     // ties -> lower index
     if (live && ol == 0) a.dist[a.perm[qi]] = nb != 0x7fffffff ? qry_dist_f64(q.x, q.y, q.z, a.t.pts[nb]) : 0.0;
+    });
 }
 
-static int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, double *dist_caller) {
+int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, double *dist_caller) {
     if (c->cap <= 0) return PCR_OK;
     NnDistArgs a; a.t = oct_view(c); a.perm = perm; a.dist = dist_caller;
     PCR_LAUNCH(ctx, k_nn_distance, dim3((unsigned)(((size_t)c->cap * OCT + QRY_BS - 1) / QRY_BS)), dim3(QRY_BS), 0, ctx->stream, a);
@@ -147,47 +131,23 @@ static int pcr_dev_cloud_distance(pcr_context *ctx, const float *src_xyz, int64_
 }
 
 // ============================================================================ radius outlier filter (RemoveRadiusOutliers)
-// The walk of k_radius_moments (pcr_cloud.hip) with a counter in place of the moments: float32 screen against a slightly wide r^2, the
-// decision in float64 on the float32 coordinates (d^2 < r^2, strict, the point itself counted).  A query whose count has passed
-// nb_points is finished: its bound drops to 0, and the wavefront's walk ends when all its queries are.  The flag goes to the caller's
-// row of the mask the flag scan compacts.
+// The fixed-radius walk with a counter (the point itself counted).  A query whose count has passed nb_points is finished; the flag goes to
+// the caller's row of the mask the flag scan compacts.
 struct RadCountArgs { OctView t; const uint32_t *perm; float r2f; double r2; int nb_points; uint8_t *keep; };
 __global__ void __launch_bounds__(QRY_BS) k_radius_count(RadCountArgs a) {
-    constexpr int OPB = QRY_BS / OCT;
-    __shared__ OctMeta m;
-    __shared__ OctGroupStack gstk[QRY_BS / 64];
-    if (threadIdx.x == 0) m = *a.t.meta;
-    __syncthreads();
-    const int n = m.n;
-    const int lane = threadIdx.x & 63, ol = lane & 7, ob = threadIdx.x >> 3;
-    const int qi = blockIdx.x * OPB + ob;
-    const bool live = qi < n;
-    if (__ballot(live) == 0ull) return;
-    const float4 q = a.t.pts[live ? qi : 0];
-    const double qx = q.x, qy = q.y, qz = q.z;
+    oct_group_frame<QRY_BS>(a.t, [&](const OctGroupQuery &g) {
     int cnt = 0, total = 0;                                   // this lane's count; the octet's (octet-uniform, refreshed after every range)
-    auto visit = [&](int first, int count) {
-        for (int base = first; base < first + count; base += OCT) {
-            const int idx = base + ol;
-            if (live && total <= a.nb_points && idx < first + count) {
-                const float4 p = a.t.pts[idx];
-                if (pcr_d2(p.x - q.x, p.y - q.y, p.z - q.z) < a.r2f) {
-                    const double dx = (double)p.x - qx, dy = (double)p.y - qy, dz = (double)p.z - qz;
-                    if (dx * dx + dy * dy + dz * dz < a.r2) cnt++;
-                }
-            }
-        }
-        total = pcr_octet_sum_i(cnt);
-    };
-    const int g0 = blockIdx.x * OPB + (threadIdx.x >> 6) * OCT;
-    oct_search_group(a.t, m, gstk[threadIdx.x >> 6], live, a.t.leaf_of[g0], q.x, q.y, q.z, [&]() { return total > a.nb_points ? 0.0f : a.r2f; }, visit,
-                     [](int, int) { return false; }, ol);
-    if (live && ol == 0) a.keep[a.perm[qi]] = total > a.nb_points ? 1 : 0;
+    // active until the count has passed nb_points: total changes in the per-range step only, as active() must
+    oct_ball_walk(a.t, g, a.r2f, [&]() { return g.live && total <= a.nb_points; },
+                  [&](int idx) { if (oct_ball_member<false>(g.q, a.t.pts[idx], a.r2f, a.r2)) cnt++; },
+                  [&]() { total = pcr_octet_sum_i(cnt); });
+    if (g.live && g.ol == 0) a.keep[a.perm[g.qi]] = total > a.nb_points ? 1 : 0;
+    });
 }
 
 static int pcr_dev_radius_count(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, int nb_points, double radius, uint8_t *keep_caller) {
     if (c->cap <= 0) return PCR_OK;
-    RadCountArgs a; a.t = oct_view(c); a.perm = perm; a.r2 = radius * radius; a.r2f = (float)(a.r2 * (1.0 + 1e-6)); a.nb_points = nb_points; a.keep = keep_caller;
+    RadCountArgs a; a.t = oct_view(c); a.perm = perm; a.r2 = radius * radius; a.r2f = pcr_wide_r2f(a.r2); a.nb_points = nb_points; a.keep = keep_caller;
     PCR_LAUNCH(ctx, k_radius_count, dim3((unsigned)(((size_t)c->cap * OCT + QRY_BS - 1) / QRY_BS)), dim3(QRY_BS), 0, ctx->stream, a);
     return PCR_OK;
 }
@@ -300,18 +260,9 @@ extern "C" int pcr_remove_radius_outlier(pcr_context *ctx, const float *xyz, int
     DevCloud c; uint32_t *perm = nullptr;
     PCR_TRY(pcr_import_cloud(ctx, xyz, nullptr, n, &c, &perm, false));
     uint8_t *keep_caller = keep_mask ? keep_mask : arena<uint8_t>(ctx, n);
-    int *pos = arena<int>(ctx, n);
-    int *total = arena<int>(ctx, 1);
-    if (!keep_caller || !pos || !total) return PCR_ENOMEM;
+    if (!keep_caller) return PCR_ENOMEM;
     PCR_TRY(pcr_dev_radius_count(ctx, &c, perm, nb_points, radius, keep_caller));
-    // the kept points in CALLER order (select_by_index semantics), as pcr_remove_statistical_outlier emits them
-    PCR_TRY(pcr_dev_flag_scan(ctx, keep_caller, nullptr, (int)n, pos, total));
-    if (out_xyz || out_index)
-        PCR_LAUNCH(ctx, k_emit_kept, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, xyz, keep_caller, pos, (int)n, out_xyz, out_index);
-    int64_t kept = 0;
-    PCR_TRY(pcr_read_count(ctx, total, &kept));
-    if (out_n) *out_n = kept;
-    return PCR_OK;
+    return pcr_emit_kept_rows(ctx, xyz, n, keep_caller, out_xyz, out_index, out_n);
     });
 }
 

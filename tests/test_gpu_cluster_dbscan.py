@@ -247,6 +247,12 @@ def test_fewer_points_than_an_octet(P):
         _assert_equal(P, pts, 0.5, mp, "7 points")
 
 
+@pytest.mark.parametrize("n", [9, 63, 65, 257])
+def test_partial_octets_wavefronts_and_a_second_workgroup(P, points, n):
+    """the first n points of the main input: a partial last octet (9, 63, 65, 257), a partial last wavefront and, at 257, a second workgroup"""
+    _assert_equal(P, points[:n], 0.5, 4, f"first {n} points")
+
+
 def test_coincident_points(P):
     pts = np.tile(np.array([[3.0, 1.0, -2.0]], np.float32), (20, 1))
     rc, lab, core, m = _raw(P, pts, 0.1, 20)

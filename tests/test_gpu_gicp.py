@@ -238,6 +238,23 @@ def test_radius_normals_and_gicp_robusto_match_oracle(P, oracle, small_pair):
     assert res.iterations == ref.iterations and abs(res.fitness - ref.fitness) < 1e-9
 
 
+@pytest.mark.parametrize("n", [1, 7, 9, 65, 257])
+def test_radius_normals_and_covariances_of_small_clouds(P, oracle, small_pair, n):
+    """The radius walk with a partial last octet (1, 7, 9), a partial last wavefront (9, 65) and a second workgroup (257: 32 queries per
+    workgroup); the first n points of the cloud of the test above, its comparison and its tolerance."""
+    sp = P.PointCloud(small_pair["source"]).voxel_down_sample(0.2).points[:n]
+    pc = P.PointCloud(sp)
+    pc.estimate_normals(P.KDTreeSearchParamRadius(radius=0.6))
+    ref_n = oracle.estimate_normals(sp, oracle.SEARCH_RADIUS, 0, 0.6)
+    dots = (pc.normals * ref_n).sum(1)
+    print(f"n = {n}: smallest dot {dots.min():.9f}")
+    assert (dots > 1 - 1e-5).mean() > 0.999
+    pc.estimate_covariances(P.KDTreeSearchParamRadius(radius=0.6))
+    ref_c = oracle.estimate_covariances(sp, oracle.SEARCH_RADIUS, 0, 0.6)
+    scale = np.abs(ref_c).max(axis=(1, 2), keepdims=True)
+    assert (np.abs(pc.covariances - ref_c) <= 2e-6 * scale + 1e-9).mean() > 0.999
+
+
 def test_register_pairs_equals_one_call_per_pair(P, golden_pair_list):
     """`pcr_register_pairs` (many pairs per call, pairs in flight inside the library) = `pcr_multiscale_gicp` per pair, bit for bit."""
     vox = P.script2.create_scales(5); dst = P.script2.max_correspondence_distances(vox)
