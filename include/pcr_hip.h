@@ -427,6 +427,56 @@ int pcr_registration_ransac_feature_matching(pcr_context *ctx, const float *src_
                                              double max_distance, const pcr_ransac_params *params, pcr_result *result, int32_t *correspondences,
                                              pcr_ransac_info *info);
 
+/* == PointCloud.segment_plane (Open3D PointCloud::SegmentPlane; the reference calls it nowhere and Open3D's own result depends on its random
+ *    engine and thread timing, so the algorithm is stated here and this statement is the specification).  [O3D ?] marks what is recalled from
+ *    SegmentPlane / GetPlaneFromPoints and not pinned against a build of Open3D.  ONE sequential loop over hypotheses i = 0, 1, ... defines the
+ *    answer, bit for bit for a given seed; the device may only reorder work that cannot change it.
+ *    SAMPLE.  Hypothesis i draws rows r_k = splitmix64(seed + ransac_n * i + k) % n, k < ransac_n (the sampler of the registration RANSAC above;
+ *    repeats allowed).
+ *    FIT.  Float64 on the float32 coordinates; every product, sum, quotient and square root rounded on its own (no fused multiply-add), in the
+ *    order written here, so that a host recomputation gives the same bits (csrc/pcr_plane.h is that order in code, host and device).
+ *    ransac_n == 3: u = p1 - p0, v = p2 - p0, normal N = u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx), origin o = p0.
+ *    ransac_n in 4..8, and the final refit: the moment fit [O3D ?].  Sums S = ((p_0 + p_1) + p_2) + ... over k = 0 .. ransac_n - 1 per
+ *    coordinate, centroid o = S / count; second moments about it, q_k = p_k - o, xx = sum qx qx, xy = sum qx qy, xz, yy, yz, zz in the same order of
+ *    k (sums, not divided by the count); det_x = yy zz - yz yz, det_y = xx zz - xz xz, det_z = xx yy - xy xy;
+ *      det_x > det_y and det_x > det_z:  N = (det_x, xz yz - xy zz, xy yz - xz yy)
+ *      else det_y > det_z:               N = (xz yz - xy zz, det_y, xy xz - yz xx)
+ *      else:                             N = (xy yz - xz yy, xy xz - yz xx, det_z).
+ *    Both: norm = sqrt((Nx Nx + Ny Ny) + Nz Nz), (a, b, c) = N / norm, d = -((a ox + b oy) + c oz).  A norm that is not > 0 or a plane that is
+ *    not finite makes the hypothesis INVALID; it still uses up its iteration.
+ *    SCORE.  dist_j = |((a x_j + b y_j) + c z_j) + d|, one expression for the score, the final inlier pass and the test hook.  Point j is an
+ *    inlier iff dist_j < distance_threshold (strict).  count_i = number of inliers, err_i = sum of dist_j over them ([O3D ?]: Open3D sums the
+ *    distance, not its square), rmse_i = err_i / sqrt(count_i).  The sum is taken in a fixed order: same bits on every run, no float atomics.
+ *    BETTER.  i is better than the running best if count_i is larger, or equal with rmse_i strictly smaller; count 0 is never better than the
+ *    empty start; on a full tie the earlier iteration stays.
+ *    STOP.  est_k = num_iterations at the start, iteration i runs iff i < est_k.  When i becomes the best and probability < 1,
+ *    k' = log(1 - probability) / log1p(-(count_i / n)^ransac_n), k' = 0 when count_i == n; if k' is finite and 0 <= k' < est_k then
+ *    est_k = ceil(k').  probability == 1 never stops early.
+ *    RESULT.  Inliers: the rows with dist_j < distance_threshold against the BEST HYPOTHESIS's plane, ascending.  plane4 = the moment fit over
+ *    those inliers (Open3D's last step; the centroid is sum / count and the moments are summed about it, both in a fixed order on the device),
+ *    with whatever sign the fit gives; a degenerate fit gives the zero plane.  No valid hypothesis with an inlier: the zero plane, no inliers,
+ *    best_iteration = -1; not an error.  num_iterations == 0: the same empty result.
+ *    PCR_EINVAL (the message names segment_plane): ransac_n outside 3..8 (Open3D has no upper limit; 8 is this library's RANSAC limit),
+ *    n < ransac_n (Open3D raises too), n above the int range, a null xyz or plane4, distance_threshold negative or not finite,
+ *    num_iterations < 0, probability outside (0, 1]. */
+typedef struct {
+    int32_t ransac_n;                 /* 3; 3..8 */
+    int32_t num_iterations;           /* 100 */
+    double probability;               /* 0.99999999; in (0, 1], 1 never stops early */
+    uint64_t seed;
+} pcr_plane_params;
+typedef struct {
+    int64_t iterations_run;
+    int64_t best_iteration;           /* -1: none */
+    int64_t n_valid;                  /* valid hypotheses among those run */
+    int64_t n_inliers;                /* count of the best hypothesis = rows in the index list */
+    double fitness, inlier_rmse;      /* of the best hypothesis: count / n and err / sqrt(count) */
+} pcr_plane_info;
+/* xyz: device, n x 3 float32.  plane4 (host): a, b, c, d.  inlier_mask (optional, device, n bytes) and out_index (optional, device int64, capacity n,
+ * ascending) + out_n (optional, host): the layout of pcr_remove_radius_outlier.  info optional (host). */
+int pcr_segment_plane(pcr_context *ctx, const float *xyz, int64_t n, double distance_threshold, const pcr_plane_params *params, double *plane4,
+                      uint8_t *inlier_mask, int64_t *out_index, int64_t *out_n, pcr_plane_info *info);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.
@@ -467,6 +517,12 @@ int pcr_debug_feature_nn(pcr_context *ctx, const float *f0, int64_t n0, const fl
 int pcr_debug_ransac_hypotheses(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
                                 int64_t n_tgt, const int32_t *corres, int64_t n_corres, double max_distance, const pcr_ransac_params *params, int64_t first,
                                 int64_t count, uint8_t *valid_out, double *T_out, int32_t *inliers_out, double *err2_out);
+
+/* what the plane kernels compute for iterations [first, first + count) of pcr_segment_plane with these arguments, no early stop (num_iterations and
+ * probability are checked, not used).  All four outputs are device arrays: valid_out count bytes, plane_out count x 4 float64 (zeros for an
+ * invalid hypothesis), inliers_out count int32 (-1: invalid), err_out count float64 (the sum of the inlier distances). */
+int pcr_debug_plane_hypotheses(pcr_context *ctx, const float *xyz, int64_t n, double distance_threshold, const pcr_plane_params *params, int64_t first,
+                               int64_t count, uint8_t *valid_out, double *plane_out, int32_t *inliers_out, double *err_out);
 
 /* test / diagnostic switches of the process (no reference equivalent).  Each one is latched from the environment variable of the same
  * name in upper case with the PCR_ prefix when the library first needs it; this call overrides it afterwards without touching the

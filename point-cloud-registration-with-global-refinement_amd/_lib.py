@@ -52,6 +52,15 @@ class PcrRansacInfo(C.Structure):
     _fields_ = [("iterations_run", C.c_int64), ("best_iteration", C.c_int64), ("n_valid", C.c_int64), ("n_corres", C.c_int64)]
 
 
+class PcrPlaneParams(C.Structure):
+    _fields_ = [("ransac_n", C.c_int32), ("num_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint64)]
+
+
+class PcrPlaneInfo(C.Structure):
+    _fields_ = [("iterations_run", C.c_int64), ("best_iteration", C.c_int64), ("n_valid", C.c_int64), ("n_inliers", C.c_int64),
+                ("fitness", C.c_double), ("inlier_rmse", C.c_double)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -100,10 +109,10 @@ EXPORTS = [
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
-    "pcr_iss_keypoints", "pcr_cluster_dbscan",
+    "pcr_iss_keypoints", "pcr_cluster_dbscan", "pcr_segment_plane", "pcr_debug_plane_hypotheses",
 ]
 
-# prototypes of the cloud queries, the keypoint detector and the clustering (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering and the plane segmentation (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -113,6 +122,10 @@ QUERY_PROTOTYPES = {
     "pcr_iss_keypoints": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)], C.c_int),
     "pcr_cluster_dbscan": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_segment_plane": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(PcrPlaneParams), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                           C.POINTER(C.c_int64), C.POINTER(PcrPlaneInfo)], C.c_int),
+    "pcr_debug_plane_hypotheses": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(PcrPlaneParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p], C.c_int),
 }
 
 _lib = None

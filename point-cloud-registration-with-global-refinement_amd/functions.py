@@ -144,6 +144,16 @@ def remove_small_clusters(cloud, eps, min_points, min_cluster_size):
     return cloud.select_by_index(indices), indices
 
 
+def remove_plane(cloud, distance_threshold, ransac_n=3, num_iterations=100, probability=0.99999999, seed=None):
+    """``segment_plane`` as a filter, not in the reference: takes the dominant plane -- the ground of a LiDAR scan, which would otherwise join
+    every object standing on it into one DBSCAN cluster -- out of the cloud.  Returns ``(rest, plane_model, removed)``: the cloud without the
+    plane's inliers, the plane ``(a, b, c, d)`` (numpy float64) and the removed rows as a device int64 tensor, ascending.  Mask and selection
+    stay on the device."""
+    import torch
+    plane, removed, info = _g._segment_plane(cloud, distance_threshold, ransac_n, num_iterations, probability, seed)
+    return cloud.select_by_index(torch.nonzero(~info["mask"]).reshape(-1)), plane, removed
+
+
 # ------------------------------------------------------------------------------------ script variants
 class script1:
     """Private copies in 1_FGR_pairwise_registration_in_NCLT_dataset.py."""

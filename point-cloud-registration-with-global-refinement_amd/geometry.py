@@ -240,6 +240,15 @@ class PointCloud:
         row by row (the rules: include/pcr_hip.h).  ``print_progress`` is accepted and ignored."""
         return _cluster_dbscan(self, eps, min_points)[0].cpu().numpy()
 
+    def segment_plane(self, distance_threshold: float, ransac_n: int = 3, num_iterations: int = 100, probability: float = 0.99999999, seed=None):
+        """``PointCloud.segment_plane``: the dominant plane of the cloud by RANSAC -> ``(plane_model, inliers)``, the plane ``(a, b, c, d)`` of
+        ``a x + b y + c z + d = 0`` as numpy float64 ``(4,)`` (refitted over the inliers, unit normal) and the ascending list of the rows within
+        ``distance_threshold`` of the best hypothesis.  The answer is that of one sequential loop, deterministic for a ``seed`` (the rules:
+        include/pcr_hip.h); ``seed=None`` draws from a process-local counter, as the registration RANSAC does.  No plane found: the zero plane
+        and an empty list."""
+        plane, index, _ = _segment_plane(self, distance_threshold, ransac_n, num_iterations, probability, seed)
+        return plane, index.cpu().numpy().tolist()
+
     def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
         """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
         if every_k_points < 1:
@@ -372,6 +381,33 @@ def _cluster_dbscan(cloud: PointCloud, eps: float, min_points: int):
     ctx.check(ctx.lib.pcr_cluster_dbscan(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), C.c_double(eps), C.c_int(int(min_points)), _ptr(labels),
                                          _ptr(core), C.byref(m)), "cluster_dbscan")
     return labels[:n], core[:n].bool(), int(m.value)
+
+
+_plane_seed_counter = [0xD1B54A32D192ED03]
+
+
+def _segment_plane(cloud: PointCloud, distance_threshold: float, ransac_n: int = 3, num_iterations: int = 100, probability: float = 0.99999999, seed=None):
+    """``pcr_segment_plane`` -> ``(plane (4,) numpy float64, inlier rows as a torch int64 tensor on the device (ascending), info)``; ``info`` is a
+    dict with ``iterations_run``, ``best_iteration`` (-1: none), ``n_valid``, ``n_inliers``, ``fitness``, ``inlier_rmse`` (the best hypothesis's) and
+    ``mask`` (the inlier mask, ``(n,)`` torch bool on the device): the form a pipeline that stays on the device builds on
+    (``functions.remove_plane``)."""
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n = len(cloud)
+    if seed is None:                       # Open3D draws from std::random_device; here a process-local counter
+        _plane_seed_counter[0] = (_plane_seed_counter[0] * 6364136223846793005 + 1442695040888963407) & (2 ** 64 - 1)
+        seed = _plane_seed_counter[0]
+    params = _lib.PcrPlaneParams(int(ransac_n), int(num_iterations), float(probability), int(seed) & (2 ** 64 - 1))
+    plane = (C.c_double * 4)()
+    mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    idx = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+    m = C.c_int64(0)
+    info = _lib.PcrPlaneInfo()
+    ctx.check(ctx.lib.pcr_segment_plane(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), C.c_double(distance_threshold), C.byref(params), plane,
+                                        _ptr(mask), _ptr(idx), C.byref(m), C.byref(info)), "segment_plane")
+    out = {k: getattr(info, k) for k, _ in _lib.PcrPlaneInfo._fields_}
+    out["mask"] = mask[:n].bool()
+    return np.array(plane, dtype=np.float64), idx[: m.value], out
 
 
 # ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
