@@ -16,7 +16,8 @@
  *     (no correspondences: fitness 0, rmse 0, T = init) are NOT errors (Open3D behaviour);
  *   - calls are ordered on the context's stream (pcr_set_stream).  Entry points with host outputs (counts, poses, results)
  *     return after those are on the host; entry points whose outputs are all device buffers (pcr_estimate_normals,
- *     pcr_estimate_covariances, pcr_compute_fpfh_feature, pcr_debug_knn) only enqueue and return;
+ *     pcr_estimate_covariances, pcr_compute_fpfh_feature, pcr_debug_knn, and the four searches pcr_index_knn, pcr_index_hybrid,
+ *     pcr_index_radius_count, pcr_index_radius_fill) only enqueue and return;
  *   - stream NULL = the legacy default stream: the library works on a stream of its own and fences every call against the
  *     default stream on both sides (the call sees everything enqueued there before it; work enqueued there after the call
  *     sees its results);
@@ -178,6 +179,46 @@ int pcr_remove_radius_outlier(pcr_context *ctx, const float *xyz, int64_t n, int
  * mean and the identity.  Float64 sums in a fixed order (same bits on every run), the second moments taken about the mean.  cov9 may be
  * NULL (get_center): the mean alone, the same bits, in one pass over the points instead of two. */
 int pcr_mean_and_covariance(pcr_context *ctx, const float *xyz, int64_t n, double *mean3, double *cov9);
+
+/* ============================================================================================ nearest-neighbour search index
+ * == o3d.geometry.KDTreeFlann (SetGeometry, SearchKNN, SearchRadius, SearchHybrid) and o3d.core.nns.NearestNeighborSearch (knn_search,
+ * fixed_radius_search, hybrid_search): an index over a cloud that outlives the call, searched with arbitrary query points.
+ *
+ * THE RESULT RULE, one for the three searches.  For a query q and a dataset point p, both float32 xyz, d^2 is taken in float64 --
+ * differences, squares and sums in the order x, y, z, each rounded once, no fused multiply-add -- and the dataset is totally ordered for q
+ * by (d^2, caller index of p), ascending.  knn: the first k points of that order, in that order.  radius: every point with d^2 < r^2, where
+ * r^2 = radius * radius in float64 and the test is strict; sorted rows come in that order.  hybrid: the first max_nn of the radius set, in that
+ * order.  The returned d^2 are those float64 values; there is no float32 tie clause, so a host recomputation gives the same rows bit for bit.
+ *
+ * All query, index and d^2 buffers are DEVICE buffers; rows are in the caller's query order and hold caller indices of the dataset.  A query
+ * with a non-finite coordinate finds nothing.  Limits: k and max_nn in 1..200, radius > 0, m and n in 0..2^31 - 1; anything else is
+ * PCR_EINVAL with a message.  The searches are asynchronous on the context's stream. */
+typedef struct pcr_index pcr_index;
+
+/* Builds the index over n float32 points (device): a Morton-sorted copy of the points with their caller indices and its octree, in ONE
+ * device allocation of its own -- not in the context's arena, so the index survives the context that built it, and any context on the same
+ * device may search it.  The build uses the context's arena as scratch and is finished when the call returns: the caller may free or
+ * overwrite xyz.  n == 0 is valid: every search on such an index finds nothing. */
+int pcr_index_create(pcr_context *ctx, const float *xyz, int64_t n, pcr_index **out);
+/* Frees the index (waits for the device, so no search is still reading it).  NULL is allowed. */
+int pcr_index_destroy(pcr_index *index);
+
+/* == KDTreeFlann.search_knn_vector_3d / NearestNeighborSearch.knn_search.  idx: m x k int32, d2: m x k float64.  Places beyond the
+ * dataset's size (k > n) hold idx = -1 and d2 = +inf. */
+int pcr_index_knn(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, int k, int32_t *idx, double *d2);
+
+/* == KDTreeFlann.search_hybrid_vector_3d / NearestNeighborSearch.hybrid_search.  idx: m x max_nn int32, d2: m x max_nn float64, counts: m int32 =
+ * min(max_nn, size of the ball).  Places beyond the count hold idx = -1 and d2 = 0 (Open3D's padding). */
+int pcr_index_hybrid(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, double radius, int max_nn,
+                     int32_t *idx, double *d2, int32_t *counts);
+
+/* == KDTreeFlann.search_radius_vector_3d / NearestNeighborSearch.fixed_radius_search, in two passes.  The count pass writes the size of every
+ * query's ball (counts: m int32).  The caller scans the counts into row_splits (m + 1 int64, device, row_splits[0] = 0) and allocates idx and
+ * d2 with row_splits[m] entries; the fill pass walks again and writes row i into [row_splits[i], row_splits[i + 1]) -- never beyond it.  With
+ * sort != 0 every row obeys the order of the rule; with sort == 0 the order inside a row is free (the set is the same). */
+int pcr_index_radius_count(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, double radius, int32_t *counts);
+int pcr_index_radius_fill(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, double radius, const int64_t *row_splits,
+                          int32_t *idx, double *d2, int sort);
 
 /* == geometry.keypoint.compute_iss_keypoints (Open3D ComputeISSKeypoints, cpp/open3d/geometry/Keypoint.cpp; not called by the reference scripts,
  * the usual stage in front of a global registration).  Per point i: the neighbourhood with d^2 < salient_radius^2 (point i included, the test
@@ -536,7 +577,9 @@ int pcr_debug_plane_hypotheses(pcr_context *ctx, const float *xyz, int64_t n, do
  * float pass whatever the size; 3: as 4 with a 16-entry queue, the overflow path), "radius_list_select" (1: overfull Hybrid(r, max_nn) balls finished by threshold selection; 0: by the k-best kernel),
  * "featnn_mutual" (1: the second direction of the feature search inside FGR runs only for the rows the first direction points at, under the
  * bound it found; 0: both directions in full), "icp_scales" (1: in lockstep groups of small clouds every pair goes through its scales by itself;
- * 0: one lockstep loop per scale).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
+ * 0: one lockstep loop per scale), "search_sort_queries" (-1: a k-nearest or hybrid search of an index takes a large batch of queries -- 131072 or more with k in
+ * 9..64, 32768 or more with k above 64 -- in the Morton order of the queries, every other search in the caller's order; 0: always in the caller's
+ * order; 1: always in Morton order).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
  * scratch nobody wrote then follows the pattern).  Returns PCR_EINVAL for an unknown name. */
 int pcr_set_option(const char *name, long long value);
 /* Process-wide event counters (value, or -1 for an unknown name; reset != 0 clears it): how often a lockstep registro_FGR group fell back to

@@ -110,9 +110,10 @@ EXPORTS = [
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
     "pcr_iss_keypoints", "pcr_cluster_dbscan", "pcr_segment_plane", "pcr_debug_plane_hypotheses",
+    "pcr_index_create", "pcr_index_destroy", "pcr_index_knn", "pcr_index_hybrid", "pcr_index_radius_count", "pcr_index_radius_fill",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering and the plane segmentation (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation and the search index (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -126,6 +127,12 @@ QUERY_PROTOTYPES = {
                            C.POINTER(C.c_int64), C.POINTER(PcrPlaneInfo)], C.c_int),
     "pcr_debug_plane_hypotheses": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(PcrPlaneParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_index_create": ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_index_destroy": ([C.c_void_p], C.c_int),
+    "pcr_index_knn": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_index_hybrid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_index_radius_count": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p], C.c_int),
+    "pcr_index_radius_fill": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int], C.c_int),
 }
 
 _lib = None

@@ -25,6 +25,7 @@ PcrOptions &pcr_options() {
         if (const char *e = getenv("PCR_RADIUS_LIST_SELECT")) o.radius_list_select = atoi(e);
         if (const char *e = getenv("PCR_FEATNN_MUTUAL")) o.featnn_mutual = atoi(e);
         if (const char *e = getenv("PCR_ICP_SCALES")) o.icp_scales = atoi(e);
+        if (const char *e = getenv("PCR_SEARCH_SORT_QUERIES")) o.search_sort_queries = atoi(e);
     });
     return o;
 }
@@ -49,6 +50,7 @@ extern "C" int pcr_set_option(const char *name, long long value) {
     if (!strcmp(name, "arena_poison")) { o.arena_poison = (int)value; return PCR_OK; }
     if (!strcmp(name, "featnn_mutual")) { o.featnn_mutual = (int)value; return PCR_OK; }
     if (!strcmp(name, "icp_scales")) { o.icp_scales = (int)value; return PCR_OK; }
+    if (!strcmp(name, "search_sort_queries")) { o.search_sort_queries = (int)value; return PCR_OK; }
     return PCR_EINVAL;
 }
 

@@ -7,6 +7,7 @@ import numpy as _np
 from . import geometry as _g
 from . import io as _io
 from . import registration as _r
+from . import search as _s
 
 
 def _read_point_cloud(path):
@@ -19,8 +20,9 @@ def _read_point_cloud(path):
 
 geometry = SimpleNamespace(PointCloud=_g.PointCloud, KDTreeSearchParamKNN=_g.KDTreeSearchParamKNN,
                            KDTreeSearchParamRadius=_g.KDTreeSearchParamRadius,
-                           KDTreeSearchParamHybrid=_g.KDTreeSearchParamHybrid,
+                           KDTreeSearchParamHybrid=_g.KDTreeSearchParamHybrid, KDTreeFlann=_s.KDTreeFlann,
                            keypoint=SimpleNamespace(compute_iss_keypoints=_g.compute_iss_keypoints))
 utility = SimpleNamespace(Vector3dVector=lambda a: _np.asarray(a, dtype=_np.float64).reshape(-1, 3))
 io = SimpleNamespace(read_point_cloud=_read_point_cloud)
 pipelines = SimpleNamespace(registration=_r)
+core = SimpleNamespace(nns=SimpleNamespace(NearestNeighborSearch=_s.NearestNeighborSearch))
