@@ -518,6 +518,37 @@ typedef struct {
 int pcr_segment_plane(pcr_context *ctx, const float *xyz, int64_t n, double distance_threshold, const pcr_plane_params *params, double *plane4,
                       uint8_t *inlier_mask, int64_t *out_index, int64_t *out_n, pcr_plane_info *info);
 
+/* == PointCloud.farthest_point_down_sample(num_samples, start_index) (Open3D PointCloud::FarthestPointDownSample; the reference calls it nowhere).
+ *    Open3D is not at hand, so the loop is stated here as recalled and this statement is the specification; [O3D ?] marks what is recalled and
+ *    not pinned against a build of Open3D: the whole loop below, its tie order and what it does once no point is
+ *    away from the samples.  ONE sequential loop of num_samples dependent steps defines the answer, bit for bit and the same on every run; the
+ *    device may only reorder work that cannot change it.
+ *    DIST.  d^2(j, s) between rows j and s is taken in float64 on the float32 coordinates: differences, squares and sums in the order x, y, z,
+ *    each rounded once, no fused multiply-add (the rule of the search index above), so a host recomputation gives the same bits.
+ *    INIT.  dist_j = +inf for every row; a row with a non-finite coordinate instead has dist_j = -1, is never updated and is never chosen.
+ *    cur = start_index.
+ *    STEP i = 0 .. num_samples - 1.  sel[i] = cur.  For every finite row, dist_j = d^2 < dist_j ? d^2 : dist_j with d^2 = d^2(j, cur).
+ *    m = max_j dist_j, with m starting from 0.  If m > 0, cur becomes the SMALLEST index with dist_j == m ([O3D ?]: Open3D scans the rows in
+ *    ascending order with a strict >).  Otherwise cur stays: a cloud with no point away from its samples repeats the last index, as Open3D's
+ *    loop does [O3D ?].
+ *    RESULT.  out_index = sel, in selection order.  cover_dist2 = m after the last step: the largest squared distance of any finite row to the
+ *    subset (its square root is the cover radius).  out_dist2 (optional, n float64) = the final dist_j, -1 on non-finite rows.
+ *    ERRORS.  PCR_EINVAL, the message naming farthest_point_down_sample: num_samples < 0 or > n (Open3D raises too); start_index outside
+ *    0..n-1 when num_samples > 0; start_index naming a non-finite row; n above the int range; a null cloud with n > 0; a null out_index with
+ *    num_samples > 0.  num_samples == 0 returns PCR_OK and writes nothing.
+ *    Two forms of the loop give the same bits: one launch per step, and one persistent launch of co-resident workgroups that keep the cloud
+ *    in LDS and meet at a bounded barrier per step; if the barrier's wait runs out the call is repeated in the first form (fell_back). */
+typedef struct {
+    int32_t form;                     /* the form that produced the answer: 0 one launch per step, 1 one persistent launch */
+    int32_t workgroups;               /* of that form */
+    int32_t fell_back;                /* 1: the persistent launch gave up waiting and the step form redid the call */
+    double cover_dist2;               /* m after the last step */
+} pcr_fps_info;
+/* xyz: device, n x 3 float32.  out_index: device int64, num_samples entries.  out_dist2: optional, device, n float64.  info: optional, host.
+ * Runs on the context's stream with scratch from its arena; returns after the one read of the loop's small state record. */
+int pcr_farthest_point_sample(pcr_context *ctx, const float *xyz, int64_t n, int64_t num_samples, int64_t start_index, int64_t *out_index,
+                              double *out_dist2, pcr_fps_info *info);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.
@@ -579,7 +610,10 @@ int pcr_debug_plane_hypotheses(pcr_context *ctx, const float *xyz, int64_t n, do
  * bound it found; 0: both directions in full), "icp_scales" (1: in lockstep groups of small clouds every pair goes through its scales by itself;
  * 0: one lockstep loop per scale), "search_sort_queries" (-1: a k-nearest or hybrid search of an index takes a large batch of queries -- 131072 or more with k in
  * 9..64, 32768 or more with k above 64 -- in the Morton order of the queries, every other search in the caller's order; 0: always in the caller's
- * order; 1: always in Morton order).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
+ * order; 1: always in Morton order), "fps_form" (-1: pcr_farthest_point_sample picks its form by size; 0: one launch per step; 1: the persistent launch), "fps_wgs"
+ * (0: the persistent workgroups by size; else that many, at most one per compute unit and 256), "fps_timeout" (ticks of the 100 MHz wall clock
+ * a persistent workgroup waits at its barrier before the call falls back to the step form; -1: the default, that of PCR_FGR_MULTI_TIMEOUT;
+ * 0 forces the fall-back).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
  * scratch nobody wrote then follows the pattern).  Returns PCR_EINVAL for an unknown name. */
 int pcr_set_option(const char *name, long long value);
 /* Process-wide event counters (value, or -1 for an unknown name; reset != 0 clears it): how often a lockstep registro_FGR group fell back to

@@ -61,6 +61,10 @@ class PcrPlaneInfo(C.Structure):
                 ("fitness", C.c_double), ("inlier_rmse", C.c_double)]
 
 
+class PcrFpsInfo(C.Structure):
+    _fields_ = [("form", C.c_int32), ("workgroups", C.c_int32), ("fell_back", C.c_int32), ("cover_dist2", C.c_double)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -111,9 +115,10 @@ EXPORTS = [
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
     "pcr_iss_keypoints", "pcr_cluster_dbscan", "pcr_segment_plane", "pcr_debug_plane_hypotheses",
     "pcr_index_create", "pcr_index_destroy", "pcr_index_knn", "pcr_index_hybrid", "pcr_index_radius_count", "pcr_index_radius_fill",
+    "pcr_farthest_point_sample",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation and the search index (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index and the farthest point sampler (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -133,6 +138,7 @@ QUERY_PROTOTYPES = {
     "pcr_index_hybrid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_index_radius_count": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p], C.c_int),
     "pcr_index_radius_fill": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int], C.c_int),
+    "pcr_farthest_point_sample": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PcrFpsInfo)], C.c_int),
 }
 
 _lib = None

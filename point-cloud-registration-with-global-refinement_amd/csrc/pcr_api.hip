@@ -26,6 +26,9 @@ PcrOptions &pcr_options() {
         if (const char *e = getenv("PCR_FEATNN_MUTUAL")) o.featnn_mutual = atoi(e);
         if (const char *e = getenv("PCR_ICP_SCALES")) o.icp_scales = atoi(e);
         if (const char *e = getenv("PCR_SEARCH_SORT_QUERIES")) o.search_sort_queries = atoi(e);
+        if (const char *e = getenv("PCR_FPS_FORM")) o.fps_form = atoi(e);
+        if (const char *e = getenv("PCR_FPS_WGS")) o.fps_wgs = atoi(e);
+        if (const char *e = getenv("PCR_FPS_TIMEOUT")) o.fps_timeout = atoi(e);
     });
     return o;
 }
@@ -51,6 +54,9 @@ extern "C" int pcr_set_option(const char *name, long long value) {
     if (!strcmp(name, "featnn_mutual")) { o.featnn_mutual = (int)value; return PCR_OK; }
     if (!strcmp(name, "icp_scales")) { o.icp_scales = (int)value; return PCR_OK; }
     if (!strcmp(name, "search_sort_queries")) { o.search_sort_queries = (int)value; return PCR_OK; }
+    if (!strcmp(name, "fps_form")) { o.fps_form = (int)value; return PCR_OK; }
+    if (!strcmp(name, "fps_wgs")) { o.fps_wgs = (int)value; return PCR_OK; }
+    if (!strcmp(name, "fps_timeout")) { o.fps_timeout = (int)value; return PCR_OK; }
     return PCR_EINVAL;
 }
 

@@ -249,6 +249,24 @@ class PointCloud:
         plane, index, _ = _segment_plane(self, distance_threshold, ransac_n, num_iterations, probability, seed)
         return plane, index.cpu().numpy().tolist()
 
+    def farthest_point_down_sample(self, num_samples: int, start_index: int = 0) -> "PointCloud":
+        """``PointCloud.farthest_point_down_sample``: ``num_samples`` points that cover the cloud evenly, in selection order -- the first is
+        ``start_index``, every further one the point farthest from those chosen so far, the smallest index on a tie (the rules:
+        include/pcr_hip.h).  Normals, colours and covariances travel with the points.  ``num_samples == 0`` gives an empty cloud,
+        ``num_samples == len(self)`` a copy in the input's order; more samples than points, or a ``start_index`` outside the cloud or on a
+        row with a non-finite coordinate, raise ``RuntimeError`` like Open3D."""
+        n = len(self)
+        num_samples, start_index = int(num_samples), int(start_index)
+        if num_samples < 0 or num_samples > n:
+            raise RuntimeError(f"farthest_point_down_sample: Illegal number of samples: {num_samples}, must be in 0..{n}")
+        if num_samples == 0:
+            return PointCloud()
+        if start_index < 0 or start_index >= n:
+            raise RuntimeError(f"farthest_point_down_sample: Illegal start index: {start_index}, must be in 0..{n - 1}")
+        if num_samples == n:
+            return self.select_by_index(_torch().arange(n, dtype=_torch().int64, device="cuda"))
+        return self.select_by_index(_farthest_point_sample(self, num_samples, start_index)[0])
+
     def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
         """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
         if every_k_points < 1:
@@ -408,6 +426,31 @@ def _segment_plane(cloud: PointCloud, distance_threshold: float, ransac_n: int =
     out = {k: getattr(info, k) for k, _ in _lib.PcrPlaneInfo._fields_}
     out["mask"] = mask[:n].bool()
     return np.array(plane, dtype=np.float64), idx[: m.value], out
+
+
+def _farthest_point_sample(cloud: PointCloud, num_samples: int, start_index: int = 0):
+    """``pcr_farthest_point_sample`` -> ``(indices as a torch int64 tensor on the device, in selection order, info)``; ``info`` is a dict with
+    ``form`` (0: one launch per step, 1: the persistent launch), ``workgroups``, ``fell_back``, ``cover_dist2``, ``cover_radius`` (its square
+    root: the largest distance of any point to the subset) and ``dist2`` (the final squared distance of every row to the subset, ``(n,)``
+    torch float64 on the device, -1 on rows with a non-finite coordinate): the form a pipeline that stays on the device builds on."""
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n, k = len(cloud), int(num_samples)
+    idx = torch.empty(max(min(k, n), 1), dtype=torch.int64, device="cuda")
+    dist2 = torch.full((max(n, 1),), -1.0, dtype=torch.float64, device="cuda")
+    info = _lib.PcrFpsInfo()
+    ctx.check(ctx.lib.pcr_farthest_point_sample(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), C.c_int64(k), C.c_int64(int(start_index)), _ptr(idx),
+                                                _ptr(dist2), C.byref(info)), "farthest_point_down_sample")
+    out = {f: getattr(info, f) for f, _ in _lib.PcrFpsInfo._fields_}
+    out["cover_radius"] = float(np.sqrt(info.cover_dist2))
+    out["dist2"] = dist2[:n]
+    return idx[:k], out
+
+
+def farthest_point_indices(cloud: PointCloud, num_samples: int, start_index: int = 0) -> np.ndarray:
+    """The rows ``PointCloud.farthest_point_down_sample`` selects, int64, in selection order: what picks the feature rows of the samples
+    (``Feature.select_by_index``) next to ``cloud.select_by_index``."""
+    return _farthest_point_sample(cloud, num_samples, start_index)[0].cpu().numpy()
 
 
 # ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
