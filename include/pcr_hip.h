@@ -549,6 +549,56 @@ typedef struct {
 int pcr_farthest_point_sample(pcr_context *ctx, const float *xyz, int64_t n, int64_t num_samples, int64_t start_index, int64_t *out_index,
                               double *out_dist2, pcr_fps_info *info);
 
+/* == PointCloud.orient_normals_consistent_tangent_plane(k), orient_normals_to_align_with_direction, orient_normals_towards_camera_location and
+ *    normalize_normals (Open3D PointCloud::OrientNormalsConsistentTangentPlane and its relatives in EstimateNormals.cpp; the reference calls
+ *    none of them).  estimate_normals leaves every normal with the sign its eigen-solver gave it; these make the signs agree.  Open3D is not
+ *    at hand and its Kruskal sorts with an unstable sort, so the statement below is the specification; [O3D ?] marks what is recalled from
+ *    Open3D and not pinned against a build of it: the Riemannian graph as EMST plus k-NN graph with weight 1 - |n_i . n_j| [O3D ?], the root
+ *    as the row with the largest z, turned to +z [O3D ?], the breadth-first walk that negates a child iff (oriented parent) . child < 0
+ *    [O3D ?], and that the k of SearchKNN counts the query row itself [O3D ?].
+ *    DIST.  d^2(i, j) follows the rule of the search index: float64 on the float32 coordinates, differences, squares and sums in the order
+ *    x, y, z, each rounded once, no fused multiply-add.
+ *    DOT.  c(i, j) = (nx_i nx_j + ny_i ny_j) + nz_i nz_j in float64 on the float32 normals, each operation rounded once.  w(i, j) = 1 - |c(i, j)|.
+ *    ORDER.  An undirected edge {i, j} has the key (weight, lo, hi), lo = min(i, j), hi = max(i, j) in the caller's row numbers; keys are
+ *    compared lexicographically, weights numerically.  This is a strict total order, so every "minimum spanning tree" below is unique and
+ *    does not depend on the algorithm that finds it.  Two copies of the same edge are the same edge.
+ *    EMST.  The minimum spanning tree of the complete graph under ORDER with weight d^2: n - 1 edges.  Duplicated points give d^2 = 0 edges,
+ *    ordered by (lo, hi).
+ *    KNN.  For row i, the first k rows of the whole cloud ordered by (d^2(i, .), index); row i takes part in that ordering and is then
+ *    skipped.  k >= n means every row, k = 0 none.
+ *    GRAPH.  E = EMST + { {i, j} : j in KNN(i) } with weight w(i, j): connected, because it contains the EMST.
+ *    TREE.  The minimum spanning tree of (rows, E) under ORDER with weight w.
+ *    ROOT.  r = the smallest row with the largest z (float32 comparison).  flip_r = (nz_r < 0).
+ *    PROPAGATE.  For a tree edge s(i, j) = (c(i, j) < 0); flip_v = flip_r XOR the XOR of s over the tree path r -> v.  That is the
+ *    breadth-first walk; a dot product of exactly 0 flips nothing in either direction.  The tree and every flip_v depend only on |c| and on
+ *    the root rule, so the output does not depend on the input signs.
+ *    RESULT.  Where flip_v holds all three components of the row are negated, otherwise the row's bits are untouched.  n = 0: PCR_OK,
+ *    nothing is written.  n = 1: the root rule only.
+ *    ERRORS.  PCR_EINVAL, the message naming orient_normals_consistent_tangent_plane: a null cloud or null normals with n > 0; n above the int
+ *    range; k < 0 or above the search index's limit (200); any non-finite coordinate or normal component (the message says "non-finite").
+ *    On error nothing is written.
+ *    Both trees are found by Boruvka rounds (csrc/pcr_orient.hip; at most ceil(log2 n) each, the host reads one small record per round).
+ *    The element-wise calls use float64 on the float32 data, sums in the order x, y, z.  direction(ref) [O3D ?]: a zero normal becomes ref
+ *    rounded to float32, otherwise the normal is negated iff n . ref < 0.  camera(loc) [O3D ?]: v = loc - p_i; a zero normal becomes v / |v|,
+ *    or (0, 0, 1) when v is zero, otherwise the normal is negated iff n . v < 0.  normalize [O3D ?]: n / |n|, a zero normal stays zero. */
+typedef struct {
+    int32_t emst_rounds, tree_rounds; /* Boruvka rounds of the two trees */
+    int64_t walked_rows;              /* rows, over all EMST rounds, that walked the octree: their k-NN list held no row of another component */
+    int64_t n_flipped;                /* rows negated */
+    int64_t root;                     /* r (-1: none, pcr_euclidean_mst) */
+} pcr_orient_info;
+/* EMST alone (single-linkage clustering reads it directly).  xyz: device, n x 3 float32.  edges: device int32, (n - 1) x 2, rows (lo, hi) ascending
+ * by (lo, hi).  d2: optional, device, n - 1 float64, aligned with edges.  info: optional, host.  n <= 1 writes nothing.  PCR_EINVAL (the message naming
+ * euclidean_minimum_spanning_tree) for a null cloud with n > 0, null edges with n > 1, n above the int range or a non-finite coordinate. */
+int pcr_euclidean_mst(pcr_context *ctx, const float *xyz, int64_t n, int32_t *edges, double *d2, pcr_orient_info *info);
+/* normals: device, n x 3 float32, updated in place.  flipped: optional, device, n bytes (flip_v).  tree_edges: optional, device int32, (n - 1) x 2, the
+ * layout of pcr_euclidean_mst.  info: optional, host. */
+int pcr_orient_normals_tangent_plane(pcr_context *ctx, const float *xyz, float *normals, int64_t n, int k, uint8_t *flipped, int32_t *tree_edges,
+                                     pcr_orient_info *info);
+/* mode 0: direction(ref), xyz may be null; mode 1: camera(ref).  ref: host, 3 float64. */
+int pcr_orient_normals(pcr_context *ctx, const float *xyz, float *normals, int64_t n, int mode, const double *ref);
+int pcr_normalize_normals(pcr_context *ctx, float *normals, int64_t n);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

@@ -10,7 +10,7 @@ from .functions import (Coarse_to_fine_FGR_M_GICP, GICP_robusto, Multiscale_GICP
                         create_scales, extract_eigen_features, knn_distance_table, radius_from_cloud_pair, registro_FGR, remove_plane, remove_small_clusters,
                         script1, script2)
 from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, PointCloud, compute_iss_keypoints,  # noqa: F401
-                       farthest_point_indices, iss_keypoint_indices)
+                       euclidean_minimum_spanning_tree, farthest_point_indices, iss_keypoint_indices)
 from .search import KDTreeFlann, NearestNeighborSearch  # noqa: F401
 
 __version__ = "0.1.0"

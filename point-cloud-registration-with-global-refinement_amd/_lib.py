@@ -65,6 +65,10 @@ class PcrFpsInfo(C.Structure):
     _fields_ = [("form", C.c_int32), ("workgroups", C.c_int32), ("fell_back", C.c_int32), ("cover_dist2", C.c_double)]
 
 
+class PcrOrientInfo(C.Structure):
+    _fields_ = [("emst_rounds", C.c_int32), ("tree_rounds", C.c_int32), ("walked_rows", C.c_int64), ("n_flipped", C.c_int64), ("root", C.c_int64)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -116,9 +120,10 @@ EXPORTS = [
     "pcr_iss_keypoints", "pcr_cluster_dbscan", "pcr_segment_plane", "pcr_debug_plane_hypotheses",
     "pcr_index_create", "pcr_index_destroy", "pcr_index_knn", "pcr_index_hybrid", "pcr_index_radius_count", "pcr_index_radius_fill",
     "pcr_farthest_point_sample",
+    "pcr_euclidean_mst", "pcr_orient_normals_tangent_plane", "pcr_orient_normals", "pcr_normalize_normals",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index and the farthest point sampler (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler and the normal orientation (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -139,6 +144,10 @@ QUERY_PROTOTYPES = {
     "pcr_index_radius_count": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p], C.c_int),
     "pcr_index_radius_fill": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int], C.c_int),
     "pcr_farthest_point_sample": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PcrFpsInfo)], C.c_int),
+    "pcr_euclidean_mst": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PcrOrientInfo)], C.c_int),
+    "pcr_orient_normals_tangent_plane": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PcrOrientInfo)], C.c_int),
+    "pcr_orient_normals": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)], C.c_int),
+    "pcr_normalize_normals": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
 }
 
 _lib = None

@@ -243,6 +243,10 @@ int pcr_emit_kept_rows(pcr_context *ctx, const float *xyz, int64_t n, const uint
 // distance of every point of a sorted cloud to its nearest other point, float64, to the caller's rows (pcr_query.hip); enqueues only
 int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *perm, double *dist_caller);
 
+// ---- the k-best kernels of the search index (pcr_search.hip) over a sorted cloud of the caller's whose points carry their caller row in w: rows of k
+// caller rows ordered by (float64 d^2, caller row), -1 / +inf beyond the cloud's size; the octets take the queries in the order qperm (optional); enqueues only
+int pcr_dev_tagged_knn(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, int k, int32_t *idx, double *d2);
+
 int pcr_registro_fgr_impl(pcr_context *ctx, const float *src_xyz, const float *src_prior, int64_t ns, const float *tgt_xyz, const float *tgt_prior, int64_t nt,
                           const pcr_fgr_params *p, float *src_normals_out, float *tgt_normals_out, pcr_result *result, int32_t *correspondences);
 // registro_FGR of G pairs through the same launches (pcr_fgr.hip); 1 = declined (sizes / parameters): run the pairs one by one

@@ -378,6 +378,13 @@ static int launch_index_knn(pcr_context *ctx, const SearchArgs &a) {
     return PCR_OK;
 }
 
+int pcr_dev_tagged_knn(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, int k, int32_t *idx, double *d2) {
+    if (k < 1 || k > SRCH_MAX_K || m < 1 || m > SRCH_MAX_POINTS) { ctx->err = "tagged_knn: k or query count out of range"; return PCR_EINVAL; }
+    SearchArgs a; std::memset(&a, 0, sizeof a);
+    a.t = oct_view(c); a.q = query_xyz; a.m = (int)m; a.qperm = qperm; a.k = k; a.idx = idx; a.d2 = d2;
+    return launch_index_knn<false>(ctx, a);
+}
+
 extern "C" int pcr_index_knn(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, int k, int32_t *idx, double *d2) {
     return pcr_api_call(ctx, [&]() -> int {
     PCR_TRY(search_check(ctx, index, query_xyz, m, "index_knn"));

@@ -267,6 +267,47 @@ class PointCloud:
             return self.select_by_index(_torch().arange(n, dtype=_torch().int64, device="cuda"))
         return self.select_by_index(_farthest_point_sample(self, num_samples, start_index)[0])
 
+    def normalize_normals(self) -> "PointCloud":
+        """``PointCloud.normalize_normals``: every normal divided by its length (float64 on the float32 components, rounded once); a zero
+        normal stays zero.  In place; returns the cloud."""
+        if self.has_normals():
+            ctx = _lib.Context.current()
+            ctx.check(ctx.lib.pcr_normalize_normals(ctx.handle, _ptr(self._nrm), C.c_int64(len(self))), "normalize_normals")
+        return self
+
+    def _need_normals(self, what):
+        if not self.has_normals():
+            raise RuntimeError(f"{what}: No normals in the PointCloud. Call estimate_normals() first.")
+
+    def orient_normals_to_align_with_direction(self, orientation_reference=(0.0, 0.0, 1.0)) -> None:
+        """``PointCloud.orient_normals_to_align_with_direction``: a normal is negated iff its dot product with ``orientation_reference`` is
+        negative; a zero normal becomes the reference (the rules: include/pcr_hip.h).  In place."""
+        self._need_normals("orient_normals_to_align_with_direction")
+        self._orient_elementwise(0, orientation_reference, "orient_normals_to_align_with_direction")
+
+    def orient_normals_towards_camera_location(self, camera_location=(0.0, 0.0, 0.0)) -> None:
+        """``PointCloud.orient_normals_towards_camera_location``: a normal is negated iff it points away from ``camera_location`` as seen from
+        its point; a zero normal becomes the unit vector towards the camera (the rules: include/pcr_hip.h).  In place."""
+        self._need_normals("orient_normals_towards_camera_location")
+        self._orient_elementwise(1, camera_location, "orient_normals_towards_camera_location")
+
+    def _orient_elementwise(self, mode, ref, what):
+        ctx = _lib.Context.current()
+        r = (C.c_double * 3)(*np.asarray(ref, dtype=np.float64).reshape(3).tolist())
+        ctx.check(ctx.lib.pcr_orient_normals(ctx.handle, _ptr(self.device_xyz()), _ptr(self._nrm), C.c_int64(len(self)), C.c_int(mode), r), what)
+
+    def orient_normals_consistent_tangent_plane(self, k: int, lambda_penalty: float = 0.0, cos_alpha_tol: float = 1.0) -> None:
+        """``PointCloud.orient_normals_consistent_tangent_plane``: the signs of the normals made consistent by propagation along the minimum
+        spanning tree of the Riemannian graph (Euclidean minimum spanning tree plus ``k``-nearest-neighbour graph, weight 1 - |n_i . n_j|) from
+        the highest point, which is turned to +z (the rules: include/pcr_hip.h).  The result does not depend on the signs the normals come
+        with.  In place; points, colours and covariances are untouched.  Only the defaults of ``lambda_penalty`` and ``cos_alpha_tol`` are
+        supported (Open3D's later penalty form is not built)."""
+        if float(lambda_penalty) != 0.0:
+            raise ValueError("orient_normals_consistent_tangent_plane: lambda_penalty other than 0.0 is not supported")
+        if float(cos_alpha_tol) != 1.0:
+            raise ValueError("orient_normals_consistent_tangent_plane: cos_alpha_tol other than 1.0 is not supported")
+        _orient_normals_tangent_plane(self, k)
+
     def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
         """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
         if every_k_points < 1:
@@ -451,6 +492,38 @@ def farthest_point_indices(cloud: PointCloud, num_samples: int, start_index: int
     """The rows ``PointCloud.farthest_point_down_sample`` selects, int64, in selection order: what picks the feature rows of the samples
     (``Feature.select_by_index``) next to ``cloud.select_by_index``."""
     return _farthest_point_sample(cloud, num_samples, start_index)[0].cpu().numpy()
+
+
+def _orient_normals_tangent_plane(cloud: PointCloud, k: int):
+    """``pcr_orient_normals_tangent_plane`` on the cloud's normals, in place -> ``(flipped mask (n,) torch bool on the device, info)``; ``info`` is a
+    dict with ``tree_edges`` (the propagation tree, ``(n - 1, 2)`` torch int64 on the device, rows (lo, hi) ascending) and the fields of
+    ``pcr_orient_info``: ``emst_rounds``, ``tree_rounds``, ``walked_rows``, ``n_flipped``, ``root``."""
+    if not cloud.has_normals():
+        raise RuntimeError("orient_normals_consistent_tangent_plane: No normals in the PointCloud. Call estimate_normals() first.")
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n = len(cloud)
+    flipped = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    edges = torch.zeros((max(n - 1, 1), 2), dtype=torch.int32, device="cuda")
+    info = _lib.PcrOrientInfo()
+    ctx.check(ctx.lib.pcr_orient_normals_tangent_plane(ctx.handle, _ptr(cloud.device_xyz()), _ptr(cloud._nrm), C.c_int64(n), C.c_int(int(k)), _ptr(flipped),
+                                                       _ptr(edges), C.byref(info)), "orient_normals_consistent_tangent_plane")
+    out = {f: getattr(info, f) for f, _ in _lib.PcrOrientInfo._fields_}
+    out["tree_edges"] = edges[: max(n - 1, 0)].to(torch.int64)
+    return flipped[:n].bool(), out
+
+
+def euclidean_minimum_spanning_tree(cloud: PointCloud):
+    """The Euclidean minimum spanning tree of the cloud (``pcr_euclidean_mst``) -> ``(edges (n - 1, 2) torch int64 on the device, rows (lo, hi)
+    ascending by (lo, hi), d2 (n - 1,) torch float64 on the device)``: unique under the order (d^2, lo, hi) of include/pcr_hip.h; what
+    single-linkage clustering reads."""
+    ctx = _lib.Context.current()
+    torch = _torch()
+    n = len(cloud)
+    edges = torch.zeros((max(n - 1, 1), 2), dtype=torch.int32, device="cuda")
+    d2 = torch.zeros(max(n - 1, 1), dtype=torch.float64, device="cuda")
+    ctx.check(ctx.lib.pcr_euclidean_mst(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), _ptr(edges), _ptr(d2), None), "euclidean_minimum_spanning_tree")
+    return edges[: max(n - 1, 0)].to(torch.int64), d2[: max(n - 1, 0)]
 
 
 # ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
