@@ -622,6 +622,15 @@ int pcr_debug_knn(pcr_context *ctx, const float *xyz, int64_t n, int k, double r
  * in the k-best kernel's slot layout (scan all k slots).  A ball of more than k points lists its k nearest by (float64 d^2, caller index). */
 int pcr_debug_radius_lists(pcr_context *ctx, int count, const float *const *xyz, const int64_t *n, int k, double radius,
                            int32_t *const *idx, int32_t *const *cnt);
+/* the voxel grids of `count` clouds (xyz[c], optional attr[c]: n[c] x 3 float32, device; n[c] > 0) at n_scales voxel sizes (1..8), through the
+ * form of the voxel pass that `form` names: 0 the one-scale pass, cloud by cloud and scale by scale (pcr_voxel_down_sample); 1 all scales of a
+ * cloud in one key / sort / scan / mean pass, cloud by cloud (pcr_multiscale_gicp); 2 all clouds and scales in one pass (the lockstep groups of
+ * pcr_register_pairs_plan; count <= 64).  Bounds are taken as those paths take them.  out_xyz[c * n_scales + s] (and out_attr[...] when attr is
+ * given): n[c] x 3 float32 (device), the packed rows of cloud c at scale s in the pass's own (Morton) order; out_n[c * n_scales + s] (host): the
+ * rows.  *taken (host) = 0 when a merged form declines (fewer than two scales, or the scale index does not fit above the Morton bits of some
+ * cloud): nothing is written then.                                                                                                          */
+int pcr_debug_voxel_grids(pcr_context *ctx, int count, const float *const *xyz, const float *const *attr, const int64_t *n, const double *voxels,
+                          int n_scales, int form, float *const *out_xyz, float *const *out_attr, int32_t *out_n, int *taken);
 /* one GICP linearisation at pose T: search + A.6 sums. JTJ36, JTr6, stats3 = {count, sum d^2, sum r^2} (host) */
 int pcr_debug_gicp_linearize(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src,
                              const float *tgt_xyz, const float *tgt_normals, int64_t n_tgt, double max_dist,

@@ -113,7 +113,7 @@ EXPORTS = [
     "pcr_registration_generalized_icp", "pcr_multiscale_gicp", "pcr_evaluate_registration", "pcr_information_matrix",
     "pcr_compute_fpfh_feature", "pcr_registration_fgr", "pcr_debug_knn", "pcr_debug_gicp_linearize",
     "pcr_profile_enable", "pcr_profile_read", "pcr_registration_generalized_icp_cov", "pcr_register_pairs", "pcr_pool_profile",
-    "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists",
+    "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists", "pcr_debug_voxel_grids",
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",

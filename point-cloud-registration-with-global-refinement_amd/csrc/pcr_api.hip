@@ -425,6 +425,53 @@ extern "C" int pcr_debug_radius_lists(pcr_context *ctx, int count, const float *
     });
 }
 
+// the voxel grids of `count` clouds at n_scales sizes through one of the three forms of the pass (0 pcr_dev_voxel, 1 pcr_dev_voxel_multi cloud by
+// cloud, 2 pcr_dev_voxel_multi_batch), packed with the helpers of pcr_voxel_down_sample: what tests/test_gpu_voxel_grid.py compares
+extern "C" int pcr_debug_voxel_grids(pcr_context *ctx, int count, const float *const *xyz, const float *const *attr, const int64_t *n, const double *voxels,
+                                     int n_scales, int form, float *const *out_xyz, float *const *out_attr, int32_t *out_n, int *taken) {
+    return pcr_api_call(ctx, [&]() -> int {
+    if (count < 1 || count > 64 || n_scales < 1 || n_scales > 8 || form < 0 || form > 2 || !xyz || !n || !voxels || !out_xyz || !out_n || !taken) return PCR_EINVAL;
+    if (attr && !out_attr) return PCR_EINVAL;
+    *taken = 0;
+    const size_t K = (size_t)count * n_scales;
+    size_t bytes = 1 << 20;
+    for (int c = 0; c < count; c++) {
+        if (n[c] <= 0 || n[c] > 0x7fffffff / 4 / n_scales || !xyz[c] || (attr && !attr[c])) return PCR_EINVAL;
+        for (int s = 0; s < n_scales; s++) if (!out_xyz[c * n_scales + s] || (attr && !out_attr[c * n_scales + s])) return PCR_EINVAL;
+        bytes += pcr_scratch_bytes_for(n[c]) + (size_t)n_scales * ((size_t)n[c] * 48 + 4096) + pcr_sort_temp_bytes((size_t)n[c] * n_scales) + (size_t)n[c] * n_scales * 40;
+    }
+    PCR_TRY(pcr_arena_reserve(ctx, bytes));
+    std::vector<double> b6((size_t)count * 6);
+    if (form == 2) PCR_TRY(pcr_dev_bounds_batch(ctx, count, xyz, n, b6.data()));
+    else for (int c = 0; c < count; c++) PCR_TRY(pcr_dev_bounds(ctx, xyz[c], n[c], &b6[6 * (size_t)c]));
+    std::vector<DevCloud> v(K);
+    for (int c = 0; c < count; c++)
+        for (int s = 0; s < n_scales; s++) PCR_TRY(pcr_alloc_cloud(ctx, &v[(size_t)c * n_scales + s], (int)n[c], attr != nullptr, false));
+    if (form == 0) {
+        for (int c = 0; c < count; c++)
+            for (int s = 0; s < n_scales; s++) PCR_TRY(pcr_dev_voxel(ctx, xyz[c], attr ? attr[c] : nullptr, n[c], &b6[6 * (size_t)c], voxels[s], &v[(size_t)c * n_scales + s]));
+    } else if (form == 1) {
+        for (int c = 0; c < count; c++) {
+            bool merged = false;
+            PCR_TRY(pcr_dev_voxel_multi(ctx, xyz[c], attr ? attr[c] : nullptr, n[c], &b6[6 * (size_t)c], voxels, n_scales, &v[(size_t)c * n_scales], &merged));
+            if (!merged) return PCR_OK;                       // (nothing reaches the caller's buffers before every cloud has been taken)
+        }
+    } else {
+        bool merged = false;
+        PCR_TRY(pcr_dev_voxel_multi_batch(ctx, count, xyz, attr, n, b6.data(), voxels, n_scales, v.data(), &merged));
+        if (!merged) return PCR_OK;
+    }
+    for (size_t k = 0; k < K; k++) {
+        PCR_TRY(pcr_dev_pack_f4_to_f3(ctx, v[k].pts, v[k].n, v[k].cap, out_xyz[k]));
+        if (attr) PCR_TRY(pcr_dev_pack_f4_to_f3(ctx, v[k].nrm, v[k].n, v[k].cap, out_attr[k]));
+        PCR_HIP_CHECK(ctx, hipMemcpyAsync(&out_n[k], v[k].n, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *taken = 1;
+    return PCR_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------------- registration API
 static int check_T(pcr_context *ctx, const double *T) {
     if (!T) return PCR_EINVAL;
