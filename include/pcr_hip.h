@@ -468,6 +468,68 @@ int pcr_registration_ransac_feature_matching(pcr_context *ctx, const float *src_
                                              double max_distance, const pcr_ransac_params *params, pcr_result *result, int32_t *correspondences,
                                              pcr_ransac_info *info);
 
+/* == TransformationEstimationPointToPoint / PointToPlane / ForGeneralizedICP .compute_transformation(source, target, corres) and
+ *    .compute_rmse(source, target, corres) (ALL_FUNCTIONS.py:438-439, registro_manual: picked point pairs give the starting pose of a registration).
+ *    One fit, or one error figure, over a correspondence list the caller holds.  This statement is the specification.
+ *    LIST.  corres: device int32 [n_corres x 2]; row (i, j) pairs source point i with target point j.  The float32 coordinates are widened to
+ *    float64; the source is read as given (no pose is applied).  There is NO distance test: every row counts, as in Open3D.  A row may repeat a
+ *    source or a target index, and the list may be shorter or longer than n_src: no buffer is sized by n_src.
+ *    n_corres == 0: the identity and RMSE 0, not an error.  An index outside [0, n_src) or [0, n_tgt): PCR_EINVAL with a message; a kernel of its
+ *    own checks every row, and its count is on the host before any row is read.
+ *    SUMS.  Float64, in an order that depends on the list and on the launch geometry only; no floating-point atomics; the same call gives the same
+ *    bits on every run.
+ *    POINT TO POINT.  T = Eigen::umeyama of the rows (the fit of pcr_registration_icp's update; a scaled pose when with_scaling), the moments
+ *    taken about the target point of row 0 so that they do not cancel far from the origin.  RMSE = sqrt(sum |s - t|^2 / C).  Rows that do not
+ *    determine a rotation (one row, collinear rows) give what the fit gives on them -- for one row the translation s -> t --, as Eigen does;
+ *    with_scaling on source points without spread divides by a zero variance.
+ *    POINT TO PLANE.  With n the target normal AS STORED (not normalised): r = (s - t).n, J = [s x n, n], w = the kernel's weight of r (L2: 1,
+ *    L1: 1 / |r|, GM: k / (k + r^2)^2), JTJ = sum w J^T J, JTr = sum w J r, solved as the loop solves it (LDLT, pivoted when a pivot is not
+ *    positive), the pose Rz Ry Rx and the translation.  A system that cannot be solved gives the identity, and so does a target without normals
+ *    (Open3D).  RMSE = sqrt(sum r^2 / C), 0 without target normals.
+ *    GENERALIZED ICP.  Both clouds carry covariances (cov6 = xx,xy,xz,yy,yz,zz, float32): the rows of pcr_registration_generalized_icp_cov at
+ *    T = identity, M = Cs + Ct, W = M^(-1/2), three rows W (s - t) per pair, each weighted by the kernel.  Neither carries covariances and both
+ *    carry normals: the rows of pcr_registration_generalized_icp at T = identity (normals normalised, e1 when n.x < -0.99, covariance
+ *    I - (1 - epsilon) n n^T).  Any other case: the identity, what Open3D returns without covariances.  RMSE = sqrt(sum |s - t|^2 / C): Open3D's
+ *    GICP RMSE is Euclidean.
+ *    T16 and rmse are host pointers; the calls return when they are written. */
+typedef enum { PCR_EST_POINT_TO_POINT = 1, PCR_EST_POINT_TO_PLANE = 2, PCR_EST_GENERALIZED_ICP = 3 } pcr_estimation_kind;
+typedef struct {
+    int32_t kind;             /* pcr_estimation_kind */
+    int32_t with_scaling;     /* point-to-point */
+    int32_t loss;             /* point-to-plane, GICP: pcr_loss_kind of the robust kernel */
+    double loss_k;            /* GMLoss k */
+    double epsilon;           /* GICP with normals: covariance regulariser, 1e-3 */
+} pcr_estimation;
+int pcr_estimation_compute_transformation(pcr_context *ctx, const pcr_estimation *estimation, const float *src_xyz, const float *src_normals,
+                                          const float *src_cov6, int64_t n_src, const float *tgt_xyz, const float *tgt_normals, const float *tgt_cov6,
+                                          int64_t n_tgt, const int32_t *corres, int64_t n_corres, double *T16);
+int pcr_estimation_compute_rmse(pcr_context *ctx, const pcr_estimation *estimation, const float *src_xyz, const float *src_normals,
+                                const float *src_cov6, int64_t n_src, const float *tgt_xyz, const float *tgt_normals, const float *tgt_cov6,
+                                int64_t n_tgt, const int32_t *corres, int64_t n_corres, double *rmse);
+
+/* == correspondences_from_features(source_features, target_features, mutual_filter, mutual_consistency_ratio) (Open3D 0.17 and later): the list
+ *    the feature forms of RANSAC and FGR match on.  Row i of the source is paired with its nearest target row: the smallest sum (a_k - b_k)^2 in
+ *    float64 over the float32 features, ties to the smaller index (the exact search of pcr_registration_fgr).  Without mutual_filter: rows
+ *    (i, nearest(i)) for every source row, in source order.  With it: only the rows whose target row points back, provided their count is
+ *    >= (int)(mutual_consistency_ratio * n_src); otherwise all rows (Open3D; its default ratio is 0.1).  A ratio of 0 always returns the mutual
+ *    list, even an empty one.  feature_dim must be 33 (FPFH); any other dimension, a negative or non-finite ratio: PCR_EINVAL.
+ *    corres: device int32, capacity n_src x 2; *n_corres (host) = rows written.  An empty cloud on either side gives 0 rows. */
+int pcr_correspondences_from_features(pcr_context *ctx, const float *src_feat, int64_t n_src, const float *tgt_feat, int64_t n_tgt, int feature_dim,
+                                      int mutual_filter, double mutual_consistency_ratio, int32_t *corres, int64_t *n_corres);
+
+/* == registration_fgr_based_on_correspondence(source, target, corres, option): pcr_registration_fgr from the point where it holds its
+ *    cross-checked list of feature matches, with the caller's list in that place (rows (source index, target index), device int32
+ *    [n_corres x 2], checked as for the estimators above).  Both clouds are normalised as there.  With option.tuple_test (and
+ *    maximum_tuple_count > 0; < 0 = the per-pair rule of pcr_registration_fgr) the tuple test draws its 100 * n_corres trials from the list in
+ *    its given order with the same sampler and seed, so that a list equal to the feature form's gives the feature form's bits; otherwise every
+ *    row goes to the optimiser, for any pair of cloud sizes.  [O3D ?] Open3D's own order of the rows inside this function (it may swap the
+ *    clouds by size as the feature form does) is not pinned against a build of it.  Fewer than 10 rows for the optimiser: the identity pose.
+ *    result / correspondences (optional, capacity n_src rows): evaluate_registration at maximum_correspondence_distance under the pose found,
+ *    as in the feature form. */
+int pcr_registration_fgr_correspondence(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt,
+                                        const int32_t *corres, int64_t n_corres, const pcr_fgr_option *option, pcr_result *result,
+                                        int32_t *correspondences);
+
 /* == PointCloud.segment_plane (Open3D PointCloud::SegmentPlane; the reference calls it nowhere and Open3D's own result depends on its random
  *    engine and thread timing, so the algorithm is stated here and this statement is the specification).  [O3D ?] marks what is recalled from
  *    SegmentPlane / GetPlaneFromPoints and not pinned against a build of Open3D.  ONE sequential loop over hypotheses i = 0, 1, ... defines the

@@ -52,6 +52,13 @@ class PcrRansacInfo(C.Structure):
     _fields_ = [("iterations_run", C.c_int64), ("best_iteration", C.c_int64), ("n_valid", C.c_int64), ("n_corres", C.c_int64)]
 
 
+EST_POINT_TO_POINT, EST_POINT_TO_PLANE, EST_GENERALIZED_ICP = 1, 2, 3          # pcr_estimation_kind
+
+
+class PcrEstimation(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("with_scaling", C.c_int32), ("loss", C.c_int32), ("loss_k", C.c_double), ("epsilon", C.c_double)]
+
+
 class PcrPlaneParams(C.Structure):
     _fields_ = [("ransac_n", C.c_int32), ("num_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint64)]
 
@@ -121,9 +128,10 @@ EXPORTS = [
     "pcr_index_create", "pcr_index_destroy", "pcr_index_knn", "pcr_index_hybrid", "pcr_index_radius_count", "pcr_index_radius_fill",
     "pcr_farthest_point_sample",
     "pcr_euclidean_mst", "pcr_orient_normals_tangent_plane", "pcr_orient_normals", "pcr_normalize_normals",
+    "pcr_estimation_compute_transformation", "pcr_estimation_compute_rmse", "pcr_correspondences_from_features", "pcr_registration_fgr_correspondence",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler and the normal orientation (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation and the calls on a correspondence list (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -148,6 +156,14 @@ QUERY_PROTOTYPES = {
     "pcr_orient_normals_tangent_plane": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PcrOrientInfo)], C.c_int),
     "pcr_orient_normals": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)], C.c_int),
     "pcr_normalize_normals": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+    "pcr_estimation_compute_transformation": ([C.c_void_p, C.POINTER(PcrEstimation), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_double)], C.c_int),
+    "pcr_estimation_compute_rmse": ([C.c_void_p, C.POINTER(PcrEstimation), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_double)], C.c_int),
+    "pcr_correspondences_from_features": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                           C.POINTER(C.c_int64)], C.c_int),
+    "pcr_registration_fgr_correspondence": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrFgrOption),
+                                             C.POINTER(PcrResult), C.c_void_p], C.c_int),
 }
 
 _lib = None

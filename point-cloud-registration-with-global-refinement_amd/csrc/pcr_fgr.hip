@@ -1113,27 +1113,37 @@ static size_t fgr_scratch_bytes(int64_t ns, int64_t nt, const pcr_fgr_option *op
            + pcr_feature_nn_scratch_bytes(ns, nt);
 }
 
+// NormalizePointCloud of both clouds: centred float64 copies (scratch from the arena above the current mark), divided by the larger extent
+// unless the scale is absolute
+struct FgrNorm { double *P[2]; double mean[2][3]; double scale_global, scale_start; };
+static int fgr_normalise_pair(pcr_context *ctx, const float *src_xyz, int64_t ns, const float *tgt_xyz, int64_t nt, const pcr_fgr_option *opt, FgrNorm *N) {
+    double **P = N->P;
+    P[0] = arena<double>(ctx, (size_t)ns * 3); P[1] = arena<double>(ctx, (size_t)nt * 3);
+    if (!P[0] || !P[1]) return PCR_ENOMEM;
+    double mx[2];
+    PCR_TRY(normalise(ctx, src_xyz, ns, P[0], N->mean[0], &mx[0]));
+    PCR_TRY(normalise(ctx, tgt_xyz, nt, P[1], N->mean[1], &mx[1]));
+    const double scale = mx[0] > mx[1] ? mx[0] : mx[1];
+    const double scale_global = opt->use_absolute_scale ? 1.0 : scale;
+    N->scale_global = scale_global; N->scale_start = opt->use_absolute_scale ? scale : 1.0;
+    if (scale_global != 1.0) {
+        PCR_LAUNCH(ctx, k_scale, dim3((unsigned)((ns * 3 + FB - 1) / FB)), dim3(FB), 0, ctx->stream, P[0], (long long)ns * 3, scale_global);
+        PCR_LAUNCH(ctx, k_scale, dim3((unsigned)((nt * 3 + FB - 1) / FB)), dim3(FB), 0, ctx->stream, P[1], (long long)nt * 3, scale_global);
+    }
+    return PCR_OK;
+}
+
+static int fgr_pose_from_list(pcr_context *ctx, const FgrNorm &N, const int32_t *cross, int64_t ncross, int swapped, const pcr_fgr_option *opt, double *Tsrc2tgt);
+
 // AdvancedMatching + OptimizePairwiseRegistration: the source -> target pose from the two clouds and their features (caller-order
 // device arrays).  Scratch comes from the arena above the current mark (the caller has reserved fgr_scratch_bytes).
 static int fgr_pose(pcr_context *ctx, const float *src_xyz, const float *src_feat, int64_t ns, const float *tgt_xyz, const float *tgt_feat, int64_t nt,
                     const pcr_fgr_option *opt, double *Tsrc2tgt) {
     { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(Tsrc2tgt, I, sizeof I); }
     if (ns > 0 && nt > 0) {
-        const int64_t nmax = ns > nt ? ns : nt;
-        const long long trial_cap = opt->tuple_test ? 100ll * nmax : 0;
         ArenaMark mark(ctx);
-        // ---- NormalizePointCloud
-        double *P[2] = {arena<double>(ctx, (size_t)ns * 3), arena<double>(ctx, (size_t)nt * 3)};
-        if (!P[0] || !P[1]) return PCR_ENOMEM;
-        double mean[2][3], mx[2];
-        PCR_TRY(normalise(ctx, src_xyz, ns, P[0], mean[0], &mx[0]));
-        PCR_TRY(normalise(ctx, tgt_xyz, nt, P[1], mean[1], &mx[1]));
-        const double scale = mx[0] > mx[1] ? mx[0] : mx[1];
-        const double scale_global = opt->use_absolute_scale ? 1.0 : scale, scale_start = opt->use_absolute_scale ? scale : 1.0;
-        if (scale_global != 1.0) {
-            PCR_LAUNCH(ctx, k_scale, dim3((unsigned)((ns * 3 + FB - 1) / FB)), dim3(FB), 0, ctx->stream, P[0], (long long)ns * 3, scale_global);
-            PCR_LAUNCH(ctx, k_scale, dim3((unsigned)((nt * 3 + FB - 1) / FB)), dim3(FB), 0, ctx->stream, P[1], (long long)nt * 3, scale_global);
-        }
+        FgrNorm N;
+        PCR_TRY(fgr_normalise_pair(ctx, src_xyz, ns, tgt_xyz, nt, opt, &N));
         // ---- AdvancedMatching: mutual nearest neighbours in feature space; i = the larger cloud
         const int swapped = nt > ns ? 1 : 0;
         const float *fi = swapped ? tgt_feat : src_feat, *fj = swapped ? src_feat : tgt_feat;
@@ -1158,6 +1168,18 @@ static int fgr_pose(pcr_context *ctx, const float *src_xyz, const float *src_fea
         PCR_LAUNCH(ctx, k_cross_emit, dim3((nPti + FB - 1) / FB), dim3(FB), 0, ctx->stream, i_to_j, cflags, cpos, nPti, cross);
         int64_t ncross = 0;
         PCR_TRY(pcr_read_count(ctx, ncross_dev, &ncross));
+        return fgr_pose_from_list(ctx, N, cross, ncross, swapped, opt, Tsrc2tgt);
+    }
+    return PCR_OK;
+}
+
+// The second half of fgr_pose, from the point where the list of matched pairs exists: cross = ncross rows (index in cloud i, index in cloud j),
+// cloud i = the target when `swapped`, else the source.  Tuple test, GNC optimiser, the pose in the original scale.  The feature form hands over
+// its cross-checked list, pcr_registration_fgr_correspondence the caller's list with swapped = 0.
+static int fgr_pose_from_list(pcr_context *ctx, const FgrNorm &N, const int32_t *cross, int64_t ncross, int swapped, const pcr_fgr_option *opt, double *Tsrc2tgt) {
+    {
+        double *const *P = N.P; const double (*mean)[3] = N.mean;
+        const double scale_global = N.scale_global, scale_start = N.scale_start;
         // ---- tuple test
         int32_t *corr = nullptr; int64_t ncorr = 0;
         if (opt->tuple_test && ncross > 0 && opt->maximum_tuple_count > 0) {
@@ -1262,6 +1284,33 @@ extern "C" int pcr_registration_fgr(pcr_context *ctx, const float *src_xyz, cons
     PCR_TRY(pcr_arena_reserve(ctx, fgr_scratch_bytes(ns, nt, opt)));
     PCR_TRY(fgr_pose(ctx, src_xyz, src_feat, ns, tgt_xyz, tgt_feat, nt, opt, Tsrc2tgt));
     // ---- EvaluateRegistration(source, target, maximum_correspondence_distance, T)
+    return pcr_evaluate_registration_impl(ctx, src_xyz, ns, tgt_xyz, nt, opt->maximum_correspondence_distance, Tsrc2tgt, result, correspondences);
+    });
+}
+
+// registration_fgr_based_on_correspondence: fgr_pose with the caller's list where the feature form has its cross-checked one (pi = source, pj = target)
+extern "C" int pcr_registration_fgr_correspondence(pcr_context *ctx, const float *src_xyz, int64_t ns, const float *tgt_xyz, int64_t nt, const int32_t *corres,
+                                                   int64_t n_corres, const pcr_fgr_option *opt, pcr_result *result, int32_t *correspondences) {
+    return pcr_api_call(ctx, [&]() -> int {
+    if (!result) return PCR_EINVAL;
+    PCR_TRY(fgr_check_args(ctx, opt, ns, nt));
+    pcr_fgr_option opt_local = *opt;
+    if (opt_local.maximum_tuple_count < 0) opt_local.maximum_tuple_count = (int32_t)((double)((ns + nt) / 2) * 0.2);     // the per-pair rule (pcr_hip.h)
+    const pcr_fgr_option *opt = &opt_local;
+    if ((ns > 0 && !src_xyz) || (nt > 0 && !tgt_xyz)) return PCR_EINVAL;
+    if (n_corres < 0 || n_corres > 0x7fffffff / 128) { ctx->err = "correspondence list too large"; return PCR_EINVAL; }
+    if (n_corres > 0 && (!corres || ns == 0 || nt == 0)) { ctx->err = "correspondences without a list or without points"; return PCR_EINVAL; }
+    double Tsrc2tgt[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    // the list may be longer than either cloud: the normalised clouds, the trials of the tuple test, the rows gathered for the optimiser
+    const size_t tuples = opt->tuple_test && opt->maximum_tuple_count > 0 ? (size_t)opt->maximum_tuple_count : 0;
+    PCR_TRY(pcr_arena_reserve(ctx, (size_t)(ns + nt) * (24 + 8 + 16) + (size_t)n_corres * (tuples ? 500 : 0) + (size_t)n_corres * (8 + 48 + 64) + tuples * (24 + 3 * 48 + 64) + (64u << 20)));
+    PCR_TRY(pcr_corres_check(ctx, corres, n_corres, ns, nt));
+    if (ns > 0 && nt > 0) {
+        ArenaMark mark(ctx);
+        FgrNorm N;
+        PCR_TRY(fgr_normalise_pair(ctx, src_xyz, ns, tgt_xyz, nt, opt, &N));
+        PCR_TRY(fgr_pose_from_list(ctx, N, corres, n_corres, 0, opt, Tsrc2tgt));
+    }
     return pcr_evaluate_registration_impl(ctx, src_xyz, ns, tgt_xyz, nt, opt->maximum_correspondence_distance, Tsrc2tgt, result, correspondences);
     });
 }

@@ -275,6 +275,10 @@ int pcr_feature_nn_mutual_batch(pcr_context *ctx, int G, const float *const *f0,
 size_t pcr_feature_corres_scratch_bytes(int64_t ns, int64_t nt);
 int pcr_feature_corres(pcr_context *ctx, const float *src_feat, int ns, const float *tgt_feat, int nt, int mutual_filter, int min_rows, int32_t *corres, int64_t *n_out);
 
+// ---- correspondence lists of the caller (pcr_corres.hip): PCR_EINVAL with a message if a row names a point outside [0, n_src) x [0, n_tgt); runs on
+// the device, the count is on the host when it returns (one int of scratch from the arena the caller has reserved)
+int pcr_corres_check(pcr_context *ctx, const int32_t *corres, int64_t n_corres, int64_t n_src, int64_t n_tgt);
+
 // ---- gicp (pcr_gicp.hip) --------------------------------------------------------------------------
 struct IcpOutputs { pcr_result res; };
 int pcr_dev_gicp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0,

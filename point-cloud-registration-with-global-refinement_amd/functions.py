@@ -40,6 +40,21 @@ def GICP_robusto(source, target, max_corres_dist, initial_T, iterations):
                                _r.ICPConvergenceCriteria(max_iteration=iterations))
 
 
+def registro_manual(source, target, picked_id_source, picked_id_target):
+    """The compute half of ALL_FUNCTIONS.py:423-442: the point pairs a user picked in the two clouds (the reference's ``escolher_pontos``
+    windows; the picking itself is not part of this package) give the starting pose of a registration,
+    ``TransformationEstimationPointToPoint().compute_transformation`` over them.  At least 3 picks per cloud and as many in one as in the
+    other, asserted as in the reference.  Returns ``T_inicial`` (4x4 float64, source -> target)."""
+    from . import o3d
+    assert (len(picked_id_source) >= 3 and len(picked_id_target) >= 3)
+    assert (len(picked_id_source) == len(picked_id_target))
+    corr = np.zeros((len(picked_id_source), 2))
+    corr[:, 0] = picked_id_source
+    corr[:, 1] = picked_id_target
+    p2p = _r.TransformationEstimationPointToPoint()
+    return p2p.compute_transformation(source, target, o3d.utility.Vector2iVector(corr))
+
+
 def amostragem_multiescala_otimizada(nuvem, n_escalas, voxel_inicial, seed=None):
     """ALL_FUNCTIONS.py:233-254: one voxel grid at ``voxel_inicial`` and ``n_escalas - 1`` random subsets of it whose sizes imitate
     coarser voxel grids (retention model a*exp(-b*voxel), a = 1.18397758, b = 5.09388767, normalised as the reference does);

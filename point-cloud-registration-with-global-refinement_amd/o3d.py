@@ -22,7 +22,8 @@ geometry = SimpleNamespace(PointCloud=_g.PointCloud, KDTreeSearchParamKNN=_g.KDT
                            KDTreeSearchParamRadius=_g.KDTreeSearchParamRadius,
                            KDTreeSearchParamHybrid=_g.KDTreeSearchParamHybrid, KDTreeFlann=_s.KDTreeFlann,
                            keypoint=SimpleNamespace(compute_iss_keypoints=_g.compute_iss_keypoints))
-utility = SimpleNamespace(Vector3dVector=lambda a: _np.asarray(a, dtype=_np.float64).reshape(-1, 3))
+utility = SimpleNamespace(Vector3dVector=lambda a: _np.asarray(a, dtype=_np.float64).reshape(-1, 3),
+                          Vector2iVector=lambda a: _np.asarray(a).astype(_np.int32).reshape(-1, 2))
 io = SimpleNamespace(read_point_cloud=_read_point_cloud)
 pipelines = SimpleNamespace(registration=_r)
 core = SimpleNamespace(nns=SimpleNamespace(NearestNeighborSearch=_s.NearestNeighborSearch))

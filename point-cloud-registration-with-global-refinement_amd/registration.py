@@ -36,28 +36,58 @@ class GMLoss(RobustKernel):
         self.k = float(k)
 
 
-class TransformationEstimationForGeneralizedICP:
+class TransformationEstimation:
+    """Open3D's ``TransformationEstimation`` methods on a correspondence list the caller holds (``pcr_estimation_compute_transformation`` /
+    ``pcr_estimation_compute_rmse``, include/pcr_hip.h): ``corres`` is (C, 2) rows of (source index, target index), a device tensor or
+    anything ``np.asarray`` turns into integers.  Every row counts (no distance test); an empty list gives the identity and 0."""
+
+    def _estimation(self) -> _lib.PcrEstimation:
+        raise RuntimeError(f"{type(self).__name__} is not implemented on the MI355X path")
+
+    def compute_transformation(self, source, target, corres) -> np.ndarray:
+        """The estimator's one update from the identity over the rows of ``corres``: a 4x4 float64 array (ALL_FUNCTIONS.py:438-439)."""
+        T = np.zeros(16, dtype=np.float64)
+        _estimation_call(self, "compute_transformation", source, target, corres, T)
+        return T.reshape(4, 4)
+
+    def compute_rmse(self, source, target, corres) -> float:
+        """The estimator's error over the rows of ``corres``: Euclidean for point-to-point and GICP, along the target normal for point-to-plane."""
+        out = np.zeros(1, dtype=np.float64)
+        _estimation_call(self, "compute_rmse", source, target, corres, out)
+        return float(out[0])
+
+
+class TransformationEstimationForGeneralizedICP(TransformationEstimation):
     def __init__(self, kernel: RobustKernel | None = None, epsilon: float = 1e-3):
         self.kernel = kernel if kernel is not None else L2Loss()
         self.epsilon = float(epsilon)
 
+    def _estimation(self):
+        return _lib.PcrEstimation(_lib.EST_GENERALIZED_ICP, 0, int(self.kernel.kind), float(self.kernel.k), float(self.epsilon))
 
-class TransformationEstimationPointToPoint:
+
+class TransformationEstimationPointToPoint(TransformationEstimation):
     """Open3D's default ``registration_icp`` estimator: the Umeyama fit of the correspondences (with a uniform scale when
     ``with_scaling``)."""
 
     def __init__(self, with_scaling: bool = False):
         self.with_scaling = bool(with_scaling)
 
+    def _estimation(self):
+        return _lib.PcrEstimation(_lib.EST_POINT_TO_POINT, int(self.with_scaling), _lib.LOSS_L2, 1.0, 1e-3)
 
-class TransformationEstimationPointToPlane:
+
+class TransformationEstimationPointToPlane(TransformationEstimation):
     """Point-to-plane ICP over the target's normals, robustly weighted by ``kernel`` (L2, L1 or GM)."""
 
     def __init__(self, kernel: RobustKernel | None = None):
         self.kernel = kernel if kernel is not None else L2Loss()
 
+    def _estimation(self):
+        return _lib.PcrEstimation(_lib.EST_POINT_TO_PLANE, 0, int(self.kernel.kind), float(self.kernel.k), 1e-3)
 
-class TransformationEstimationForColoredICP:
+
+class TransformationEstimationForColoredICP(TransformationEstimation):
     """Colored ICP (Park, Zhou, Koltun, ICCV 2017): a point-to-plane term weighted ``lambda_geometric`` and a photometric term over the
     target's colour gradients weighted ``1 - lambda_geometric``, both robustly weighted by ``kernel``.  As in Open3D a ``lambda_geometric``
     outside [0, 1] is reset to 0.968."""
@@ -66,6 +96,13 @@ class TransformationEstimationForColoredICP:
         lam = float(lambda_geometric)
         self.lambda_geometric = lam if 0.0 <= lam <= 1.0 else 0.968
         self.kernel = kernel if kernel is not None else L2Loss()
+
+    # Open3D's own methods need the gradient-carrying target that only registration_colored_icp builds
+    def compute_transformation(self, source, target, corres):
+        raise RuntimeError("TransformationEstimationForColoredICP.compute_transformation is not implemented on the MI355X path")
+
+    def compute_rmse(self, source, target, corres):
+        raise RuntimeError("TransformationEstimationForColoredICP.compute_rmse is not implemented on the MI355X path")
 
 
 class ICPConvergenceCriteria:
@@ -160,6 +197,41 @@ def _result(r: _lib.PcrResult, corr=None, scales=None) -> RegistrationResult:
 def _T(init):
     T = np.ascontiguousarray(np.asarray(init, dtype=np.float64).reshape(4, 4))
     return T, T.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _corres_device(fn: str, corres, ns: int, nt: int):
+    """A caller's correspondence list as a contiguous device int32 tensor (C, 2): a torch tensor, or anything ``np.asarray`` turns into
+    integers (the reference passes a float array of integral values, ALL_FUNCTIONS.py:433-435).  A wrong shape or a row outside the two
+    clouds raises ``RuntimeError`` before the library is called; a host list is checked on the host, before anything touches a device."""
+    torch = _torch()
+    if isinstance(corres, torch.Tensor):
+        if corres.dim() == 2 and corres.shape[1] != 2:
+            raise RuntimeError(f"{fn}: corres must have shape (C, 2), got {tuple(corres.shape)}")
+        cd = corres.to(device="cuda", dtype=torch.int32).reshape(-1, 2).contiguous()
+        lo, hi = (cd.min(0).values.tolist(), cd.max(0).values.tolist()) if cd.shape[0] else ((0, 0), (-1, -1))
+    else:
+        a = np.asarray(corres, dtype=np.int64)
+        if a.ndim == 2 and a.shape[1] != 2:
+            raise RuntimeError(f"{fn}: corres must have shape (C, 2), got {a.shape}")
+        a = np.ascontiguousarray(a.reshape(-1, 2))
+        lo, hi = (a.min(0).tolist(), a.max(0).tolist()) if a.shape[0] else ((0, 0), (-1, -1))
+        cd = None
+    if hi[0] >= lo[0] and (ns == 0 or nt == 0 or lo[0] < 0 or lo[1] < 0 or hi[0] >= ns or hi[1] >= nt):
+        raise RuntimeError(f"{fn}: correspondence index out of range")
+    return cd if cd is not None else torch.from_numpy(a.astype(np.int32)).cuda()
+
+
+def _estimation_call(estimation, what: str, source: PointCloud, target: PointCloud, corres, out: np.ndarray) -> None:
+    fn = f"{type(estimation).__name__}.{what}"
+    e = estimation._estimation()
+    ns, nt = len(source), len(target)
+    cd = _corres_device(fn, corres, ns, nt)
+    ctx = _lib.Context.current()
+    call = getattr(ctx.lib, "pcr_estimation_" + what)
+    ctx.check(call(ctx.handle, C.byref(e), _ptr(source.device_xyz()), _ptr(source.device_normals() if source.has_normals() else None),
+                   _ptr(source._cov if source.has_covariances() else None), C.c_int64(ns), _ptr(target.device_xyz()),
+                   _ptr(target.device_normals() if target.has_normals() else None), _ptr(target._cov if target.has_covariances() else None),
+                   C.c_int64(nt), _ptr(cd), C.c_int64(int(cd.shape[0])), out.ctypes.data_as(C.POINTER(C.c_double))), fn)
 
 
 def _ensure_gicp_normals(pc: PointCloud):
@@ -575,18 +647,22 @@ def compute_fpfh_feature(cloud: PointCloud, search_param) -> Feature:
     return Feature(feat[:n].contiguous())
 
 
-def registration_fgr_based_on_feature_matching(source: PointCloud, target: PointCloud, source_feature: Feature,
-                                               target_feature: Feature, option: FastGlobalRegistrationOption | None = None):
-    ctx = _lib.Context.current()
-    torch = _torch()
+def _fgr_option(option) -> _lib.PcrFgrOption:
     option = option or FastGlobalRegistrationOption()
     seed = option.seed
     if seed is None:                       # Open3D draws from std::random_device; here a process-local counter
         _fgr_seed_counter[0] = (_fgr_seed_counter[0] * 6364136223846793005 + 1442695040888963407) & (2 ** 64 - 1)
         seed = _fgr_seed_counter[0]
-    o = _lib.PcrFgrOption(option.division_factor, int(option.use_absolute_scale), int(option.decrease_mu),
-                          option.maximum_correspondence_distance, option.iteration_number, option.tuple_scale,
-                          option.maximum_tuple_count, int(option.tuple_test), int(seed))
+    return _lib.PcrFgrOption(option.division_factor, int(option.use_absolute_scale), int(option.decrease_mu),
+                             option.maximum_correspondence_distance, option.iteration_number, option.tuple_scale,
+                             option.maximum_tuple_count, int(option.tuple_test), int(seed))
+
+
+def registration_fgr_based_on_feature_matching(source: PointCloud, target: PointCloud, source_feature: Feature,
+                                               target_feature: Feature, option: FastGlobalRegistrationOption | None = None):
+    ctx = _lib.Context.current()
+    torch = _torch()
+    o = _fgr_option(option)
     ns, nt = len(source), len(target)
     corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
     res = _lib.PcrResult()
@@ -594,6 +670,43 @@ def registration_fgr_based_on_feature_matching(source: PointCloud, target: Point
                                            _ptr(target.device_xyz()), _ptr(target_feature._dev), C.c_int64(nt), C.byref(o),
                                            C.byref(res), _ptr(corr)), "registration_fgr_based_on_feature_matching")
     return _result(res, corr)
+
+
+def registration_fgr_based_on_correspondence(source: PointCloud, target: PointCloud, corres, option: FastGlobalRegistrationOption | None = None):
+    """Open3D ``registration_fgr_based_on_correspondence``: fast global registration on a list of (source index, target index) rows the
+    caller holds -- ``correspondences_from_features`` gives the one the feature form builds -- instead of on features
+    (``pcr_registration_fgr_correspondence``, include/pcr_hip.h).  With ``option.tuple_test`` the tuple test draws from the list in its
+    given order; without it every row goes to the optimiser.  The result is ``evaluate_registration`` under the pose found."""
+    o = _fgr_option(option)
+    ns, nt = len(source), len(target)
+    cd = _corres_device("registration_fgr_based_on_correspondence", corres, ns, nt)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+    res = _lib.PcrResult()
+    ctx.check(ctx.lib.pcr_registration_fgr_correspondence(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), C.c_int64(nt),
+                                                          _ptr(cd), C.c_int64(int(cd.shape[0])), C.byref(o), C.byref(res), _ptr(corr)),
+              "registration_fgr_based_on_correspondence")
+    return _result(res, corr)
+
+
+def correspondences_from_features(source_features: Feature, target_features: Feature, mutual_filter: bool = False, mutual_consistency_ratio: float = 0.1):
+    """Open3D ``correspondences_from_features`` (0.17 and later): every source feature row paired with its nearest target row -- float64
+    distance, ties to the smaller index --, in source order; with ``mutual_filter`` only the rows whose target row points back, unless fewer
+    than ``int(mutual_consistency_ratio * n_source)`` remain (then all rows).  Returns a device int32 tensor (M, 2) that
+    ``registration_ransac_based_on_correspondence``, ``registration_fgr_based_on_correspondence`` and the estimators' methods take as it
+    is; ``.cpu().numpy()`` gives Open3D's array."""
+    if source_features.dimension() != target_features.dimension():
+        raise RuntimeError("correspondences_from_features: the two feature sets have different dimensions")
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = source_features.num(), target_features.num()
+    out = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+    n = C.c_int64(0)
+    ctx.check(ctx.lib.pcr_correspondences_from_features(ctx.handle, _ptr(source_features._dev.contiguous()), C.c_int64(ns), _ptr(target_features._dev.contiguous()),
+                                                        C.c_int64(nt), C.c_int(source_features.dimension()), C.c_int(int(bool(mutual_filter))),
+                                                        C.c_double(float(mutual_consistency_ratio)), _ptr(out), C.byref(n)), "correspondences_from_features")
+    return out[: n.value]
 
 
 class RANSACConvergenceCriteria:
@@ -678,14 +791,9 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
     p = _ransac_params("registration_ransac_based_on_correspondence", max_correspondence_distance, estimation_method, ransac_n, checkers, criteria, seed)
     ctx = _lib.Context.current()
     torch = _torch()
-    if isinstance(corres, torch.Tensor):
-        cd = corres.to(device="cuda", dtype=torch.int32).reshape(-1, 2).contiguous()
-    else:
-        cd = torch.from_numpy(np.ascontiguousarray(np.asarray(corres, dtype=np.int64).reshape(-1, 2).astype(np.int32))).cuda()
-    nc = int(cd.shape[0])
     ns, nt = len(source), len(target)
-    if nc and (ns == 0 or nt == 0 or int(cd[:, 0].min()) < 0 or int(cd[:, 1].min()) < 0 or int(cd[:, 0].max()) >= ns or int(cd[:, 1].max()) >= nt):
-        raise RuntimeError("registration_ransac_based_on_correspondence: correspondence index out of range")
+    cd = _corres_device("registration_ransac_based_on_correspondence", corres, ns, nt)
+    nc = int(cd.shape[0])
     out = torch.empty((max(nc, 1), 2), dtype=torch.int32, device="cuda")
     res, info = _lib.PcrResult(), _lib.PcrRansacInfo()
     ctx.check(ctx.lib.pcr_registration_ransac_correspondence(
