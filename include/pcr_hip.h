@@ -661,6 +661,42 @@ int pcr_orient_normals_tangent_plane(pcr_context *ctx, const float *xyz, float *
 int pcr_orient_normals(pcr_context *ctx, const float *xyz, float *normals, int64_t n, int mode, const double *ref);
 int pcr_normalize_normals(pcr_context *ctx, float *normals, int64_t n);
 
+/* == PointCloud.compute_boundary_points(radius, max_nn, angle_threshold) (Open3D t::geometry::PointCloud::ComputeBoundaryPoints, the angle
+ *    criterion of PCL's BoundaryEstimation; the reference calls it nowhere): the points on the rim of the sampled surface -- occlusion shadows,
+ *    the edge of the field of view, holes.  Open3D is not at hand, so the rule is stated here and this statement is the specification.  Per
+ *    point i, with p the float32 coordinates and n the float32 normals, both read into float64:
+ *    1. NEIGHBOURHOOD.  The row pcr_index_hybrid returns for the query p_i on the cloud itself: every point with d^2 < radius^2 (strict, d^2 in
+ *       float64 on the float32 coordinates, unfused, in the order x, y, z), ordered by (d^2, caller index), the first max_nn of them.  The point
+ *       itself and coincident points are members.  count_i is the row length.
+ *    2. NORMAL.  Taken as a unit vector, as Open3D takes it: it is not normalised.  A row whose normal has a non-finite component or is
+ *       (0, 0, 0) is undecided: not boundary, gap 0.  So is a row whose point has a non-finite coordinate: it finds nothing (count 0), and it
+ *       is nobody's neighbour.
+ *    3. TANGENT FRAME.  a = the axis with the smallest |n component|, on a tie x before y before z; e = that unit axis.  v = n x e, u = v x n.
+ *       A cross product p x q is (p_y q_z - p_z q_y, p_z q_x - p_x q_z, p_x q_y - p_y q_x), every product and every difference rounded once, no
+ *       fused multiply-add.
+ *    4. ANGLES.  For every member j in row order: d = p_j - p_i, x = (u_x d_x + u_y d_y) + u_z d_z, y = (v_x d_x + v_y d_y) + v_z d_z, unfused.
+ *       A member with x == 0 and y == 0 is skipped: the point itself, coincident points, a point exactly on the normal line.  Otherwise its
+ *       angle is atan2(y, x) in float64.  m = the number of angles.
+ *    5. GAP.  m == 0: gap 0, not boundary.  Otherwise, with the angles sorted ascending a_0 .. a_{m-1}:
+ *       gap = max(the largest a_{t+1} - a_t, 2 pi - (a_{m-1} - a_0)), 2 pi = 2.0 * M_PI; m == 1 gives 2 pi.
+ *    6. VERDICT.  Boundary iff gap > T, T = angle_threshold * M_PI / 180.0 evaluated left to right.
+ *    Everything up to the arguments of atan2 is fixed bit for bit: a host recomputation in that order gives the same bits.  atan2 itself is
+ *    not: the device's and libm's differ by ulps.  The largest circular gap is a continuous function of the angles (two nearly equal angles
+ *    changing places, or one moving from pi to -pi, change it by rounding only), so the reported gap carries an error of a few 1e-16 and the
+ *    verdict can differ from a host recomputation only for a gap within rounding of T.  Two runs give the same bits in every output.
+ *    TWO DEVIATIONS from Open3D, [O3D ?] = recalled and not pinned against a build of it: the tangent frame is
+ *    this library's (Open3D's GetCoordinateSystemOnPlane chooses another one [O3D ?]; in exact arithmetic the gap does not depend on the
+ *    frame), and the row order -- which decides the members of a ball of more than max_nn points that has ties in d^2 -- is this library's
+ *    total order (d^2, caller index) [O3D ?].
+ *    ERRORS.  PCR_EINVAL with a message naming boundary_points: radius not finite or <= 0; max_nn outside 1..200 (the search index's limit);
+ *    angle_threshold not finite or outside [0, 360]; n < 0 or above the int range; a null xyz or normals with n > 0.  n == 0: PCR_OK, *out_n = 0.
+ * xyz, normals: device, n x 3 float32.  Device, each optional: boundary_mask (n bytes), out_xyz (capacity n x 3), out_index (capacity n int64,
+ * ascending: the layout of pcr_remove_radius_outlier and pcr_iss_keypoints), max_gap (n float64, radians, caller order), counts (n int32, the
+ * count_i of rule 1).  Host: out_n (optional).  Asynchronous on the context's stream except for the read of the count; scratch from the
+ * context's arena (12 bytes per row place: n x max_nn x 12 for the rows). */
+int pcr_boundary_points(pcr_context *ctx, const float *xyz, const float *normals, int64_t n, double radius, int max_nn, double angle_threshold,
+                        uint8_t *boundary_mask, float *out_xyz, int64_t *out_index, int64_t *out_n, double *max_gap, int32_t *counts);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

@@ -7,9 +7,9 @@ The directory name contains hyphens; import it with ``importlib.import_module`` 
 """
 from . import _lib, drivers, functions, geometry, io, o3d, posegraph, refinement, registration, search, sharding  # noqa: F401
 from .functions import (Coarse_to_fine_FGR_M_GICP, GICP_robusto, Multiscale_GICP, amostragem_multiescala_otimizada, calculate_RMSE_and_fitness,  # noqa: F401
-                        create_scales, extract_eigen_features, knn_distance_table, radius_from_cloud_pair, registro_FGR, registro_manual, remove_plane, remove_small_clusters,
+                        create_scales, extract_eigen_features, knn_distance_table, radius_from_cloud_pair, registro_FGR, registro_manual, remove_boundary_points, remove_plane, remove_small_clusters,
                         script1, script2)
-from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, PointCloud, compute_iss_keypoints,  # noqa: F401
+from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius, PointCloud, boundary_point_indices, compute_iss_keypoints,  # noqa: F401
                        euclidean_minimum_spanning_tree, farthest_point_indices, iss_keypoint_indices)
 from .search import KDTreeFlann, NearestNeighborSearch  # noqa: F401
 

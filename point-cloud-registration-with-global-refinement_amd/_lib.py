@@ -129,9 +129,10 @@ EXPORTS = [
     "pcr_farthest_point_sample",
     "pcr_euclidean_mst", "pcr_orient_normals_tangent_plane", "pcr_orient_normals", "pcr_normalize_normals",
     "pcr_estimation_compute_transformation", "pcr_estimation_compute_rmse", "pcr_correspondences_from_features", "pcr_registration_fgr_correspondence",
+    "pcr_boundary_points",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation and the calls on a correspondence list (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list and the boundary detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -164,6 +165,8 @@ QUERY_PROTOTYPES = {
                                            C.POINTER(C.c_int64)], C.c_int),
     "pcr_registration_fgr_correspondence": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrFgrOption),
                                              C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_boundary_points": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(C.c_int64), C.c_void_p, C.c_void_p], C.c_int),
 }
 
 _lib = None

@@ -246,6 +246,10 @@ int pcr_dev_nn_distance(pcr_context *ctx, const DevCloud *c, const uint32_t *per
 // ---- the k-best kernels of the search index (pcr_search.hip) over a sorted cloud of the caller's whose points carry their caller row in w: rows of k
 // caller rows ordered by (float64 d^2, caller row), -1 / +inf beyond the cloud's size; the octets take the queries in the order qperm (optional); enqueues only
 int pcr_dev_tagged_knn(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, int k, int32_t *idx, double *d2);
+// ... and the hybrid form (pcr_index_hybrid's kernel): per query the first max_nn caller rows with d^2 < radius^2 (strict) in that order, -1 / 0 beyond
+// counts[i] entries; a query with a non-finite coordinate finds nothing
+int pcr_dev_tagged_hybrid(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, double radius, int max_nn, int32_t *idx, double *d2,
+                          int32_t *counts);
 
 int pcr_registro_fgr_impl(pcr_context *ctx, const float *src_xyz, const float *src_prior, int64_t ns, const float *tgt_xyz, const float *tgt_prior, int64_t nt,
                           const pcr_fgr_params *p, float *src_normals_out, float *tgt_normals_out, pcr_result *result, int32_t *correspondences);

@@ -385,6 +385,15 @@ int pcr_dev_tagged_knn(pcr_context *ctx, const DevCloud *c, const float *query_x
     return launch_index_knn<false>(ctx, a);
 }
 
+int pcr_dev_tagged_hybrid(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, double radius, int max_nn, int32_t *idx, double *d2,
+                          int32_t *counts) {
+    if (max_nn < 1 || max_nn > SRCH_MAX_K || !(radius > 0.0) || m < 1 || m > SRCH_MAX_POINTS) { ctx->err = "tagged_hybrid: max_nn, radius or query count out of range"; return PCR_EINVAL; }
+    SearchArgs a; std::memset(&a, 0, sizeof a);
+    a.t = oct_view(c); a.q = query_xyz; a.m = (int)m; a.qperm = qperm; a.k = max_nn; a.r2 = radius * radius; a.r2f = pcr_wide_r2f(a.r2);
+    a.idx = idx; a.d2 = d2; a.counts = counts;
+    return launch_index_knn<true>(ctx, a);
+}
+
 extern "C" int pcr_index_knn(pcr_context *ctx, const pcr_index *index, const float *query_xyz, int64_t m, int k, int32_t *idx, double *d2) {
     return pcr_api_call(ctx, [&]() -> int {
     PCR_TRY(search_check(ctx, index, query_xyz, m, "index_knn"));

@@ -169,6 +169,17 @@ def remove_plane(cloud, distance_threshold, ransac_n=3, num_iterations=100, prob
     return cloud.select_by_index(torch.nonzero(~info["mask"]).reshape(-1)), plane, removed
 
 
+def remove_boundary_points(cloud, radius, max_nn=30, angle_threshold=90.0):
+    """``compute_boundary_points`` as a filter, not in the reference: takes the rim of the sampled surface -- where normals and FPFH rows come
+    from half a neighbourhood -- out of the cloud.  Returns ``(interior, removed)``: the cloud without its boundary points and the removed rows
+    as a device int64 tensor, ascending.  Mask and selection stay on the device."""
+    import torch
+    radius, max_nn, angle_threshold = _g._boundary_args(radius, max_nn, angle_threshold)
+    cloud._need_normals("remove_boundary_points")
+    removed, mask, _, _ = _g._boundary_call(cloud, radius, max_nn, angle_threshold)
+    return cloud.select_by_index(torch.nonzero(~mask).reshape(-1)), removed
+
+
 # ------------------------------------------------------------------------------------ script variants
 class script1:
     """Private copies in 1_FGR_pairwise_registration_in_NCLT_dataset.py."""

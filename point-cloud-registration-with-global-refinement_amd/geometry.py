@@ -308,6 +308,18 @@ class PointCloud:
             raise ValueError("orient_normals_consistent_tangent_plane: cos_alpha_tol other than 1.0 is not supported")
         _orient_normals_tangent_plane(self, k)
 
+    def compute_boundary_points(self, radius: float, max_nn: int = 30, angle_threshold: float = 90.0):
+        """``PointCloud.compute_boundary_points`` (Open3D's tensor ``PointCloud``; the angle criterion of PCL's ``BoundaryEstimation``): the
+        points on the rim of the sampled surface -- occlusion shadows, the edge of the field of view, holes -> ``(boundary_cloud, mask)``.
+        A point is a boundary point when the directions to its Hybrid(``radius``, ``max_nn``) neighbours, projected into its tangent plane,
+        leave an angular gap of more than ``angle_threshold`` degrees (the rules: include/pcr_hip.h).  Needs normals, which are taken as
+        unit vectors.  Normals, colours and covariances travel with the points, in the input's order; ``mask`` is a ``torch.bool`` tensor
+        of length n on the device.  Bad arguments raise ``ValueError`` before anything touches a device."""
+        radius, max_nn, angle_threshold = _boundary_args(radius, max_nn, angle_threshold)
+        self._need_normals("compute_boundary_points")
+        idx, mask, _, _ = _boundary_call(self, radius, max_nn, angle_threshold)
+        return self.select_by_index(idx), mask
+
     def uniform_down_sample(self, every_k_points: int) -> "PointCloud":
         """``PointCloud.uniform_down_sample``: points 0, k, 2k, ... in their order (host side: an index list for ``select_by_index``)."""
         if every_k_points < 1:
@@ -524,6 +536,52 @@ def euclidean_minimum_spanning_tree(cloud: PointCloud):
     d2 = torch.zeros(max(n - 1, 1), dtype=torch.float64, device="cuda")
     ctx.check(ctx.lib.pcr_euclidean_mst(ctx.handle, _ptr(cloud.device_xyz()), C.c_int64(n), _ptr(edges), _ptr(d2), None), "euclidean_minimum_spanning_tree")
     return edges[: max(n - 1, 0)].to(torch.int64), d2[: max(n - 1, 0)]
+
+
+# ---- boundary points --------------------------------------------------------------------------------------------
+def _boundary_args(radius, max_nn, angle_threshold):
+    """The arguments of the boundary detector as (float, int, float), or ``ValueError``: checked on the host, before a device is touched."""
+    radius, max_nn, angle_threshold = float(radius), int(max_nn), float(angle_threshold)
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"compute_boundary_points: radius must be finite and > 0, got {radius}")
+    if not 1 <= max_nn <= 200:
+        raise ValueError(f"compute_boundary_points: max_nn must be in 1..200, got {max_nn}")
+    if not (np.isfinite(angle_threshold) and 0.0 <= angle_threshold <= 360.0):
+        raise ValueError(f"compute_boundary_points: angle_threshold must be finite and in [0, 360] degrees, got {angle_threshold}")
+    return radius, max_nn, angle_threshold
+
+
+def _boundary_call(cloud: PointCloud, radius, max_nn, angle_threshold):
+    """``pcr_boundary_points`` with every output, all on the device -> ``(indices int64 ascending, mask (n,) bool, max_gap (n,) float64 in
+    radians, counts (n,) int32)``."""
+    n = len(cloud)
+    if n > 0:
+        cloud._need_normals("compute_boundary_points")
+    ctx = _lib.Context.current()
+    torch = _torch()
+    mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    idx = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+    gap = torch.zeros(max(n, 1), dtype=torch.float64, device="cuda")
+    counts = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    m = C.c_int64(0)
+    ctx.check(ctx.lib.pcr_boundary_points(ctx.handle, _ptr(cloud.device_xyz()), _ptr(cloud._nrm if n > 0 else None), C.c_int64(n), C.c_double(radius),
+                                          C.c_int(max_nn), C.c_double(angle_threshold), _ptr(mask), None, _ptr(idx), C.byref(m), _ptr(gap), _ptr(counts)),
+              "compute_boundary_points")
+    return idx[: m.value], mask[:n].bool(), gap[:n], counts[:n]
+
+
+def _boundary_points(cloud: PointCloud, radius, max_nn=30, angle_threshold=90.0):
+    """``pcr_boundary_points`` with every output -> ``(indices (torch int64, device, ascending), mask (n,) bool, max_gap (n,) float64 in radians,
+    counts (n,) int32: the neighbours each row had)``; the arrays on the host."""
+    idx, mask, gap, counts = _boundary_call(cloud, *_boundary_args(radius, max_nn, angle_threshold))
+    return idx, mask.cpu().numpy(), gap.cpu().numpy(), counts.cpu().numpy()
+
+
+def boundary_point_indices(cloud: PointCloud, radius: float, max_nn: int = 30, angle_threshold: float = 90.0) -> np.ndarray:
+    """The rows ``PointCloud.compute_boundary_points`` selects, int64, ascending: what takes rim points out of a keypoint list
+    (``np.setdiff1d(iss_keypoint_indices(cloud), boundary_point_indices(cloud, radius))``) or marks the rows of a correspondence set whose
+    target is a rim point (``np.isin(corres[:, 1], boundary_point_indices(target, radius))``)."""
+    return _boundary_call(cloud, *_boundary_args(radius, max_nn, angle_threshold))[0].cpu().numpy()
 
 
 # ---- o3d.geometry.keypoint ------------------------------------------------------------------------------------
