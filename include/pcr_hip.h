@@ -313,6 +313,69 @@ int pcr_registration_colored_icp(pcr_context *ctx, const float *src_xyz, const f
 int pcr_color_gradient(pcr_context *ctx, const float *xyz, const float *normals, const float *colors, int64_t n, int search_kind, int knn,
                        double radius, float *gradient3);
 
+/* ============================================================================================ voxelized GICP on a voxel covariance map
+ * Voxelized GICP (Koide, Yokozuka, Oishi, Banno, ICRA 2021; fast_gicp's FastVGICP): the target becomes a grid of cells, each with a count, a mean
+ * and a mean covariance, and a source point is matched to the cell it falls into (or to that cell and its neighbours) by a few hash probes
+ * instead of a nearest-neighbour search.  The map is built once and serves any number of registrations (scan to map).  Open3D has no such call
+ * and the reference never makes one, so this statement is the specification.
+ *
+ * MAP.  Input: n target points (float32) and one covariance per point (float32 cov6 = xx,xy,xz,yy,yz,zz) -- or normals, from which the member
+ *   covariance is the one the GICP estimator uses, R diag(epsilon, 1, 1) R^T with R the rotation taking e1 onto the normal (identity when
+ *   n.x < -0.99; the normal is not normalised), computed in float64 from the float32 normal and rounded to float32 before it is summed.
+ *   The grid is pcr_voxel_down_sample's: in float64 on the float32 values, origin = min - voxel_size / 2 per axis,
+ *   index = floor((p - origin) / voxel_size); indices must fit 21 bits (otherwise PCR_EINVAL, as pcr_voxel_down_sample).
+ *   Per occupied cell v: the count N_v; the mean mu_v = (float64 sum of the members in input order) / N_v, rounded to float32; the covariance
+ *   C_v = per channel (float64 sum of the members' cov6 in input order) / N_v, rounded to float32.  The rows are listed in Morton order of the
+ *   cell index (bit b of ix, iy, iz at bits 3b, 3b + 1, 3b + 2): the order in which pcr_voxel_down_sample lists them.
+ * ROWS AT A POSE T (float64 4x4, row-major).  For source point a = (x, y, z): q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 in float64, every
+ *   operation rounded once, no fused multiply-add (numpy's elementwise expression gives the same bits); cell = floor((q - origin) / voxel_size);
+ *   the candidate cells are cell + offset for the neighbourhood: 1: (0,0,0); 7: (0,0,0), (+1,0,0), (-1,0,0), (0,+1,0), (0,-1,0), (0,0,+1), (0,0,-1)
+ *   in that order; 27: all (dx,dy,dz) in {-1,0,1}^3 in lexicographic order, dx slowest.  A candidate with an index outside [0, 2^21) on any
+ *   axis, unoccupied, or with N_v < min_points_per_voxel gives no row.  The rows (i, v) are ordered by i, then by offset order; v is the map row.
+ * UPDATE.  Row (i, v) contributes N_v times what the GICP estimator contributes for a correspondence with source point q_i, source covariance
+ *   R C_i R^T, target point mu_v and target covariance C_v: W = (C_v + R C_i R^T)^(-1/2), three whitened rows r = W (q_i - mu_v),
+ *   J = W [-skew(q_i) | I], each weighted by the kernel's weight of its own r (L2 / L1 / GM as in pcr_registration_generalized_icp) and then by
+ *   N_v.  The 6x6 system is solved and turned into a pose exactly as the GICP update (LDLT, Rz Ry Rx, left-multiplied).  No rows: the identity.
+ * LOOP.  RegistrationICP's, as in pcr_registration_icp: rows at init, then update / left-multiply / rows, until |d fitness| < relative_fitness
+ *   and |d RMSE| < relative_rmse, or max_iteration.  fitness = (source points with at least one row) / n_src,
+ *   inlier_rmse = sqrt(sum over the rows of |q_i - mu_v|^2 / rows), n_correspondences = the number of rows.  There is no
+ *   max_correspondence_distance: the voxel size plays its part.
+ * All cloud, covariance and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed; it is
+ * read-only after creation, and any context on the same device may use it for any number of calls. */
+typedef struct pcr_voxel_map pcr_voxel_map;
+typedef struct {
+    int32_t loss;             /* the fields of pcr_gicp_params ...            */
+    double loss_k;
+    double epsilon;           /* source covariances from normals (src_cov6 == NULL) */
+    double relative_fitness;
+    double relative_rmse;
+    int32_t max_iteration;
+    int32_t neighborhood;     /* ... plus: 1, 7 or 27 candidate cells per source point */
+    int32_t min_points_per_voxel;   /* >= 1: cells with fewer members give no row */
+} pcr_vgicp_params;
+
+/* Exactly one of cov6 / normals must be given (n x 6 / n x 3 float32); n >= 1.  voxel_size <= 0, a non-finite voxel_size or epsilon, a non-finite
+ * value in xyz / cov6 / normals, both or neither of cov6 / normals: PCR_EINVAL with a message naming the argument.  Finished when it returns. */
+int pcr_voxel_map_create(pcr_context *ctx, const float *xyz, const float *cov6, const float *normals, int64_t n, double voxel_size, double epsilon,
+                         pcr_voxel_map **out);
+/* Frees the map (waits for the device, so no call is still reading it).  NULL is allowed. */
+int pcr_voxel_map_destroy(pcr_voxel_map *map);
+/* number of occupied cells = map rows */
+int pcr_voxel_map_size(const pcr_voxel_map *map, int64_t *cells);
+/* the map's rows in Morton order, each output optional: cell3 (cells x 3 int32: ix, iy, iz), count (cells int32), mean3 (cells x 3 float32),
+ * cov6 (cells x 6 float32).  Asynchronous on the context's stream. */
+int pcr_voxel_map_read(pcr_context *ctx, const pcr_voxel_map *map, int32_t *cell3, int32_t *count, float *mean3, float *cov6);
+/* the rows (i, v) of the rule at the pose T: rows2 = int32 pairs, capacity n_src x neighborhood rows; *n_rows on the host. */
+int pcr_voxel_map_correspondences(pcr_context *ctx, const pcr_voxel_map *map, const float *src_xyz, int64_t n_src, const double *T, int neighborhood,
+                                  int min_points_per_voxel, int32_t *rows2, int64_t *n_rows);
+/* the loop of the rule from init_T.  Exactly as for the map, the source carries src_cov6 or, without it, src_normals (covariances by
+ * params->epsilon); neither is PCR_EINVAL naming src_cov6.  A neighborhood that is not 1, 7 or 27, min_points_per_voxel < 1, a non-finite
+ * value in src_xyz / src_cov6 / src_normals / init_T: PCR_EINVAL with a message naming the argument.  correspondences: optional device int32,
+ * capacity n_src x neighborhood rows: the rows at the returned pose (n_correspondences of them). */
+int pcr_registration_voxelized_gicp(pcr_context *ctx, const float *src_xyz, const float *src_cov6, const float *src_normals, int64_t n_src,
+                                    const pcr_voxel_map *map, const double *init_T, const pcr_vgicp_params *params, pcr_result *result,
+                                    int32_t *correspondences);
+
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)
  * -> registration_generalized_icp, chained.  src/tgt_normals optional (AF flow orientation prior).

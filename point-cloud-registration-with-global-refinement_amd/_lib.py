@@ -42,6 +42,11 @@ class PcrColoredIcpParams(C.Structure):
                 ("relative_rmse", C.c_double), ("max_iteration", C.c_int32)]
 
 
+class PcrVgicpParams(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("loss_k", C.c_double), ("epsilon", C.c_double), ("relative_fitness", C.c_double),
+                ("relative_rmse", C.c_double), ("max_iteration", C.c_int32), ("neighborhood", C.c_int32), ("min_points_per_voxel", C.c_int32)]
+
+
 class PcrRansacParams(C.Structure):
     _fields_ = [("ransac_n", C.c_int32), ("with_scaling", C.c_int32), ("max_iteration", C.c_int32), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("edge_length_threshold", C.c_double), ("distance_threshold", C.c_double),
@@ -130,6 +135,8 @@ EXPORTS = [
     "pcr_euclidean_mst", "pcr_orient_normals_tangent_plane", "pcr_orient_normals", "pcr_normalize_normals",
     "pcr_estimation_compute_transformation", "pcr_estimation_compute_rmse", "pcr_correspondences_from_features", "pcr_registration_fgr_correspondence",
     "pcr_boundary_points",
+    "pcr_voxel_map_create", "pcr_voxel_map_destroy", "pcr_voxel_map_size", "pcr_voxel_map_read", "pcr_voxel_map_correspondences",
+    "pcr_registration_voxelized_gicp",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list and the boundary detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -167,6 +174,14 @@ QUERY_PROTOTYPES = {
                                              C.POINTER(PcrResult), C.c_void_p], C.c_int),
     "pcr_boundary_points": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.POINTER(C.c_int64), C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_voxel_map_create": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_voxel_map_destroy": ([C.c_void_p], C.c_int),
+    "pcr_voxel_map_size": ([C.c_void_p, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_voxel_map_read": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_voxel_map_correspondences": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p,
+                                       C.POINTER(C.c_int64)], C.c_int),
+    "pcr_registration_voxelized_gicp": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrVgicpParams),
+                                         C.POINTER(PcrResult), C.c_void_p], C.c_int),
 }
 
 _lib = None

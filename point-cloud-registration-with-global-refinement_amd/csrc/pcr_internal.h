@@ -293,6 +293,8 @@ int pcr_dev_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, doub
 // registration_colored_icp: the loop of pcr_dev_icp with k_icp_iter_colored; intensities (float64) and gradients in the clouds' Morton order
 int pcr_dev_colored_icp(pcr_context *ctx, const DevCloud *src, const DevCloud *tgt, double max_dist, const double *T0, const pcr_colored_icp_params *p,
                         const double *src_int, const double *tgt_int, const float4 *tgt_grad, pcr_result *out, int32_t *match_dev /*optional src.cap*/);
+// the loop switches of pcr_gicp.hip that every loop over pcr_icp_loop.h obeys: launches per chunk (PCR_ICP_CHUNK), chunks replayed as graphs (PCR_ICP_GRAPH)
+void pcr_icp_loop_switches(int *chunk, bool *graph);
 int pcr_dev_gicp_group_scales(pcr_context *ctx, int G, int S, const DevCloud *const *src /* G x S */, const DevCloud *const *tgt, const double *max_dists /* G x S */, const double *T0 /* G x 16 */,
                               const pcr_gicp_params *p, pcr_result *out /* G x S */, int32_t *const *match_dev /* G, optional */);       // all scales of a lockstep group in one loop; 1: declined
 int pcr_dev_gicp_group(pcr_context *ctx, int G, const DevCloud *const *src, const DevCloud *const *tgt, const double *max_dists /* G */, const double *T0 /* G x 16 */,

@@ -1,0 +1,64 @@
+// pcr_vgicp.h -- what the kernels of pcr_vgicp.hip share on the device (the map's count and row kernels, the voxelized GICP iteration kernel):
+// the map as they see it, the pose applied to a source point with every operation rounded once, the cell of the result, the neighbourhood's
+// offsets and the probe of the cell hash.  The rule is the statement in include/pcr_hip.h.
+#pragma once
+#include "pcr_octree.h"
+
+// One map row per occupied cell, in Morton order of the cell: mean4[v] = (mean, w = bit pattern of the count N_v), cov8[2 v], cov8[2 v + 1] =
+// (xx, xy, xz, yy), (yz, zz, 0, 0); `tab` is the cell hash of level 0 (pcr_dev_build_grid_batch): cell -> (row, 1).
+struct VgicpMapView {
+    const GridEntry *tab; const unsigned *dmask;
+    const float4 *mean4, *cov8;
+    double org[3], voxel;                  // origin = min - voxel / 2 in float64: the grid of voxel_down_sample
+};
+
+#define VG_NO_CELL (-4)                    // a coordinate with every candidate cell outside the grid (also: a non-finite coordinate)
+
+// q = T p with q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 in float64, every product and sum rounded once: numpy's elementwise expression gives
+// the same bits, so the cell of q is decided (T: the first three rows of the pose, row-major)
+__device__ static inline void vg_transform(const double *T, float x, float y, float z, double &qx, double &qy, double &qz) {
+#pragma clang fp contract(off)
+    const double px = x, py = y, pz = z;
+    const double ax = T[0] * px, bx = T[1] * py, cx = T[2] * pz;
+    const double ay = T[4] * px, by = T[5] * py, cy = T[6] * pz;
+    const double az = T[8] * px, bz = T[9] * py, cz = T[10] * pz;
+    double sx = ax + bx, sy = ay + by, sz = az + bz;
+    sx = sx + cx; sy = sy + cy; sz = sz + cz;
+    qx = sx + T[3]; qy = sy + T[7]; qz = sz + T[11];
+}
+// floor((q - origin) / voxel) of one axis as an int; everything from which no offset of -1, 0, +1 leads into [0, 2^21) becomes VG_NO_CELL
+__device__ static inline int vg_cell(double q, double org, double voxel) {
+#pragma clang fp contract(off)
+    const double d = q - org;
+    const double c = floor(d / voxel);
+    return (c >= -1.0 && c <= 2097152.0) ? (int)c : VG_NO_CELL;
+}
+// offset k of the neighbourhood nbh: 1: the cell; 7: the cell, then +x, -x, +y, -y, +z, -z; 27: {-1, 0, 1}^3 in lexicographic order, dx slowest
+__device__ static inline void vg_offset(int nbh, int k, int &dx, int &dy, int &dz) {
+    if (nbh == 27) { dx = k / 9 - 1; dy = (k / 3) % 3 - 1; dz = k % 3 - 1; return; }
+    const int axis = (k - 1) >> 1, s = k == 0 ? 0 : ((k & 1) ? 1 : -1);
+    dx = axis == 0 ? s : 0; dy = axis == 1 ? s : 0; dz = axis == 2 ? s : 0;
+}
+// map row of the cell (x, y, z), or -1: outside [0, 2^21)^3 or unoccupied.  pcr_grid_lookup's probe loop: one 16-B load per probe
+__device__ static inline int vg_row(const VgicpMapView &m, unsigned mask, int x, int y, int z) {
+    GridView g;
+    g.tab = m.tab; g.dmask = m.dmask; g.L = 0;
+    const int2 r = pcr_grid_lookup(g, mask, x, y, z);
+    return r.y > 0 ? r.x : -1;
+}
+// c = a b and c = a b^T of row-major 3x3 matrices, every entry (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j with its zero terms and without contraction: the
+// oracle's m3_mul / m3_mul_bt
+__device__ static inline void vg_mul3(const double *a, const double *b, double *c) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) { double s = a[i * 3] * b[j]; s = s + a[i * 3 + 1] * b[3 + j]; s = s + a[i * 3 + 2] * b[6 + j]; c[i * 3 + j] = s; }
+}
+__device__ static inline void vg_mul3_bt(const double *a, const double *b, double *c) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) { double s = a[i * 3] * b[j * 3]; s = s + a[i * 3 + 1] * b[j * 3 + 1]; s = s + a[i * 3 + 2] * b[j * 3 + 2]; c[i * 3 + j] = s; }
+}

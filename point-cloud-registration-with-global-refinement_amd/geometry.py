@@ -118,6 +118,18 @@ class PointCloud:
         out[:, 1, 1] = c[:, 3]; out[:, 1, 2] = out[:, 2, 1] = c[:, 4]; out[:, 2, 2] = c[:, 5]
         return out
 
+    @covariances.setter
+    def covariances(self, value):
+        """(n, 3, 3) matrices (the upper triangle is kept) or (n, 6) rows xx,xy,xz,yy,yz,zz; stored as float32 cov6 on the device."""
+        torch = _torch()
+        shape = tuple(value.shape) if hasattr(value, "shape") else np.asarray(value).shape
+        if len(shape) == 3 and shape[1:] == (3, 3):
+            v = value if isinstance(value, torch.Tensor) else np.asarray(value)
+            value = v.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]]
+        elif not (len(shape) == 2 and shape[1] == 6):
+            raise ValueError(f"covariances must have shape (n, 3, 3) or (n, 6), got {shape}")
+        self._cov = _dev_f32(value, 6)
+
     def __len__(self):
         return 0 if self._xyz is None else int(self._xyz.shape[0])
 

@@ -353,6 +353,184 @@ def color_gradient(cloud: PointCloud, search_param) -> np.ndarray:
     return out[:n].cpu().numpy()
 
 
+# ---- voxelized GICP on a reusable voxel covariance map (pcr_voxel_map_*, pcr_registration_voxelized_gicp; the rule: include/pcr_hip.h)
+def _check_vgicp_rule(fn: str, neighborhood, min_points_per_voxel):
+    if neighborhood not in (1, 7, 27):
+        raise ValueError(f"{fn}: neighborhood must be 1, 7 or 27, got {neighborhood!r}")
+    if not isinstance(min_points_per_voxel, (int, np.integer)) or min_points_per_voxel < 1:
+        raise ValueError(f"{fn}: min_points_per_voxel must be an integer >= 1, got {min_points_per_voxel!r}")
+
+
+def _check_voxel_size(fn: str, voxel_size):
+    try:
+        v = float(voxel_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: voxel_size must be a number greater than 0, got {voxel_size!r}") from None
+    if not (v > 0.0) or not np.isfinite(v):
+        raise ValueError(f"{fn}: voxel_size must be a finite number greater than 0, got {voxel_size!r}")
+    return v
+
+
+class VoxelCovarianceMap:
+    """The target of voxelized GICP (Koide et al., ICRA 2021): per occupied cell of ``voxel_down_sample``'s grid the member count, the mean
+    point and the mean covariance, behind a cell hash on the device.  Built once from ``target.covariances`` (or, without them, from its
+    normals with ``epsilon`` as the GICP estimator forms them), read-only afterwards, and good for any number of registrations until
+    ``close()``.  Rows are in Morton order of the cell index, the order in which ``voxel_down_sample`` lists its points."""
+
+    _handle = None
+
+    def __init__(self, target: PointCloud, voxel_size: float, epsilon: float = 1e-3):
+        self.voxel_size = _check_voxel_size("VoxelCovarianceMap", voxel_size)
+        self.epsilon = float(epsilon)
+        if not np.isfinite(self.epsilon):
+            raise ValueError(f"VoxelCovarianceMap: epsilon must be finite, got {epsilon!r}")
+        if not isinstance(target, PointCloud) or len(target) == 0:
+            raise RuntimeError("VoxelCovarianceMap: the target must be a PointCloud with at least one point")
+        cov = target._cov if target.has_covariances() else None
+        nrm = target._nrm if cov is None and target.has_normals() else None
+        if cov is None and nrm is None:
+            raise RuntimeError("VoxelCovarianceMap: the target has neither covariances nor normals")
+        ctx = _lib.Context.current()
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pcr_voxel_map_create(ctx.handle, _ptr(target.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(target)),
+                                               C.c_double(self.voxel_size), C.c_double(self.epsilon), C.byref(h)), "VoxelCovarianceMap")
+        self._handle = h
+        self._lib = ctx.lib
+        m = C.c_int64(0)
+        ctx.lib.pcr_voxel_map_size(h, C.byref(m))
+        self._cells = int(m.value)
+
+    def close(self):
+        """Destroy the map (waits for the device)."""
+        h, self._handle = self._handle, None
+        if h is not None and h.value:
+            self._lib.pcr_voxel_map_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _open(self):
+        if self._handle is None:
+            raise RuntimeError("VoxelCovarianceMap: the map is closed")
+        return self._handle
+
+    def __len__(self):
+        self._open()
+        return self._cells
+
+    def _read(self, what: str):
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        m = self._cells
+        out = {"cells": torch.empty((m, 3), dtype=torch.int32, device="cuda") if what == "cells" else None,
+               "counts": torch.empty((m,), dtype=torch.int32, device="cuda") if what == "counts" else None,
+               "points": torch.empty((m, 3), dtype=torch.float32, device="cuda") if what == "points" else None,
+               "covariances": torch.empty((m, 6), dtype=torch.float32, device="cuda") if what == "covariances" else None}
+        ctx.check(ctx.lib.pcr_voxel_map_read(ctx.handle, h, _ptr(out["cells"]), _ptr(out["counts"]), _ptr(out["points"]), _ptr(out["covariances"])),
+                  "VoxelCovarianceMap." + what)
+        return out[what]
+
+    @property
+    def cells(self) -> np.ndarray:
+        """(cells, 3) int32: the cell index (ix, iy, iz) of every row"""
+        return self._read("cells").cpu().numpy()
+
+    @property
+    def counts(self) -> np.ndarray:
+        """(cells,) int32: the member count N_v"""
+        return self._read("counts").cpu().numpy()
+
+    @property
+    def points(self) -> np.ndarray:
+        """(cells, 3) float32: the mean point of every cell"""
+        return self._read("points").cpu().numpy()
+
+    @property
+    def covariances(self) -> np.ndarray:
+        """(cells, 6) float32: the mean covariance of every cell, xx,xy,xz,yy,yz,zz"""
+        return self._read("covariances").cpu().numpy()
+
+    def to_point_cloud(self) -> PointCloud:
+        """The cells' means as a cloud that carries the cells' covariances."""
+        pc = PointCloud()
+        pc._xyz = self._read("points")
+        pc._cov = self._read("covariances")
+        return pc
+
+    def correspondences(self, source: PointCloud, T=np.eye(4), neighborhood: int = 1, min_points_per_voxel: int = 1):
+        """The rows (source index, map row) of the rule at the pose ``T``, ordered by source index and then by the neighbourhood's offset
+        order: a device tensor (rows, 2) int32."""
+        _check_vgicp_rule("VoxelCovarianceMap.correspondences", neighborhood, min_points_per_voxel)
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        rows = torch.empty((max(ns, 1) * int(neighborhood), 2), dtype=torch.int32, device="cuda")
+        n = C.c_int64(0)
+        _, Tp = _T(T)
+        ctx.check(ctx.lib.pcr_voxel_map_correspondences(ctx.handle, h, _ptr(source.device_xyz()), C.c_int64(ns), Tp, C.c_int(int(neighborhood)),
+                                                        C.c_int(int(min_points_per_voxel)), _ptr(rows), C.byref(n)), "VoxelCovarianceMap.correspondences")
+        return rows[: n.value]
+
+
+def registration_voxelized_gicp(source: PointCloud, target_or_map, voxel_size=None, init=np.eye(4), estimation_method=None, criteria=None,
+                                neighborhood: int = 1, min_points_per_voxel: int = 1) -> RegistrationResult:
+    """Voxelized GICP (``pcr_registration_voxelized_gicp``, include/pcr_hip.h): the loop of ``registration_generalized_icp`` without its
+    nearest-neighbour search -- a source point is matched to the cell of the target's voxel covariance map it falls into (``neighborhood``
+    1), or to that cell and its 6 / 26 neighbours (7 / 27), and every such row weighs in with the cell's member count.  ``target_or_map`` is
+    a ``VoxelCovarianceMap`` (``voxel_size`` is then ignored; the map serves any number of calls) or a ``PointCloud``, for which a map of
+    ``voxel_size`` is built and closed inside the call.  ``correspondence_set`` holds (source index, map row)."""
+    fn = "registration_voxelized_gicp"
+    estimation = TransformationEstimationForGeneralizedICP() if estimation_method is None else estimation_method
+    if not isinstance(estimation, TransformationEstimationForGeneralizedICP):
+        raise RuntimeError(f"{fn}: {type(estimation).__name__} is not TransformationEstimationForGeneralizedICP")
+    _check_vgicp_rule(fn, neighborhood, min_points_per_voxel)
+    criteria = criteria or ICPConvergenceCriteria()
+    own = None
+    if isinstance(target_or_map, VoxelCovarianceMap):
+        vmap = target_or_map
+        vmap._open()
+    elif isinstance(target_or_map, PointCloud):
+        if voxel_size is None:
+            raise ValueError(f"{fn}: voxel_size is required when the target is a PointCloud")
+        _check_voxel_size(fn, voxel_size)
+        target = target_or_map
+        if len(target) and not target.has_covariances():
+            target = _ensure_gicp_normals(target)
+        own = vmap = VoxelCovarianceMap(target, voxel_size, estimation.epsilon)
+    else:
+        raise TypeError(f"{fn}: the target must be a PointCloud or a VoxelCovarianceMap, got {type(target_or_map).__name__}")
+    try:
+        if len(source) and not source.has_covariances():
+            source = _ensure_gicp_normals(source)
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        corr = torch.empty((max(ns, 1) * int(neighborhood), 2), dtype=torch.int32, device="cuda")
+        res = _lib.PcrResult()
+        _, Tp = _T(init)
+        p = _lib.PcrVgicpParams(int(estimation.kernel.kind), float(estimation.kernel.k), float(estimation.epsilon), float(criteria.relative_fitness),
+                                float(criteria.relative_rmse), int(criteria.max_iteration), int(neighborhood), int(min_points_per_voxel))
+        cov = source._cov if source.has_covariances() else None
+        ctx.check(ctx.lib.pcr_registration_voxelized_gicp(ctx.handle, _ptr(source.device_xyz()), _ptr(cov), _ptr(source.device_normals() if cov is None else None),
+                                                          C.c_int64(ns), vmap._open(), Tp, C.byref(p), C.byref(res), _ptr(corr)), fn)
+        return _result(res, corr)
+    finally:
+        if own is not None:
+            own.close()
+
+
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
                     estimation_method=None, criteria=None, nb_neighbors: int = 30, std_ratio: float = 1.0,
                     normal_knn: int = 20) -> RegistrationResult:
