@@ -541,14 +541,22 @@ int pcr_registration_ransac_feature_matching(pcr_context *ctx, const float *src_
  *    own checks every row, and its count is on the host before any row is read.
  *    SUMS.  Float64, in an order that depends on the list and on the launch geometry only; no floating-point atomics; the same call gives the same
  *    bits on every run.
- *    POINT TO POINT.  T = Eigen::umeyama of the rows (the fit of pcr_registration_icp's update; a scaled pose when with_scaling), the moments
- *    taken about the target point of row 0 so that they do not cancel far from the origin.  RMSE = sqrt(sum |s - t|^2 / C).  Rows that do not
- *    determine a rotation (one row, collinear rows) give what the fit gives on them -- for one row the translation s -> t --, as Eigen does;
- *    with_scaling on source points without spread divides by a zero variance.
+ *    POINT TO POINT.  T = Eigen::umeyama of the rows (the fit of pcr_registration_icp's update; a scaled pose when with_scaling), the target's
+ *    moments taken about the target point of row 0 and the source's about the source point of row 0, so that neither cancels far from the
+ *    origin or far from the other cloud.  RMSE = sqrt(sum |s - t|^2 / C).  Rows that do not determine a rotation (one row, collinear rows)
+ *    give what the fit gives on them -- for one row, or copies of one row, the identity rotation and the translation s -> t --, as Eigen
+ *    does; with_scaling on source points without spread divides by a zero variance: 0 / 0, the pose is not finite (as Eigen's).
  *    POINT TO PLANE.  With n the target normal AS STORED (not normalised): r = (s - t).n, J = [s x n, n], w = the kernel's weight of r (L2: 1,
  *    L1: 1 / |r|, GM: k / (k + r^2)^2), JTJ = sum w J^T J, JTr = sum w J r, solved as the loop solves it (LDLT, pivoted when a pivot is not
  *    positive), the pose Rz Ry Rx and the translation.  A system that cannot be solved gives the identity, and so does a target without normals
- *    (Open3D).  RMSE = sqrt(sum r^2 / C), 0 without target normals.
+ *    (Open3D).  RMSE = sqrt(sum r^2 / C), 0 without target normals.  "Cannot be solved" is decided by the pivots: a system whose rank
+ *    deficiency is exact (a floor, a corridor, a sphere with exact normals: whole columns of J zero) meets an exact zero pivot and gives the
+ *    identity bit for bit; one that is deficient only in exact arithmetic (fewer rows than unknowns, nearly dependent columns) has a last pivot
+ *    of rounding size and either sign, and gives a finite pose that is not pinned.
+ *    L1 AT r == 0.  Open3D divides by zero there: its sums turn NaN, its solve fails and it returns the identity.  Here the weight is
+ *    1 / max(|r|, 1e-300): such a row enters JTJ with 1e300 J^T J, beside which every other row vanishes, and adds nothing to JTr.  The
+ *    update is then finite and a negligible distance from the identity (|T - I| of 1e-280 and less has been seen) but NOT the identity bit for
+ *    bit, and not the fit over the remaining rows either; it is the same bits on every run.  (The loop, pcr_registration_icp, does the same.)
  *    GENERALIZED ICP.  Both clouds carry covariances (cov6 = xx,xy,xz,yy,yz,zz, float32): the rows of pcr_registration_generalized_icp_cov at
  *    T = identity, M = Cs + Ct, W = M^(-1/2), three rows W (s - t) per pair, each weighted by the kernel.  Neither carries covariances and both
  *    carry normals: the rows of pcr_registration_generalized_icp at T = identity (normals normalised, e1 when n.x < -0.99, covariance

@@ -67,8 +67,9 @@ __device__ static inline void corr_row(const CorrArgs &a, int c, const double *o
     if (MODE == CORR_RMSE_POINT) {
         acc[0] += dx * dx + dy * dy + dz * dz;
     } else if (MODE == CORR_P2P) {
-        // u = s - o, v = t - o about the target point of row 0: [0..2] sum u, [3..5] sum v, [6..14] sum v u^T, [15] sum |u|^2
-        const double ux = qx - o[0], uy = qy - o[1], uz = qz - o[2], vx = tx - o[0], vy = ty - o[1], vz = tz - o[2];
+        // u = s - os about the source point of row 0, v = t - o about its target point (each cloud about a point of its own: the list may pair
+        // clouds that lie far apart): [0..2] sum u, [3..5] sum v, [6..14] sum v u^T, [15] sum |u|^2
+        const double ux = qx - o[3], uy = qy - o[4], uz = qz - o[5], vx = tx - o[0], vy = ty - o[1], vz = tz - o[2];
         acc[0] += ux; acc[1] += uy; acc[2] += uz;
         acc[3] += vx; acc[4] += vy; acc[5] += vz;
         acc[6] += vx * ux; acc[7] += vx * uy; acc[8] += vx * uz;
@@ -133,8 +134,11 @@ template <int MODE>
 __global__ void __launch_bounds__(CORR_BS) k_corr_rows(CorrArgs a) {
     constexpr int NV = CorrNV<MODE>::value;
     __shared__ double red[CORR_BS / 16][CORR_NVP];          // one row per 16-lane DPP row
-    double o[3] = {0, 0, 0};
-    if (MODE == CORR_P2P) { const float *t0 = a.tgt + (size_t)a.corres[1] * 3; o[0] = t0[0]; o[1] = t0[1]; o[2] = t0[2]; }
+    double o[6] = {0, 0, 0, 0, 0, 0};            // the origins of the moments: the target point of row 0, then its source point
+    if (MODE == CORR_P2P) {
+        const float *t0 = a.tgt + (size_t)a.corres[1] * 3, *s0 = a.src + (size_t)a.corres[0] * 3;
+        o[0] = t0[0]; o[1] = t0[1]; o[2] = t0[2]; o[3] = s0[0]; o[4] = s0[1]; o[5] = s0[2];
+    }
     double acc[NV];
 #pragma unroll
     for (int k = 0; k < NV; k++) acc[k] = 0.0;
@@ -176,9 +180,9 @@ __global__ void __launch_bounds__(64) k_corr_fit(CorrArgs a, int nb, int with_sc
     double U[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     double fitted = 0.0;
     if (MODE == CORR_P2P) {
-        const float *t0 = a.tgt + (size_t)a.corres[1] * 3;
-        const double org[3] = {t0[0], t0[1], t0[2]};
-        icp_umeyama(S, (double)a.C, org, with_scaling != 0, U);
+        const float *t0 = a.tgt + (size_t)a.corres[1] * 3, *s0 = a.src + (size_t)a.corres[0] * 3;
+        const double org[3] = {t0[0], t0[1], t0[2]}, org_s[3] = {s0[0], s0[1], s0[2]};
+        icp_umeyama(S, (double)a.C, org, with_scaling != 0, U, org_s);
         fitted = 1.0;
     } else if (MODE == CORR_P2PL || MODE == CORR_GICP || MODE == CORR_GICP_COV) {
         double nb6[6], x[6];

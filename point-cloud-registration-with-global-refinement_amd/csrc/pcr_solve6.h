@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/pcr_hip.h"
 
-__device__ static inline double icp_weight(int loss, double k, double r) {
+__host__ __device__ static inline double icp_weight(int loss, double k, double r) {
     if (loss == PCR_LOSS_L1) return 1.0 / fmax(fabs(r), 1e-300);    // Open3D: 1/|r| (unguarded); guard only against r == 0
     if (loss == PCR_LOSS_GM) { const double d = k + r * r; return k / (d * d); }
     return 1.0;
@@ -12,7 +12,7 @@ __device__ static inline double icp_weight(int loss, double k, double r) {
 
 // W = (M^-1)^(1/2), symmetric principal root of an SPD 3x3 (general covariances: no closed form): cyclic Jacobi in
 // float64, fully unrolled (static indexing only -> registers)
-__device__ static inline void icp_sym3_inv_sqrt(const double *M6 /*xx,xy,xz,yy,yz,zz*/, double *W) {
+__host__ __device__ static inline void icp_sym3_inv_sqrt(const double *M6 /*xx,xy,xz,yy,yz,zz*/, double *W) {
     double a[3][3] = {{M6[0], M6[1], M6[2]}, {M6[1], M6[3], M6[4]}, {M6[2], M6[4], M6[5]}};
     double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
 #pragma unroll
@@ -44,7 +44,7 @@ __device__ static inline void icp_sym3_inv_sqrt(const double *M6 /*xx,xy,xz,yy,y
 // 6x6 symmetric solve on ONE lane.  Fast path: LDL^T without pivoting, fully unrolled so that every array lives in
 // registers (no scratch traffic on the critical path of the iteration).  If a pivot is not strictly positive/finite
 // (semi-definite or indefinite system) fall back to the diagonally pivoted LDL^T of Eigen::LDLT on LDS arrays.
-__device__ static bool icp_ldlt6_fast(const double *S /*21 upper-triangular sums*/, const double *b /*6*/, double *x) {
+__host__ __device__ static bool icp_ldlt6_fast(const double *S /*21 upper-triangular sums*/, const double *b /*6*/, double *x) {
     double A[6][6];
     {
         int t = 0;
@@ -94,7 +94,7 @@ __device__ static bool icp_ldlt6_fast(const double *S /*21 upper-triangular sums
 }
 
 // pivoted fallback; w = LDS workspace of >= 36+36+6+6+6 doubles and 6 ints
-__device__ static bool icp_ldlt6_pivoted(const double *S, const double *b6, double *x6, double *w, int *perm) {
+__host__ __device__ static bool icp_ldlt6_pivoted(const double *S, const double *b6, double *x6, double *w, int *perm) {
     double *A = w, *L = w + 36, *D = w + 72, *y = w + 78, *z = w + 84;
     {
         int t = 0;

@@ -12,11 +12,13 @@ __host__ __device__ static inline uint64_t pcr_splitmix64(uint64_t x) {
 }
 
 // Eigen::umeyama(source, target, with_scaling) (Eigen >= 3.3, what TransformationEstimationPointToPoint returns) from the float64 moments of the
-// n pairs (icp_point, P2P modes): M[0..2] = sum u, M[3..5] = sum v, M[6..14] = sum v u^T (row-major), M[15] = sum |u|^2, u = q - o, v = t - o.
+// n pairs (icp_point, P2P modes): M[0..2] = sum u, M[3..5] = sum v, M[6..14] = sum v u^T (row-major), M[15] = sum |u|^2, u = q - os, v = t - o
+// (os = o unless the caller took the source's moments about an origin of its own: a source far from the target would otherwise leave var(u)
+// and sigma as small differences of large sums).
 // sigma = cov(v, u); R = the rotation that maximises tr(R^T sigma), i.e. Umeyama's U S V^T with the reflection fixed, found as Horn's unit
 // quaternion: the eigenvector of the largest eigenvalue of the symmetric 4x4 N(sigma), by cyclic Jacobi in float64 with static indexing only
 // (registers); for sigma of rank >= 2 the same R.  c = tr(R^T sigma) / var(u) = tr(D S) / var(u) (1 without scaling), t = mean t - c R mean q.
-__host__ __device__ static inline void icp_umeyama(const double *M, double n, const double *o, bool scaling, double *U) {
+__host__ __device__ static inline void icp_umeyama(const double *M, double n, const double *o, bool scaling, double *U, const double *os = nullptr) {
     const double inv = 1.0 / n;
     const double mu[3] = {M[0] * inv, M[1] * inv, M[2] * inv}, mv[3] = {M[3] * inv, M[4] * inv, M[5] * inv};
     double sg[3][3];
@@ -76,7 +78,8 @@ __host__ __device__ static inline void icp_umeyama(const double *M, double n, co
             for (int k = 0; k < 3; k++) tr += R[r][k] * sg[r][k];
         c = tr / var;
     }
-    const double ms[3] = {mu[0] + o[0], mu[1] + o[1], mu[2] + o[2]}, md[3] = {mv[0] + o[0], mv[1] + o[1], mv[2] + o[2]};
+    if (!os) os = o;
+    const double ms[3] = {mu[0] + os[0], mu[1] + os[1], mu[2] + os[2]}, md[3] = {mv[0] + o[0], mv[1] + o[1], mv[2] + o[2]};
 #pragma unroll
     for (int r = 0; r < 3; r++) {
         U[r * 4 + 0] = c * R[r][0]; U[r * 4 + 1] = c * R[r][1]; U[r * 4 + 2] = c * R[r][2];
