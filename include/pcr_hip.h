@@ -38,7 +38,8 @@ typedef enum {
     PCR_ENOMEM = -2,
     PCR_EHIP = -3,        /* a HIP runtime call failed; see pcr_last_error() */
     PCR_ENUMERIC = -4,    /* non-finite pose */
-    PCR_ECAPACITY = -5    /* caller buffer too small */
+    PCR_ECAPACITY = -5,   /* caller buffer too small */
+    PCR_DECLINED = 1      /* pcr_debug_scale_clouds only: the form asked for does not serve these inputs; nothing was written */
 } pcr_status;
 
 /* == o3d.geometry.KDTreeSearchParam{KNN,Radius,Hybrid}  (ALL_FUNCTIONS.py:181,185,213,301) */
@@ -800,6 +801,22 @@ int pcr_debug_radius_lists(pcr_context *ctx, int count, const float *const *xyz,
  * cloud): nothing is written then.                                                                                                          */
 int pcr_debug_voxel_grids(pcr_context *ctx, int count, const float *const *xyz, const float *const *attr, const int64_t *n, const double *voxels,
                           int n_scales, int form, float *const *out_xyz, float *const *out_attr, int32_t *out_n, int *taken);
+/* the scale clouds the GICP loops of pcr_multiscale_gicp / pcr_register_pairs_plan consume -- voxel grid, outlier filter (sor_k, sor_std), normals of
+ * the CLEANED cloud (normal_k nearest kept points) oriented by the voxel means of `normals` -- of `count` clouds (xyz[c], optional normals[c]:
+ * n[c] x 3 float32, device; normals itself or single entries may be null; n[c] > 0; count <= 64) at n_scales voxel sizes (1..8).  Cloud c is
+ * prepared as a GICP source for even c and as a target (with its search tree) for odd c, as the lockstep groups number their clouds.  The code
+ * that runs is the product's own preparation, picked by `form`:
+ *   0  scale by scale after the merged voxel pass (the path pcr_multiscale_gicp takes when the batched one declines; any sor_k, normal_k);
+ *   1  all scales of a cloud in one set of batched launches, cloud by cloud (pcr_multiscale_gicp's first choice);
+ *   2  all clouds and scales as one batch (the lockstep groups of pcr_register_pairs_plan; count x n_scales <= 256).
+ * Outputs, problem k = c * n_scales + s: out_xyz[k], out_normals[k] (device, caller buffers of n[c] x 3 float32): the cleaned points and their
+ * normals, row for row in the order the GICP loop receives them (the Morton order of the voxel grid, outliers removed); out_n_voxel[k],
+ * out_n_clean[k] (host): the rows of the voxel cloud and of the cleaned cloud (the rows written).  Finished when it returns.
+ * Returns PCR_DECLINED (1), having written nothing, when forms 1 / 2 do not serve the inputs -- exactly where the product falls back to the next
+ * path: sor_k > 32, normal_k > 32, fewer than 2 scales, or the merged voxel pass declining (pcr_debug_voxel_grids).  Form 0 never declines. */
+int pcr_debug_scale_clouds(pcr_context *ctx, int count, const float *const *xyz, const float *const *normals, const int64_t *n, const double *voxels,
+                           int n_scales, int sor_k, double sor_std, int normal_k, int form, float *const *out_xyz, float *const *out_normals,
+                           int32_t *out_n_voxel, int32_t *out_n_clean);
 /* one GICP linearisation at pose T: search + A.6 sums. JTJ36, JTr6, stats3 = {count, sum d^2, sum r^2} (host) */
 int pcr_debug_gicp_linearize(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src,
                              const float *tgt_xyz, const float *tgt_normals, int64_t n_tgt, double max_dist,

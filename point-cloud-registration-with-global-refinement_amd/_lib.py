@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("PCR_HIP_SO") or os.path.join(_HERE, "libpcr_hip.so")      # (PCR_HIP_SO: diagnostic builds of tools/build_variant.sh)
 
 PCR_OK, PCR_EINVAL, PCR_ENOMEM, PCR_EHIP, PCR_ENUMERIC, PCR_ECAPACITY = 0, -1, -2, -3, -4, -5
+PCR_DECLINED = 1          # pcr_debug_scale_clouds: the form asked for does not serve the inputs
 SEARCH_KNN, SEARCH_RADIUS, SEARCH_HYBRID = 0, 1, 2
 LOSS_L2, LOSS_L1, LOSS_GM = 0, 1, 2
 
@@ -126,6 +127,7 @@ EXPORTS = [
     "pcr_compute_fpfh_feature", "pcr_registration_fgr", "pcr_debug_knn", "pcr_debug_gicp_linearize",
     "pcr_profile_enable", "pcr_profile_read", "pcr_registration_generalized_icp_cov", "pcr_register_pairs", "pcr_pool_profile",
     "pcr_registro_fgr", "pcr_register_pairs_plan", "pcr_debug_feature_nn", "pcr_set_option", "pcr_counter", "pcr_debug_radius_lists", "pcr_debug_voxel_grids",
+    "pcr_debug_scale_clouds",
     "pcr_registration_icp", "pcr_registration_ransac_correspondence", "pcr_registration_ransac_feature_matching", "pcr_debug_ransac_hypotheses",
     "pcr_registration_colored_icp", "pcr_color_gradient", "pcr_voxel_down_sample_ex",
     "pcr_nearest_neighbor_distance", "pcr_point_cloud_distance", "pcr_remove_radius_outlier", "pcr_mean_and_covariance",
@@ -182,6 +184,8 @@ QUERY_PROTOTYPES = {
                                        C.POINTER(C.c_int64)], C.c_int),
     "pcr_registration_voxelized_gicp": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrVgicpParams),
                                          C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }
 
 _lib = None
@@ -244,6 +248,44 @@ def set_option(name: str, value: int) -> None:
     rc = load().pcr_set_option(name.encode(), int(value))
     if rc != PCR_OK:
         raise ValueError(f"pcr_set_option: unknown option {name!r}")
+
+
+def debug_scale_clouds(clouds, priors, voxels, sor_k, sor_std, normal_k, form, fill=-7.0):
+    """Test hook ``pcr_debug_scale_clouds`` (include/pcr_hip.h): the scale clouds the GICP loops consume, made by the preparation code of the
+    path ``form`` names (0 scale by scale, 1 all scales of a cloud batched, 2 all clouds and scales as one batch).  clouds: float32 arrays
+    (n x 3), cloud c a source for even c and a target for odd c; priors: None, or one array / None per cloud.  Returns None when the form
+    declines, else ``out[c][s] = (points, normals, n_voxel, untouched)``: the cleaned rows in the loop's order, the rows of the voxel cloud,
+    and whether every row past the clean count still holds ``fill``."""
+    import numpy as np
+    import torch
+    ctx = Context.current()
+    m, S = len(clouds), len(voxels)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)).cuda()
+    dx = [up(p) for p in clouds]
+    dn = [up(q) if q is not None else None for q in priors] if priors is not None else None
+    ox = [torch.full((len(p), 3), fill, dtype=torch.float32, device="cuda") for p in dx for _ in range(S)]
+    on = [torch.full((len(p), 3), fill, dtype=torch.float32, device="cuda") for p in dx for _ in range(S)]
+    ptr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
+    nv = (C.c_int32 * (m * S))(*([-1] * (m * S))); nc = (C.c_int32 * (m * S))(*([-1] * (m * S)))
+    torch.cuda.synchronize()
+    rc = ctx.lib.pcr_debug_scale_clouds(ctx.handle, m, ptr(dx), ptr(dn) if dn is not None else None, (C.c_int64 * m)(*[len(p) for p in dx]),
+                                        (C.c_double * S)(*voxels), S, int(sor_k), float(sor_std), int(normal_k), int(form), ptr(ox), ptr(on), nv, nc)
+    torch.cuda.synchronize()
+    if rc == PCR_DECLINED:
+        if not (all((t == fill).all().item() for t in ox + on) and all(v == -1 for v in list(nv) + list(nc))):
+            raise RuntimeError("pcr_debug_scale_clouds declined but wrote to the caller's buffers")
+        return None
+    ctx.check(rc, "debug_scale_clouds")
+    out = []
+    for c in range(m):
+        row = []
+        for s in range(S):
+            k = c * S + s
+            cnt = nc[k]
+            untouched = bool((ox[k][cnt:] == fill).all().item() and (on[k][cnt:] == fill).all().item())
+            row.append((ox[k][:cnt].cpu().numpy(), on[k][:cnt].cpu().numpy(), int(nv[k]), untouched))
+        out.append(row)
+    return out
 
 
 class Context:

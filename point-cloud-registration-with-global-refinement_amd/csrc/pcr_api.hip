@@ -621,6 +621,46 @@ static int prep_scale(pcr_context *ctx, const float *xyz, const float *nrm, int6
     return PCR_OK;
 }
 
+// Which inputs the batched preparations (prep_cloud_scales, prep_group_scales) serve: the others go scale by scale (prep_scale).
+static bool batched_prep_serves(int n_scales, int sor_k, int normal_k) { return n_scales >= 2 && n_scales <= 8 && sor_k <= 32 && normal_k <= 32; }
+
+// ALL scales of ONE cloud in one set of batched launches (blockIdx.y = scale), on the stream and arena the caller has made current: voxel grids
+// (one key / sort / scan / mean pass), voxel trees, SOR chain with the normals of the cleaned clouds, cleaned trees of a GICP target (need_tree).
+// clean[s], cnt_in[s], cnt_kept[s]: the cleaned cloud of scale s and where its voxel / clean counts go (device).  *declined: the merged voxel
+// pass does not take these scales (pcr_dev_voxel_multi); nothing but the allocations has happened then.
+static int prep_cloud_scales(pcr_context *ctx, const float *xyz, const float *nrm, int64_t n, const double *b6, const double *voxels, int n_scales, int sor_k,
+                             double sor_std, int normal_k, bool need_tree, DevCloud *clean, int *const *cnt_in, int *const *cnt_kept, bool *declined) {
+    DevCloud vox[8], tmp[8];
+    const DevCloud *ins[8]; DevCloud *outs[8], *trees[8];
+    const float4 *priors[8]; uint8_t *todos[8]; int *todo_counts[8];
+    *declined = false;
+    for (int s = 0; s < n_scales; s++) {
+        PCR_TRY(pcr_alloc_cloud(ctx, &vox[s], (int)n, nrm != nullptr, true));
+        PCR_TRY(pcr_alloc_cloud(ctx, &clean[s], (int)n, true, need_tree));
+        float4 *prior = nrm ? arena<float4>(ctx, n) : nullptr;
+        uint8_t *todo = arena<uint8_t>(ctx, n);
+        int *tc = arena<int>(ctx, 2);
+        if (!todo || !tc || (nrm && !prior)) return PCR_ENOMEM;
+        tmp[s] = clean[s];
+        tmp[s].nrm = prior;                          // compacted voxel-mean normals = orientation prior
+        tmp[s].nrm_final = clean[s].nrm;             // normals of the cleaned cloud, straight from the SOR lists
+        ins[s] = &vox[s]; outs[s] = &tmp[s]; trees[s] = &clean[s];
+        priors[s] = prior; todos[s] = todo; todo_counts[s] = tc + 1;
+    }
+    bool merged = false;
+    PCR_TRY(pcr_dev_voxel_multi(ctx, xyz, nrm, n, b6, voxels, n_scales, vox, &merged));
+    if (!merged) { *declined = true; return PCR_OK; }
+    DevCloud *vp[8];
+    for (int s = 0; s < n_scales; s++) vp[s] = &vox[s];
+    PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp, n_scales));
+    // (round 5: the incomplete normal lists of the TARGETS are searched over the voxel trees too, through the piece lists of the filter pass -- they
+    // used to wait for the cleaned trees and run as a full-range launch with a todo mask)
+    PCR_TRY(pcr_dev_sor_batch(ctx, ins, outs, n_scales, sor_k, sor_std, normal_k, priors, todos, todo_counts, cnt_in, cnt_kept, true));
+    for (int s = 0; s < n_scales; s++) { for (int d = 0; d < 3; d++) { clean[s].key_org[d] = tmp[s].key_org[d]; clean[s].key_unit[d] = tmp[s].key_unit[d]; } clean[s].voxel_lattice = tmp[s].voxel_lattice; }
+    if (need_tree) PCR_TRY(pcr_dev_build_bvh_batch(ctx, trees, n_scales));
+    return PCR_OK;
+}
+
 // ---- Multiscale_GICP with the preprocessing of ALL scales of a cloud in one set of batched launches (blockIdx.y = scale):
 // voxel grids (one key / sort / scan / mean pass), voxel trees (6 launches), SOR chain (7), cleaned target trees (6), exact fallback
 // normals (1): ~33 launches per cloud whatever the number of scales, instead of 13 + 20 per scale.  The two clouds run on their own
@@ -629,7 +669,7 @@ static int prep_scale(pcr_context *ctx, const float *xyz, const float *nrm, int6
 static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
                               int64_t n_tgt, const double *voxels, const double *dists, int n_scales, int sor_k, double sor_std, int normal_k, const double *init_T,
                               const pcr_gicp_params *params, pcr_scale_record *records, int32_t *correspondences, const double *bs, const double *bt) {
-    if (n_scales < 2 || n_scales > 8 || sor_k > 32 || normal_k > 32 || n_src <= 0 || n_tgt <= 0) return 1;
+    if (!batched_prep_serves(n_scales, sor_k, normal_k) || n_src <= 0 || n_tgt <= 0) return 1;
     auto lane_bytes = [&](int64_t n) { return (size_t)n_scales * ((size_t)n + 512) * 1100 + pcr_sort_temp_bytes((size_t)n * n_scales) + (size_t)n * n_scales * 40 + (32u << 20); };
     const size_t blk_s = lane_bytes(n_src), blk_t = lane_bytes(n_tgt);
     PCR_TRY(pcr_arena_reserve(ctx, blk_s + blk_t + pcr_scratch_bytes_for(n_src) + (1u << 20)));
@@ -649,37 +689,11 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
     bool declined = false;
     auto prep_cloud = [&](int which, const float *xyz, const float *nrm, int64_t n, const double *b6, char *block, size_t bytes, hipStream_t lane) -> int {
         SideLane sl(ctx, block, bytes, lane);
-        const bool need_tree = which == 1;               // a GICP target: its tree serves the correspondence search
-        DevCloud vox[8], tmp[8];
-        const DevCloud *ins[8]; DevCloud *outs[8], *trees[8];
-        const float4 *priors[8]; uint8_t *todos[8]; int *todo_counts[8], *cnt_in[8], *cnt_kept[8];
-        float4 *nouts[8];
-        for (int s = 0; s < n_scales; s++) {
-            PCR_TRY(pcr_alloc_cloud(ctx, &vox[s], (int)n, nrm != nullptr, true));
-            PCR_TRY(pcr_alloc_cloud(ctx, &clean[which][s], (int)n, true, need_tree));
-            float4 *prior = nrm ? arena<float4>(ctx, n) : nullptr;
-            uint8_t *todo = arena<uint8_t>(ctx, n);
-            int *tc = arena<int>(ctx, 2);
-            if (!todo || !tc || (nrm && !prior)) return PCR_ENOMEM;
-            tmp[s] = clean[which][s];
-            tmp[s].nrm = prior;                          // compacted voxel-mean normals = orientation prior
-            tmp[s].nrm_final = clean[which][s].nrm;      // normals of the cleaned cloud, straight from the SOR lists
-            ins[s] = &vox[s]; outs[s] = &tmp[s]; trees[s] = &clean[which][s];
-            priors[s] = prior; todos[s] = todo; todo_counts[s] = tc + 1;
-            cnt_in[s] = cnt4 + 4 * s + which; cnt_kept[s] = cnt4 + 4 * s + 2 + which;
-            nouts[s] = clean[which][s].nrm;
-        }
-        bool merged = false;
-        PCR_TRY(pcr_dev_voxel_multi(ctx, xyz, nrm, n, b6, voxels, n_scales, vox, &merged));
-        if (!merged) { declined = true; return PCR_OK; }
-        DevCloud *vp[8];
-        for (int s = 0; s < n_scales; s++) vp[s] = &vox[s];
-        PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp, n_scales));
-        // (round 5: the incomplete normal lists of the TARGETS are searched over the voxel trees too, through the piece lists of the filter pass -- they
-        // used to wait for the cleaned trees and run as a full-range launch with a todo mask)
-        PCR_TRY(pcr_dev_sor_batch(ctx, ins, outs, n_scales, sor_k, sor_std, normal_k, priors, todos, todo_counts, cnt_in, cnt_kept, true));
-        for (int s = 0; s < n_scales; s++) { for (int d = 0; d < 3; d++) { clean[which][s].key_org[d] = tmp[s].key_org[d]; clean[which][s].key_unit[d] = tmp[s].key_unit[d]; } clean[which][s].voxel_lattice = tmp[s].voxel_lattice; }
-        if (need_tree) PCR_TRY(pcr_dev_build_bvh_batch(ctx, trees, n_scales));
+        int *cnt_in[8], *cnt_kept[8];
+        for (int s = 0; s < n_scales; s++) { cnt_in[s] = cnt4 + 4 * s + which; cnt_kept[s] = cnt4 + 4 * s + 2 + which; }
+        // (which == 1: a GICP target, its tree serves the correspondence search)
+        PCR_TRY(prep_cloud_scales(ctx, xyz, nrm, n, b6, voxels, n_scales, sor_k, sor_std, normal_k, which == 1, clean[which], cnt_in, cnt_kept, &declined));
+        if (declined) return PCR_OK;
         PCR_HIP_CHECK(ctx, hipEventRecord(ctx->lane_ev[which], ctx->stream));
         return PCR_OK;
     };
@@ -707,6 +721,58 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
     return PCR_OK;
 }
 
+// ALL clouds and scales of a lockstep group as one batch (blockIdx.y = cloud x scale), on the context's stream: voxel grids, voxel trees, SOR chains
+// with the normals of the cleaned clouds, cleaned trees of the GICP targets (odd c).  Problem k = c * n_scales + s: clean[k] its cleaned cloud,
+// cnt[2 k], cnt[2 k + 1] (device) its voxel and clean counts.  nrm[c] may be null cloud by cloud.  *declined: the merged voxel pass does not take
+// these clouds (pcr_dev_voxel_multi_batch); nothing but the allocations has happened then.
+static int prep_group_scales(pcr_context *ctx, int C, const float *const *xyz, const float *const *nrm, const int64_t *n, const double *b6, const double *voxels,
+                             int n_scales, int sor_k, double sor_std, int normal_k, std::vector<DevCloud> &clean, int *cnt, bool *declined) {
+    const size_t K = (size_t)C * n_scales;
+    *declined = false;
+    bool any_nrm = false;
+    for (int c = 0; c < C; c++) any_nrm = any_nrm || nrm[c];
+    std::vector<DevCloud> vox(K), tmp(K);
+    clean.assign(K, DevCloud());
+    std::vector<const float4 *> priors(K); std::vector<uint8_t *> todos(K);
+    std::vector<int *> tcs(K), cin(K), ckept(K);
+    for (int c = 0; c < C; c++) {
+        const bool need_tree = (c & 1) == 1;
+        for (int s = 0; s < n_scales; s++) {
+            const size_t k = (size_t)c * n_scales + s;
+            PCR_TRY(pcr_alloc_cloud(ctx, &vox[k], (int)n[c], nrm[c] != nullptr, true));
+            PCR_TRY(pcr_alloc_cloud(ctx, &clean[k], (int)n[c], true, need_tree));
+            float4 *prior = nrm[c] ? arena<float4>(ctx, n[c]) : nullptr;
+            uint8_t *todo = arena<uint8_t>(ctx, n[c]);
+            int *tc = arena<int>(ctx, 2);
+            if (!todo || !tc || (nrm[c] && !prior)) return PCR_ENOMEM;
+            tmp[k] = clean[k]; tmp[k].nrm = prior; tmp[k].nrm_final = clean[k].nrm;
+            priors[k] = prior; todos[k] = todo; tcs[k] = tc + 1; cin[k] = cnt + 2 * k; ckept[k] = cnt + 2 * k + 1;
+        }
+    }
+    bool merged = false;
+    PCR_TRY(pcr_dev_voxel_multi_batch(ctx, C, xyz, any_nrm ? nrm : nullptr, n, b6, voxels, n_scales, vox.data(), &merged));
+    if (!merged) { *declined = true; return PCR_OK; }
+    {
+        std::vector<DevCloud *> vp(K);
+        for (size_t k = 0; k < K; k++) vp[k] = &vox[k];
+        PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp.data(), (int)K));
+    }
+    {   // the filter chains of ALL clouds and scales of the group as one batch (round 5: sources and targets were two batches -- twice the launches, and
+        // twice the tails of the list-driven searches); incomplete normal lists are searched over the voxel trees (piece lists of the filter pass)
+        std::vector<const DevCloud *> ins(K); std::vector<DevCloud *> outs(K);
+        for (size_t k = 0; k < K; k++) { ins[k] = &vox[k]; outs[k] = &tmp[k]; }
+        PCR_TRY(pcr_dev_sor_batch(ctx, ins.data(), outs.data(), (int)K, sor_k, sor_std, normal_k, priors.data(), todos.data(), tcs.data(), cin.data(), ckept.data(), true));
+    }
+    for (size_t k = 0; k < K; k++) { for (int d = 0; d < 3; d++) { clean[k].key_org[d] = tmp[k].key_org[d]; clean[k].key_unit[d] = tmp[k].key_unit[d]; } clean[k].voxel_lattice = tmp[k].voxel_lattice; }
+    {
+        std::vector<DevCloud *> trees;
+        for (int c = 1; c < C; c += 2)
+            for (int s = 0; s < n_scales; s++) trees.push_back(&clean[(size_t)c * n_scales + s]);
+        if (!trees.empty()) PCR_TRY(pcr_dev_build_bvh_batch(ctx, trees.data(), (int)trees.size()));
+    }
+    return PCR_OK;
+}
+
 // ---- Multiscale_GICP of a GROUP of G pairs through the same launches: bounds (2 launches), voxel grids of all clouds and scales
 // (one key / sort / scan / mean pass), voxel trees, SOR chains, cleaned target trees and fallback normals (one batch each, blockIdx.y
 // = cloud x scale), then per scale ONE lockstep GICP loop over the G pairs (pcr_dev_gicp_group).  Everything on the context's stream:
@@ -714,10 +780,9 @@ static int multiscale_batched(pcr_context *ctx, const float *src_xyz, const floa
 // bit-identical results.  Returns 1 (nothing enqueued but the bounds) when the merged voxel pass declines: the caller falls back.
 static int multiscale_group(pcr_context *ctx, pcr_pair_ex *const *px, int G, const double *voxels, const double *given_dists /* n_scales, radius_rule 0 */, int radius_rule,
                             int n_scales, int sor_k, double sor_std, int normal_k, const pcr_gicp_params *params) {
-    if (G < 1 || G > 32 || n_scales < 2 || n_scales > 8 || sor_k > 32 || normal_k > 32) return 1;
+    if (G < 1 || G > 32 || !batched_prep_serves(n_scales, sor_k, normal_k)) return 1;
     const int C = 2 * G;                                  // cloud c = 2 g + which (0 source, 1 target)
     std::vector<const float *> xyz((size_t)C), nrm((size_t)C); std::vector<int64_t> n((size_t)C);
-    bool any_nrm = false;
     size_t total = 0;
     for (int g = 0; g < G; g++) {
         const pcr_pair &p = px[g]->base;
@@ -725,7 +790,6 @@ static int multiscale_group(pcr_context *ctx, pcr_pair_ex *const *px, int G, con
         PCR_TRY(check_T(ctx, p.init_T));
         xyz[2 * g] = p.src_xyz; xyz[2 * g + 1] = p.tgt_xyz; nrm[2 * g] = p.src_normals; nrm[2 * g + 1] = p.tgt_normals;
         n[2 * g] = p.n_src; n[2 * g + 1] = p.n_tgt;
-        any_nrm = any_nrm || p.src_normals || p.tgt_normals;
     }
     for (int c = 0; c < C; c++) total += (size_t)n_scales * ((size_t)n[c] + 512) * 1100 + pcr_sort_temp_bytes((size_t)n[c] * n_scales) + (size_t)n[c] * n_scales * 40 + (8u << 20);
     PCR_TRY(pcr_arena_reserve(ctx, total + (16u << 20)));
@@ -743,49 +807,10 @@ static int multiscale_group(pcr_context *ctx, pcr_pair_ex *const *px, int G, con
     }
     int *cnt = arena<int>(ctx, (size_t)C * n_scales * 2);          // [c][s]: voxel count, clean count
     if (!cnt) return PCR_ENOMEM;
-    std::vector<DevCloud> vox((size_t)C * n_scales), clean((size_t)C * n_scales), tmp((size_t)C * n_scales);
-    std::vector<const float4 *> priors((size_t)C * n_scales); std::vector<uint8_t *> todos((size_t)C * n_scales);
-    std::vector<int *> tcs((size_t)C * n_scales), cin((size_t)C * n_scales), ckept((size_t)C * n_scales);
-    for (int c = 0; c < C; c++) {
-        const bool need_tree = (c & 1) == 1;
-        for (int s = 0; s < n_scales; s++) {
-            const size_t k = (size_t)c * n_scales + s;
-            PCR_TRY(pcr_alloc_cloud(ctx, &vox[k], (int)n[c], nrm[c] != nullptr, true));
-            PCR_TRY(pcr_alloc_cloud(ctx, &clean[k], (int)n[c], true, need_tree));
-            float4 *prior = nrm[c] ? arena<float4>(ctx, n[c]) : nullptr;
-            uint8_t *todo = arena<uint8_t>(ctx, n[c]);
-            int *tc = arena<int>(ctx, 2);
-            if (!todo || !tc || (nrm[c] && !prior)) return PCR_ENOMEM;
-            tmp[k] = clean[k]; tmp[k].nrm = prior; tmp[k].nrm_final = clean[k].nrm;
-            priors[k] = prior; todos[k] = todo; tcs[k] = tc + 1; cin[k] = cnt + 2 * k; ckept[k] = cnt + 2 * k + 1;
-        }
-    }
-    bool merged = false;
-    PCR_TRY(pcr_dev_voxel_multi_batch(ctx, C, xyz.data(), any_nrm ? nrm.data() : nullptr, n.data(), b6.data(), voxels, n_scales, vox.data(), &merged));
-    if (!merged) return 1;
-    {
-        std::vector<DevCloud *> vp((size_t)C * n_scales);
-        for (size_t k = 0; k < vp.size(); k++) vp[k] = &vox[k];
-        PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp.data(), (int)vp.size()));
-    }
-    {   // the filter chains of ALL clouds and scales of the group as one batch (round 5: sources and targets were two batches -- twice the launches, and
-        // twice the tails of the list-driven searches); incomplete normal lists are searched over the voxel trees (piece lists of the filter pass)
-        std::vector<const DevCloud *> ins; std::vector<DevCloud *> outs; std::vector<const float4 *> pr; std::vector<uint8_t *> td; std::vector<int *> tc, ci, ck;
-        for (size_t k = 0; k < (size_t)C * n_scales; k++) {
-            ins.push_back(&vox[k]); outs.push_back(&tmp[k]); pr.push_back(priors[k]); td.push_back(todos[k]); tc.push_back(tcs[k]); ci.push_back(cin[k]); ck.push_back(ckept[k]);
-        }
-        PCR_TRY(pcr_dev_sor_batch(ctx, ins.data(), outs.data(), (int)ins.size(), sor_k, sor_std, normal_k, pr.data(), td.data(), tc.data(), ci.data(), ck.data(), true));
-    }
-    for (size_t k = 0; k < clean.size(); k++) { for (int d = 0; d < 3; d++) { clean[k].key_org[d] = tmp[k].key_org[d]; clean[k].key_unit[d] = tmp[k].key_unit[d]; } clean[k].voxel_lattice = tmp[k].voxel_lattice; }
-    {
-        std::vector<DevCloud *> trees; std::vector<const float4 *> pr; std::vector<float4 *> no; std::vector<const uint8_t *> td;
-        for (int g = 0; g < G; g++)
-            for (int s = 0; s < n_scales; s++) {
-                const size_t k = (size_t)(2 * g + 1) * n_scales + s;
-                trees.push_back(&clean[k]); pr.push_back(priors[k]); no.push_back(clean[k].nrm); td.push_back(todos[k]);
-            }
-        PCR_TRY(pcr_dev_build_bvh_batch(ctx, trees.data(), (int)trees.size()));
-    }
+    std::vector<DevCloud> clean;
+    bool declined = false;
+    PCR_TRY(prep_group_scales(ctx, C, xyz.data(), nrm.data(), n.data(), b6.data(), voxels, n_scales, sor_k, sor_std, normal_k, clean, cnt, &declined));
+    if (declined) return 1;
     // ---- the GICP loops, one lockstep loop per scale
     std::vector<double> T((size_t)G * 16), md((size_t)G);
     std::vector<pcr_result> res((size_t)G);
@@ -834,6 +859,75 @@ static int multiscale_group(pcr_context *ctx, pcr_pair_ex *const *px, int G, con
             for (int w = 0; w < 2; w++) { r.n_voxel[w] = h[2 * ((size_t)(2 * g + w) * n_scales + s)]; r.n_clean[w] = h[2 * ((size_t)(2 * g + w) * n_scales + s) + 1]; }
         }
     return PCR_OK;
+}
+
+// the scale clouds the GICP loops receive (cleaned points and their normals, in the loops' own order), made by the preparation code of the path
+// that `form` names: 0 prep_scale after the merged voxel pass, as the scale-by-scale path of pcr_multiscale_gicp; 1 prep_cloud_scales, as its
+// batched path; 2 prep_group_scales, as the lockstep groups.  What tests/test_gpu_scale_normals.py compares.
+extern "C" int pcr_debug_scale_clouds(pcr_context *ctx, int count, const float *const *xyz, const float *const *normals, const int64_t *n, const double *voxels,
+                                      int n_scales, int sor_k, double sor_std, int normal_k, int form, float *const *out_xyz, float *const *out_normals,
+                                      int32_t *out_n_voxel, int32_t *out_n_clean) {
+    return pcr_api_call(ctx, [&]() -> int {
+    if (count < 1 || count > 64 || n_scales < 1 || n_scales > 8 || form < 0 || form > 2 || !xyz || !n || !voxels || !out_xyz || !out_normals || !out_n_voxel || !out_n_clean) return PCR_EINVAL;
+    if (sor_k < 1 || !(sor_std > 0.0) || normal_k < 1) { ctx->err = "nb_neighbors < 1, std_ratio <= 0 or knn < 1"; return PCR_EINVAL; }
+    for (int s = 0; s < n_scales; s++) if (!(voxels[s] > 0.0)) { ctx->err = "voxel_size <= 0"; return PCR_EINVAL; }
+    const size_t K = (size_t)count * n_scales;
+    size_t bytes = 16u << 20;
+    for (int c = 0; c < count; c++) {
+        if (n[c] <= 0 || n[c] > 0x7fffffff / 4 / n_scales || !xyz[c]) return PCR_EINVAL;
+        for (int s = 0; s < n_scales; s++) if (!out_xyz[c * n_scales + s] || !out_normals[c * n_scales + s]) return PCR_EINVAL;
+        bytes += (size_t)n_scales * ((size_t)n[c] + 512) * 1100 + pcr_sort_temp_bytes((size_t)n[c] * n_scales) + (size_t)n[c] * n_scales * 40 + (8u << 20);
+        if (form == 0) bytes += (size_t)n_scales * 2 * pcr_scratch_bytes_for(n[c]);
+    }
+    if (form != 0 && !batched_prep_serves(n_scales, sor_k, normal_k)) return PCR_DECLINED;
+    PCR_TRY(pcr_arena_reserve(ctx, bytes));
+    std::vector<const float *> nrm((size_t)count);
+    for (int c = 0; c < count; c++) nrm[c] = normals ? normals[c] : nullptr;
+    std::vector<double> b6((size_t)count * 6);
+    if (form == 2) PCR_TRY(pcr_dev_bounds_batch(ctx, count, xyz, n, b6.data()));
+    else for (int c = 0; c < count; c++) PCR_TRY(pcr_dev_bounds(ctx, xyz[c], n[c], &b6[6 * (size_t)c]));
+    int *cnt = arena<int>(ctx, K * 2);                     // [c][s]: voxel count, clean count
+    if (!cnt) return PCR_ENOMEM;
+    std::vector<DevCloud> clean(K);
+    if (form == 0) {
+        for (int c = 0; c < count; c++) {
+            DevCloud vox[8]; bool merged = false;
+            if (n_scales >= 2) {                           // the voxel stage of all scales in one pass, then scale by scale (multiscale_gicp_impl)
+                DevCloud *vp[8];
+                for (int s = 0; s < n_scales; s++) { PCR_TRY(pcr_alloc_cloud(ctx, &vox[s], (int)n[c], nrm[c] != nullptr, true)); vp[s] = &vox[s]; }
+                PCR_TRY(pcr_dev_voxel_multi(ctx, xyz[c], nrm[c], n[c], &b6[6 * (size_t)c], voxels, n_scales, vox, &merged));
+                if (merged) PCR_TRY(pcr_dev_build_bvh_batch(ctx, vp, n_scales));
+            }
+            for (int s = 0; s < n_scales; s++) {
+                const size_t k = (size_t)c * n_scales + s;
+                PCR_TRY(prep_scale(ctx, xyz[c], nrm[c], n[c], &b6[6 * (size_t)c], voxels[s], sor_k, sor_std, normal_k, &clean[k], cnt + 2 * k, cnt + 2 * k + 1, (c & 1) == 1,
+                                   merged ? &vox[s] : nullptr));
+            }
+        }
+    } else if (form == 1) {
+        for (int c = 0; c < count; c++) {
+            int *cnt_in[8], *cnt_kept[8]; bool declined = false;
+            for (int s = 0; s < n_scales; s++) { cnt_in[s] = cnt + 2 * ((size_t)c * n_scales + s); cnt_kept[s] = cnt_in[s] + 1; }
+            PCR_TRY(prep_cloud_scales(ctx, xyz[c], nrm[c], n[c], &b6[6 * (size_t)c], voxels, n_scales, sor_k, sor_std, normal_k, (c & 1) == 1, &clean[(size_t)c * n_scales], cnt_in,
+                                      cnt_kept, &declined));
+            if (declined) return PCR_DECLINED;              // (nothing reaches the caller's buffers before every cloud has been taken)
+        }
+    } else {
+        if (K > PCR_MAX_GROUP_BATCH) { ctx->err = "debug_scale_clouds: count x n_scales above the batch limit"; return PCR_EINVAL; }
+        bool declined = false;
+        PCR_TRY(prep_group_scales(ctx, count, xyz, nrm.data(), n, b6.data(), voxels, n_scales, sor_k, sor_std, normal_k, clean, cnt, &declined));
+        if (declined) return PCR_DECLINED;
+    }
+    for (size_t k = 0; k < K; k++) {
+        PCR_TRY(pcr_dev_pack_f4_to_f3(ctx, clean[k].pts, clean[k].n, clean[k].cap, out_xyz[k]));
+        PCR_TRY(pcr_dev_pack_f4_to_f3(ctx, clean[k].nrm, clean[k].n, clean[k].cap, out_normals[k]));
+    }
+    std::vector<int> h(K * 2);
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), cnt, sizeof(int) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < K; k++) { out_n_voxel[k] = h[2 * k]; out_n_clean[k] = h[2 * k + 1]; }
+    return PCR_OK;
+    });
 }
 
 static int multiscale_gicp_impl(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src,
