@@ -341,8 +341,31 @@ int pcr_color_gradient(pcr_context *ctx, const float *xyz, const float *normals,
  *   and |d RMSE| < relative_rmse, or max_iteration.  fitness = (source points with at least one row) / n_src,
  *   inlier_rmse = sqrt(sum over the rows of |q_i - mu_v|^2 / rows), n_correspondences = the number of rows.  There is no
  *   max_correspondence_distance: the voxel size plays its part.
- * All cloud, covariance and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed; it is
- * read-only after creation, and any context on the same device may use it for any number of calls. */
+ *
+ * A map that grows (pcr_voxel_map_create_on_grid / _insert / _merge / _remove_far).  Open3D has no such calls either; this is their specification.
+ * GRID.  A map has a voxel size and a grid_min g (three float64); its origin is g - voxel_size / 2 per axis in float64, the expression of MAP with g
+ *   standing in for the cloud's minimum.  A map made by pcr_voxel_map_create has g = the target's minimum.  Two maps are on the same grid iff
+ *   their voxel sizes and their origins are equal bit for bit.
+ * MAP ON A GIVEN GRID, AT A POSE.  Input: n >= 1 points with cov6 or normals (exactly one, as for MAP), a grid, and an optional pose T (float64
+ *   4x4, row-major; none is the identity).  Member point: p' = float32(q) with q the float64 expression of ROWS,
+ *   ((T_r0 x + T_r1 y) + T_r2 z) + T_r3, every operation rounded once, no fused multiply-add.  Member covariance: first formed as MAP forms it (the
+ *   cov6 as given, or R diag(epsilon, 1, 1) R^T from the normal, in float32), then rotated: C' = float32((R C) R^T) with R the upper 3x3 of T in
+ *   float64, both products entry by entry as (a0 b0 + a1 b1) + a2 b2 without contraction.  With T the identity p' and C' are the inputs bit for
+ *   bit (but for the sign of a zero: -0 comes out as +0), so there is no special case.  The cells, counts, means and covariances are those of MAP over (p', C') on the given grid, rows in Morton order.  A member whose cell
+ *   index lies outside [0, 2^21) on any axis -- below the origin counts too -- is PCR_EINVAL: xyz lies outside the map's grid; nothing is changed.
+ * MERGE(A, B).  A and B are on the same grid (otherwise PCR_EINVAL).  One row per cell occupied in A or in B, in Morton order.  A cell in only one
+ *   of them keeps that row bit for bit.  A cell in both gets N = N_a + N_b (a sum above 2^31 - 1 is PCR_EINVAL) and, for each of its nine channels
+ *   (3 mean, 6 covariance), float32((float64(N_a) float64(a) + float64(N_b) float64(b)) / float64(N)): the sum, then the division, then one
+ *   rounding to float32.  The two products are exact for counts below 2^29 (a 24-bit significand times an integer under 2^29 fits the 53 bits of
+ *   a float64), so a fused multiply-add cannot change the result there.  MERGE is commutative bit for bit; it is not associative.
+ * INSERT(map, cloud, T) = MERGE(map, the map of the cloud at T on the map's grid).
+ * REMOVE_FAR(map, center c (float64 x3), max_distance r).  A row is kept iff d^2 < r^2 (strict), with d^2 in float64 from the float32 mean:
+ *   differences, squares and sums in the order x, y, z, each rounded once, and r^2 = r r.  Kept rows keep their bits and their relative order.
+ * A map never has zero rows: an operation that would leave none is PCR_EINVAL (would leave the map empty) and changes nothing.
+ * All cloud, covariance and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed, and any
+ * context on the same device may use it for any number of calls.  _insert, _merge and _remove_far change it, all or nothing and finished when they
+ * return: the new block is built, swapped in, and the old one freed (which waits for the device); on any error the map is exactly as before.
+ * While such a call runs no other call may use the map, and map rows in an earlier correspondence set are stale afterwards (row indices change). */
 typedef struct pcr_voxel_map pcr_voxel_map;
 typedef struct {
     int32_t loss;             /* the fields of pcr_gicp_params ...            */
@@ -376,6 +399,21 @@ int pcr_voxel_map_correspondences(pcr_context *ctx, const pcr_voxel_map *map, co
 int pcr_registration_voxelized_gicp(pcr_context *ctx, const float *src_xyz, const float *src_cov6, const float *src_normals, int64_t n_src,
                                     const pcr_voxel_map *map, const double *init_T, const pcr_vgicp_params *params, pcr_result *result,
                                     int32_t *correspondences);
+/* The map of a cloud on the grid (grid_min3, voxel_size) at the pose T (MAP ON A GIVEN GRID; T optional: NULL is the identity).  The arguments of
+ * pcr_voxel_map_create and their refusals, plus: a non-finite value in grid_min3 or T (named), a member outside the grid (xyz lies outside the
+ * map's grid).  Finished when it returns. */
+int pcr_voxel_map_create_on_grid(pcr_context *ctx, const float *xyz, const float *cov6, const float *normals, int64_t n, double voxel_size, double epsilon,
+                                 const double *grid_min3, const double *T, pcr_voxel_map **out);
+/* map <- INSERT(map, cloud, T); T optional.  A NULL map, a map on another device than the context, the cloud refusals of the call above. */
+int pcr_voxel_map_insert(pcr_context *ctx, pcr_voxel_map *map, const float *xyz, const float *cov6, const float *normals, int64_t n, double epsilon,
+                         const double *T);
+/* map <- MERGE(map, other); other is unchanged.  other == map, a NULL map, maps on another device or on different grids: PCR_EINVAL. */
+int pcr_voxel_map_merge(pcr_context *ctx, pcr_voxel_map *map, const pcr_voxel_map *other);
+/* map <- REMOVE_FAR(map, center3, max_distance); *removed (optional, host) = rows dropped.  A non-finite center3, a max_distance that is not
+ * finite or <= 0: PCR_EINVAL naming the argument. */
+int pcr_voxel_map_remove_far(pcr_context *ctx, pcr_voxel_map *map, const double *center3, double max_distance, int64_t *removed);
+/* the grid of a map, each output optional (host): grid_min3, origin3 = grid_min3 - voxel_size / 2, voxel_size */
+int pcr_voxel_map_grid(const pcr_voxel_map *map, double *grid_min3, double *origin3, double *voxel_size);
 
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)

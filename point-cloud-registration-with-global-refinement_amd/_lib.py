@@ -139,6 +139,7 @@ EXPORTS = [
     "pcr_boundary_points",
     "pcr_voxel_map_create", "pcr_voxel_map_destroy", "pcr_voxel_map_size", "pcr_voxel_map_read", "pcr_voxel_map_correspondences",
     "pcr_registration_voxelized_gicp",
+    "pcr_voxel_map_create_on_grid", "pcr_voxel_map_insert", "pcr_voxel_map_merge", "pcr_voxel_map_remove_far", "pcr_voxel_map_grid",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list and the boundary detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -184,6 +185,12 @@ QUERY_PROTOTYPES = {
                                        C.POINTER(C.c_int64)], C.c_int),
     "pcr_registration_voxelized_gicp": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrVgicpParams),
                                          C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_voxel_map_create_on_grid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_voxel_map_insert": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_double)], C.c_int),
+    "pcr_voxel_map_merge": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_voxel_map_remove_far": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_voxel_map_grid": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

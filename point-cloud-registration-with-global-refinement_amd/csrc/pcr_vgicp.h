@@ -12,7 +12,31 @@ struct VgicpMapView {
     double org[3], voxel;                  // origin = min - voxel / 2 in float64: the grid of voxel_down_sample
 };
 
-#define VG_NO_CELL (-4)                    // a coordinate with every candidate cell outside the grid (also: a non-finite coordinate)
+// The map behind the C handle (pcr_vgicp.hip creates, reads and destroys it; pcr_vmap.hip grows and trims it by swapping in a new block).
+struct pcr_voxel_map {
+    int device = 0;
+    int64_t cells = 0;
+    char *block = nullptr;       // the one allocation: rows, keys, count word, cell hash
+    size_t bytes = 0;
+    VgicpMapView view;
+    uint64_t *keys = nullptr;    // Morton keys of the rows (ascending)
+    int *n_dev = nullptr;        // the row count on the device (what the hash build reads)
+    double grid_min[3] = {0, 0, 0};     // g of the GRID rule: view.org = g - voxel / 2
+};
+// device bytes of a map of `cells` rows: rows, keys, the count word, the cell hash and its mask word (every array rounded up to 256 B)
+static inline size_t vg_block_bytes(int64_t cells) {
+    return (size_t)cells * (sizeof(float4) * 3 + sizeof(uint64_t)) + (size_t)pcr_grid_slots((unsigned)cells) * sizeof(GridEntry) + 16 * 256;
+}
+
+// host helpers of pcr_vgicp.hip that pcr_vmap.hip calls too: PCR_EINVAL naming the first of up to three arrays that holds a non-finite value
+// (one read-back); the map / pose argument checks; the member covariances of n points as packed cov6 (enqueues only)
+struct pcr_context;
+int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr, const size_t *count, const char *const *name, int arrays);
+int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call);
+int vg_check_T(pcr_context *ctx, const char *call, const char *name, const double *T);
+int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, double eps, int64_t n, float *out6);
+
+#define VG_NO_CELL (-4)                   // a coordinate with every candidate cell outside the grid (also: a non-finite coordinate)
 
 // q = T p with q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 in float64, every product and sum rounded once: numpy's elementwise expression gives
 // the same bits, so the cell of q is decided (T: the first three rows of the pose, row-major)

@@ -200,15 +200,7 @@ static int vgicp_loop(pcr_context *ctx, const float *src_xyz, const float *src_c
 
 // ================================================================ the map
 
-struct pcr_voxel_map {
-    int device = 0;
-    int64_t cells = 0;
-    char *block = nullptr;       // the one allocation: rows, keys, count word, cell hash
-    size_t bytes = 0;
-    VgicpMapView view;
-    uint64_t *keys = nullptr;    // Morton keys of the rows (ascending)
-    int *n_dev = nullptr;        // the row count on the device (what the hash build reads)
-};
+// (struct pcr_voxel_map: pcr_vgicp.h)
 
 // ---- input checks on the device: *flag |= bit when a value is not finite
 __global__ void __launch_bounds__(VG_BS) k_vg_nonfinite(const float *__restrict__ v, size_t count, int bit, int *__restrict__ flag) {
@@ -322,7 +314,7 @@ __global__ void __launch_bounds__(VG_BS) k_vmap_emit(const int32_t *__restrict__
 static unsigned vg_blocks(size_t n) { return (unsigned)((n + VG_BS - 1) / VG_BS); }
 
 // PCR_EINVAL naming the first of up to three arrays that holds a non-finite value (one read-back)
-static int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr, const size_t *count, const char *const *name, int arrays) {
+int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr, const size_t *count, const char *const *name, int arrays) {
     int *flag = arena<int>(ctx, 1);
     if (!flag) return PCR_ENOMEM;
     PCR_HIP_CHECK(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
@@ -338,20 +330,20 @@ static int vg_check_finite(pcr_context *ctx, const char *call, const float *cons
     return PCR_OK;
 }
 
-static int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call) {
+int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call) {
     if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
     if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
+    return PCR_OK;
+}
+// the member covariances of n points (k_vmap_member_cov) for the units that grow a map: packed cov6 into out6; enqueues only
+int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, double eps, int64_t n, float *out6) {
+    PCR_LAUNCH(ctx, k_vmap_member_cov, dim3(vg_blocks((size_t)n)), dim3(VG_BS), 0, ctx->stream, cov6, normals, eps, (int)n, (float *)nullptr, (float *)nullptr, out6);
     return PCR_OK;
 }
 static int vg_check_rule(pcr_context *ctx, const char *call, int neighborhood, int min_points) {
     if (neighborhood != 1 && neighborhood != 7 && neighborhood != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
     if (min_points < 1) { ctx->err = std::string(call) + ": min_points_per_voxel < 1"; return PCR_EINVAL; }
     return PCR_OK;
-}
-
-// device bytes of a map of `cells` rows: rows, keys, the count word, the cell hash and its mask word (every array rounded up to 256 B)
-static size_t vg_block_bytes(int64_t cells) {
-    return (size_t)cells * (sizeof(float4) * 3 + sizeof(uint64_t)) + (size_t)pcr_grid_slots((unsigned)cells) * sizeof(GridEntry) + 16 * 256;
 }
 
 extern "C" int pcr_voxel_map_create(pcr_context *ctx, const float *xyz, const float *cov6, const float *normals, int64_t n, double voxel_size, double epsilon,
@@ -407,6 +399,7 @@ extern "C" int pcr_voxel_map_create(pcr_context *ctx, const float *xyz, const fl
         m->view.tab = gv.tab; m->view.dmask = gv.dmask; m->view.mean4 = mean4; m->view.cov8 = cov8;
         for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
         m->view.voxel = voxel_size;
+        for (int d = 0; d < 3; d++) m->grid_min[d] = b6[d];
         int *count = arena<int>(ctx, (size_t)cells);
         if (!count) return PCR_ENOMEM;
         PCR_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(int) * (size_t)cells, ctx->stream));
@@ -466,7 +459,7 @@ static int vg_rows(pcr_context *ctx, const pcr_voxel_map *map, const float *src_
 }
 static size_t vg_rows_scratch(int64_t n_src, int nbh) { return (size_t)(n_src > 0 ? n_src : 1) * nbh * 10 + (1u << 20); }
 
-static int vg_check_T(pcr_context *ctx, const char *call, const char *name, const double *T) {
+int vg_check_T(pcr_context *ctx, const char *call, const char *name, const double *T) {
     if (!T) { ctx->err = std::string(call) + ": " + name + " is null"; return PCR_EINVAL; }
     for (int k = 0; k < 16; k++) if (!std::isfinite(T[k])) { ctx->err = std::string(call) + ": " + name + " holds a non-finite value"; return PCR_EINVAL; }
     return PCR_OK;

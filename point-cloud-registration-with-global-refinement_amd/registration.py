@@ -374,31 +374,157 @@ def _check_voxel_size(fn: str, voxel_size):
 class VoxelCovarianceMap:
     """The target of voxelized GICP (Koide et al., ICRA 2021): per occupied cell of ``voxel_down_sample``'s grid the member count, the mean
     point and the mean covariance, behind a cell hash on the device.  Built once from ``target.covariances`` (or, without them, from its
-    normals with ``epsilon`` as the GICP estimator forms them), read-only afterwards, and good for any number of registrations until
-    ``close()``.  Rows are in Morton order of the cell index, the order in which ``voxel_down_sample`` lists its points."""
+    normals with ``epsilon`` as the GICP estimator forms them) and good for any number of registrations until ``close()``.  Rows are in
+    Morton order of the cell index, the order in which ``voxel_down_sample`` lists its points.
+
+    ``VoxelCovarianceMap(target, voxel_size)`` takes the grid from the target's own minimum, so nothing below that minimum can ever be added.
+    A map that will grow is made by ``VoxelCovarianceMap.on_grid(target, voxel_size, grid_min=centered_grid_min(point, voxel_size))``, whose
+    grid has ``point`` in its middle; then ``insert`` adds a scan at a pose, ``merge`` adds another map of the same grid and ``remove_far``
+    drops the cells far from a point (the GRID / MERGE / INSERT / REMOVE_FAR rules of include/pcr_hip.h).  Each of them replaces the rows as a
+    whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call may use the map while one runs."""
 
     _handle = None
 
     def __init__(self, target: PointCloud, voxel_size: float, epsilon: float = 1e-3):
-        self.voxel_size = _check_voxel_size("VoxelCovarianceMap", voxel_size)
+        self._create(target, voxel_size, epsilon, None, None)
+
+    @classmethod
+    def on_grid(cls, target: PointCloud, voxel_size: float, epsilon: float = 1e-3, grid_min=None, transformation=None):
+        """The map of ``target`` placed at ``transformation`` (4x4; ``None``: as it lies) on the grid whose origin is
+        ``grid_min - voxel_size / 2`` (``pcr_voxel_map_create_on_grid``).  With both ``None`` this is
+        ``VoxelCovarianceMap(target, voxel_size, epsilon)``, through the same call and with the same bits; a pose needs a ``grid_min``.  A point outside
+        the grid's 2^21 cells per axis -- below ``grid_min - voxel_size / 2`` too -- raises the library's error."""
+        m = cls.__new__(cls)
+        m._create(target, voxel_size, epsilon, grid_min, transformation)
+        return m
+
+    @staticmethod
+    def centered_grid_min(point, voxel_size) -> np.ndarray:
+        """``floor(point / voxel_size) * voxel_size - 2^20 * voxel_size`` per axis (float64): the ``grid_min`` of a grid with ``point`` in the
+        middle of its 2^21 cells per axis, so the map can grow by 2^20 cells in every direction."""
+        v = _check_voxel_size("VoxelCovarianceMap.centered_grid_min", voxel_size)
+        p = np.asarray(point, np.float64).reshape(-1)
+        if p.shape != (3,) or not np.isfinite(p).all():
+            raise ValueError(f"VoxelCovarianceMap.centered_grid_min: point must be three finite numbers, got {point!r}")
+        return np.floor(p / v) * v - float(1 << 20) * v
+
+    @staticmethod
+    def _cloud_arrays(fn: str, cloud, what: str = "cloud"):
+        """(covariances or None, normals or None) of a cloud that goes into a map: exactly one is given"""
+        if not isinstance(cloud, PointCloud) or len(cloud) == 0:
+            raise RuntimeError(f"{fn}: the {what} must be a PointCloud with at least one point")
+        cov = cloud._cov if cloud.has_covariances() else None
+        nrm = cloud._nrm if cov is None and cloud.has_normals() else None
+        if cov is None and nrm is None:
+            raise RuntimeError(f"{fn}: the {what} has neither covariances nor normals")
+        return cov, nrm
+
+    @staticmethod
+    def _pose(fn: str, transformation):
+        """(array kept alive, pointer) of an optional 4x4 pose; ``None`` is the NULL pointer (the identity)"""
+        if transformation is None:
+            return None, None
+        T = np.asarray(transformation, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError(f"{fn}: transformation must have shape (4, 4), got {T.shape}")
+        return _T(T)
+
+    def _create(self, target, voxel_size, epsilon, grid_min, transformation):
+        fn = "VoxelCovarianceMap"
+        self._voxel_size = _check_voxel_size(fn, voxel_size)
         self.epsilon = float(epsilon)
         if not np.isfinite(self.epsilon):
             raise ValueError(f"VoxelCovarianceMap: epsilon must be finite, got {epsilon!r}")
-        if not isinstance(target, PointCloud) or len(target) == 0:
-            raise RuntimeError("VoxelCovarianceMap: the target must be a PointCloud with at least one point")
-        cov = target._cov if target.has_covariances() else None
-        nrm = target._nrm if cov is None and target.has_normals() else None
-        if cov is None and nrm is None:
-            raise RuntimeError("VoxelCovarianceMap: the target has neither covariances nor normals")
+        cov, nrm = self._cloud_arrays(fn, target, "target")
+        T, Tp = self._pose(fn, transformation)
+        g = None
+        if grid_min is not None:
+            g = np.ascontiguousarray(np.asarray(grid_min, np.float64).reshape(-1))
+            if g.shape != (3,):
+                raise ValueError(f"{fn}: grid_min must hold three numbers, got {grid_min!r}")
+        if g is None and T is not None:
+            raise ValueError(f"{fn}: a transformation needs a grid_min (the placed target's minimum is not known before the call)")
         ctx = _lib.Context.current()
         h = C.c_void_p()
-        ctx.check(ctx.lib.pcr_voxel_map_create(ctx.handle, _ptr(target.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(target)),
-                                               C.c_double(self.voxel_size), C.c_double(self.epsilon), C.byref(h)), "VoxelCovarianceMap")
+        if g is None:
+            ctx.check(ctx.lib.pcr_voxel_map_create(ctx.handle, _ptr(target.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(target)),
+                                                   C.c_double(self._voxel_size), C.c_double(self.epsilon), C.byref(h)), fn)
+        else:
+            ctx.check(ctx.lib.pcr_voxel_map_create_on_grid(ctx.handle, _ptr(target.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(target)),
+                                                           C.c_double(self._voxel_size), C.c_double(self.epsilon), g.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           Tp, C.byref(h)), fn)
         self._handle = h
         self._lib = ctx.lib
+        self._refresh()
+
+    def _refresh(self):
         m = C.c_int64(0)
-        ctx.lib.pcr_voxel_map_size(h, C.byref(m))
+        self._lib.pcr_voxel_map_size(self._handle, C.byref(m))
         self._cells = int(m.value)
+
+    def _grid(self):
+        h = self._open()
+        g, o, v = (C.c_double * 3)(), (C.c_double * 3)(), C.c_double(0)
+        self._lib.pcr_voxel_map_grid(h, g, o, C.byref(v))
+        return np.array(g, np.float64), np.array(o, np.float64), float(v.value)
+
+    @property
+    def voxel_size(self) -> float:
+        return self._voxel_size
+
+    @property
+    def grid_min(self) -> np.ndarray:
+        """(3,) float64: g of the GRID rule; for a map made without ``grid_min`` the target's minimum"""
+        return self._grid()[0]
+
+    @property
+    def origin(self) -> np.ndarray:
+        """(3,) float64: ``grid_min - voxel_size / 2``, the corner of cell (0, 0, 0)"""
+        return self._grid()[1]
+
+    def insert(self, cloud: PointCloud, transformation=np.eye(4)):
+        """Add ``cloud`` placed at ``transformation`` (``pcr_voxel_map_insert``): the map becomes MERGE(map, the map of the placed cloud on this
+        grid).  The cloud carries covariances or normals, as the target of the constructor.  A point outside the grid raises the library's
+        error and leaves the map as it was."""
+        fn = "VoxelCovarianceMap.insert"
+        h = self._open()
+        cov, nrm = self._cloud_arrays(fn, cloud)
+        T, Tp = self._pose(fn, np.eye(4) if transformation is None else transformation)
+        ctx = _lib.Context.current()
+        ctx.check(ctx.lib.pcr_voxel_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(cloud)), C.c_double(self.epsilon), Tp), fn)
+        self._refresh()
+
+    def merge(self, other: "VoxelCovarianceMap"):
+        """Add the cells of ``other``, a map on the same grid (``pcr_voxel_map_merge``); ``other`` is unchanged.  A cell in both gets the sum of
+        the counts and the count-weighted means of the nine channels."""
+        fn = "VoxelCovarianceMap.merge"
+        h = self._open()
+        if not isinstance(other, VoxelCovarianceMap):
+            raise TypeError(f"{fn}: other must be a VoxelCovarianceMap, got {type(other).__name__}")
+        ho = other._open()
+        ctx = _lib.Context.current()
+        ctx.check(ctx.lib.pcr_voxel_map_merge(ctx.handle, h, ho), fn)
+        self._refresh()
+
+    def remove_far(self, center, max_distance) -> int:
+        """Drop every cell whose mean is not closer to ``center`` than ``max_distance`` (``pcr_voxel_map_remove_far``; d^2 < r^2 keeps) and return
+        the number of rows removed.  A call that would keep nothing raises the library's error and leaves the map as it was."""
+        fn = "VoxelCovarianceMap.remove_far"
+        h = self._open()
+        c = np.ascontiguousarray(np.asarray(center, np.float64).reshape(-1))
+        if c.shape != (3,):
+            raise ValueError(f"{fn}: center must hold three numbers, got {center!r}")
+        try:
+            r = float(max_distance)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: max_distance must be a number greater than 0, got {max_distance!r}") from None
+        if not np.isfinite(r) or not (r > 0.0):
+            raise ValueError(f"{fn}: max_distance must be a finite number greater than 0, got {max_distance!r}")
+        ctx = _lib.Context.current()
+        removed = C.c_int64(0)
+        ctx.check(ctx.lib.pcr_voxel_map_remove_far(ctx.handle, h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r), C.byref(removed)), fn)
+        self._refresh()
+        return int(removed.value)
 
     def close(self):
         """Destroy the map (waits for the device)."""
@@ -529,6 +655,60 @@ def registration_voxelized_gicp(source: PointCloud, target_or_map, voxel_size=No
     finally:
         if own is not None:
             own.close()
+
+
+def scan_to_map_odometry(scans, voxel_size, init=np.eye(4), estimation_method=None, criteria=None, neighborhood: int = 1, min_points_per_voxel: int = 1,
+                         motion_model: str = "constant_velocity", max_range=None, grid_min=None):
+    """LiDAR odometry by scan-to-map voxelized GICP -> ``(poses, results, map)``.  Exactly these public calls, in this order (calling them by
+    hand with the same arguments gives the same poses bit for bit):
+
+    * ``map = VoxelCovarianceMap.on_grid(scans[0], voxel_size, estimation.epsilon, grid_min, init)``; ``grid_min=None`` is
+      ``centered_grid_min`` of scan 0's centre (``get_center()``) placed at ``init``; ``poses[0] = init``, ``results[0] = None``;
+    * for every further scan k: ``results[k] = registration_voxelized_gicp(scans[k], map, None, start, estimation_method, criteria, neighborhood,
+      min_points_per_voxel)`` with ``start = P[k-1] @ inv(P[k-2]) @ P[k-1]`` under ``"constant_velocity"`` and ``P[k-1]`` under ``"static"`` (and
+      for scan 1 in either model); ``poses[k]`` is its transformation;
+    * ``map.insert(scans[k], poses[k])``, and with a ``max_range``, ``map.remove_far(poses[k][:3, 3], max_range)``.
+
+    Every scan carries covariances or normals.  A scan that would leave the grid raises the library's error (the map is closed then).  The caller
+    owns the returned map and closes it."""
+    fn = "scan_to_map_odometry"
+    if motion_model not in ("constant_velocity", "static"):
+        raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
+    _check_voxel_size(fn, voxel_size)
+    _check_vgicp_rule(fn, neighborhood, min_points_per_voxel)
+    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
+        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
+    scans = list(scans)
+    if not scans:
+        raise ValueError(f"{fn}: at least one scan is needed")
+    for k, s in enumerate(scans):
+        VoxelCovarianceMap._cloud_arrays(fn, s, f"scan {k}")
+    estimation = TransformationEstimationForGeneralizedICP() if estimation_method is None else estimation_method
+    if not isinstance(estimation, TransformationEstimationForGeneralizedICP):
+        raise RuntimeError(f"{fn}: {type(estimation).__name__} is not TransformationEstimationForGeneralizedICP")
+    P0 = np.array(np.asarray(init, np.float64), np.float64)
+    if P0.shape != (4, 4):
+        raise ValueError(f"{fn}: init must have shape (4, 4), got {P0.shape}")
+    if grid_min is None:
+        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
+        grid_min = VoxelCovarianceMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
+    vmap = VoxelCovarianceMap.on_grid(scans[0], voxel_size, estimation.epsilon, grid_min, P0)
+    poses, results = [P0], [None]
+    try:
+        for k in range(1, len(scans)):
+            start = poses[-1]
+            if motion_model == "constant_velocity" and k >= 2:
+                start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
+            res = registration_voxelized_gicp(scans[k], vmap, None, start, estimation_method, criteria, neighborhood, min_points_per_voxel)
+            poses.append(np.array(res.transformation, np.float64))
+            results.append(res)
+            vmap.insert(scans[k], poses[-1])
+            if max_range is not None:
+                vmap.remove_far(poses[-1][:3, 3], max_range)
+    except BaseException:
+        vmap.close()
+        raise
+    return poses, results, vmap
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
