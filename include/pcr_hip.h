@@ -896,7 +896,8 @@ int pcr_debug_plane_hypotheses(pcr_context *ctx, const float *xyz, int64_t n, do
  * order; 1: always in Morton order), "fps_form" (-1: pcr_farthest_point_sample picks its form by size; 0: one launch per step; 1: the persistent launch), "fps_wgs"
  * (0: the persistent workgroups by size; else that many, at most one per compute unit and 256), "fps_timeout" (ticks of the 100 MHz wall clock
  * a persistent workgroup waits at its barrier before the call falls back to the step form; -1: the default, that of PCR_FGR_MULTI_TIMEOUT;
- * 0 forces the fall-back).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
+ * 0 forces the fall-back), "nfl_form" (the kernel that turns the outlier filter's lists into the normals of the cleaned cloud -- 1, the default:
+ * one point per lane; 0: eight lanes per point in eight rounds, the reference form).  "arena_poison": the scratch arena is filled with this byte before every call (a read of
  * scratch nobody wrote then follows the pattern).  Returns PCR_EINVAL for an unknown name. */
 int pcr_set_option(const char *name, long long value);
 /* Process-wide event counters (value, or -1 for an unknown name; reset != 0 clears it): how often a lockstep registro_FGR group fell back to

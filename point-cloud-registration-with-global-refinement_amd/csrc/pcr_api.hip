@@ -29,6 +29,7 @@ PcrOptions &pcr_options() {
         if (const char *e = getenv("PCR_FPS_FORM")) o.fps_form = atoi(e);
         if (const char *e = getenv("PCR_FPS_WGS")) o.fps_wgs = atoi(e);
         if (const char *e = getenv("PCR_FPS_TIMEOUT")) o.fps_timeout = atoi(e);
+        if (const char *e = getenv("PCR_NFL_FORM")) o.nfl_form = atoi(e);
     });
     return o;
 }
@@ -57,6 +58,7 @@ extern "C" int pcr_set_option(const char *name, long long value) {
     if (!strcmp(name, "fps_form")) { o.fps_form = (int)value; return PCR_OK; }
     if (!strcmp(name, "fps_wgs")) { o.fps_wgs = (int)value; return PCR_OK; }
     if (!strcmp(name, "fps_timeout")) { o.fps_timeout = (int)value; return PCR_OK; }
+    if (!strcmp(name, "nfl_form")) { o.nfl_form = (int)value; return PCR_OK; }
     return PCR_EINVAL;
 }
 

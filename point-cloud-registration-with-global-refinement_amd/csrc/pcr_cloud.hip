@@ -1638,9 +1638,35 @@ struct NflArgs {
     uint8_t *todo; int *todo_count;
     int *piece_list, *piece_count;                   // optional: first point (un-cleaned index) of every 8-point piece that holds a todo point -- the work list of the fallback search
 };
-// A wavefront serves 64 points: octet o takes points base + 8 o + r in rounds r = 0..7 (list filtering, farthest-survivor drops, raw
-// moments: 8 lanes per point as before), lane r of the octet keeps the moments of round r, and after the eighth round ALL 64 lanes
-// run the analytic eigen solver at once -- it is ~2/3 of this kernel's instructions and used to run with one live lane per octet.
+// one kept neighbour's term of the nine raw moments -- ONE helper for both bodies below, so that the compiler forms the same (contracted)
+// operations in both.  (The products of two float32 values are exact in float64, so a fused and an unfused form round alike anyway.)
+__device__ static inline void nfl_add_moments(double (&cu)[9], float px, float py, float pz) {
+    const double x = px, y = py, z = pz;
+    cu[0] += x; cu[1] += y; cu[2] += z;
+    cu[3] += x * x; cu[4] += x * y; cu[5] += x * z; cu[6] += y * y; cu[7] += y * z; cu[8] += z * z;
+}
+// the shared tail: covariance of the raw moments, analytic eigen solver, prior / +z fallback, orientation, store (all 64 lanes at once)
+__device__ static inline void nfl_solve_and_store(const NflArgs &a, double (&my_cu)[9], double my_c, int my_j) {
+    double myC[6] = {1, 0, 0, 1, 0, 1};
+    if (my_c >= 3.0) {                                  // (the nine float64 divisions once per wavefront, not once per round under a one-lane-in-eight branch)
+#pragma unroll
+        for (int t = 0; t < 9; t++) my_cu[t] = my_cu[t] / my_c;
+        myC[0] = my_cu[3] - my_cu[0] * my_cu[0]; myC[1] = my_cu[4] - my_cu[0] * my_cu[1]; myC[2] = my_cu[5] - my_cu[0] * my_cu[2];
+        myC[3] = my_cu[6] - my_cu[1] * my_cu[1]; myC[4] = my_cu[7] - my_cu[1] * my_cu[2]; myC[5] = my_cu[8] - my_cu[2] * my_cu[2];
+    }
+    double nv[3];
+    d_fast_eigen3x3(myC, nv);
+    const double nn = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+    double px = 0, py = 0, pz = 0;
+    if (a.prior) { const float4 pr = a.prior[my_j]; px = pr.x; py = pr.y; pz = pr.z; }
+    if (nn == 0.0 || !(nn == nn)) { if (a.prior) { nv[0] = px; nv[1] = py; nv[2] = pz; } else { nv[0] = 0; nv[1] = 0; nv[2] = 1; } }
+    if (a.prior && nv[0] * px + nv[1] * py + nv[2] * pz < 0.0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
+    a.normals[my_j] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.0f);
+}
+
+// OCTET form (option nfl_form = 0, the reference form of the one below).  A wavefront serves 64 points: octet o takes points base + 8 o + r
+// in rounds r = 0..7 (list filtering, farthest-survivor drops, raw moments: 8 lanes per point), lane r of the octet keeps the moments of
+// round r, and after the eighth round ALL 64 lanes run the analytic eigen solver at once.
 __device__ static inline void d_normals_from_lists(const NflArgs &a) {
     const int n = *a.n_ptr;
     const int ol = threadIdx.x & 7, oct_id = (threadIdx.x & 63) >> 3;
@@ -1690,10 +1716,7 @@ __device__ static inline void d_normals_from_lists(const NflArgs &a) {
 #pragma unroll
         for (int s = 0; s < 4; s++) {
             if (exact && ok[s]) {
-                const float4 p = pn[s];
-                const double x = p.x, y = p.y, z = p.z;
-                cu[0] += x; cu[1] += y; cu[2] += z;
-                cu[3] += x * x; cu[4] += x * y; cu[5] += x * z; cu[6] += y * y; cu[7] += y * z; cu[8] += z * z;
+                nfl_add_moments(cu, pn[s].x, pn[s].y, pn[s].z);
                 c += 1.0;
             }
         }
@@ -1710,24 +1733,183 @@ __device__ static inline void d_normals_from_lists(const NflArgs &a) {
     // per 8 points of the whole cloud to find the ~2 % that hold one (8.9 % of the headline run's kernel time)
     if (a.piece_list && piece_todo && ol == 0) a.piece_list[atomicAdd(a.piece_count, 1)] = base + oct_id * OCT;
     if (!my_exact) return;
-    double myC[6] = {1, 0, 0, 1, 0, 1};
-    if (my_c >= 3.0) {                                  // (the nine float64 divisions once per wavefront, not once per round under a one-lane-in-eight branch)
-#pragma unroll
-        for (int t = 0; t < 9; t++) my_cu[t] = my_cu[t] / my_c;
-        myC[0] = my_cu[3] - my_cu[0] * my_cu[0]; myC[1] = my_cu[4] - my_cu[0] * my_cu[1]; myC[2] = my_cu[5] - my_cu[0] * my_cu[2];
-        myC[3] = my_cu[6] - my_cu[1] * my_cu[1]; myC[4] = my_cu[7] - my_cu[1] * my_cu[2]; myC[5] = my_cu[8] - my_cu[2] * my_cu[2];
-    }
-    double nv[3];
-    d_fast_eigen3x3(myC, nv);
-    const double nn = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-    double px = 0, py = 0, pz = 0;
-    if (a.prior) { const float4 pr = a.prior[my_j]; px = pr.x; py = pr.y; pz = pr.z; }
-    if (nn == 0.0 || !(nn == nn)) { if (a.prior) { nv[0] = px; nv[1] = py; nv[2] = pz; } else { nv[0] = 0; nv[1] = 0; nv[2] = 1; } }
-    if (a.prior && nv[0] * px + nv[1] * py + nv[2] * pz < 0.0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
-    a.normals[my_j] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.0f);
+    nfl_solve_and_store(a, my_cu, my_c, my_j);
 }
 
+// LANE form (nfl_form = 1, the default): lane l of the wavefront owns point base + l from the row to the store -- the same sets, the same
+// summation tree and so the same bits as the octet form, without its cross-lane traffic (per round three DPP steps for each of ten float64
+// sums and a wave-wide arg-max loop that runs as long as the worst of eight octets needs).  Slot r + 8 s of a row is "slot s of lane r" of
+// the octet form; bit 4 r + s of the masks below stands for it, so that ascending bits are the order in which the arg-max rounds take equal
+// distances (ties go to the lowest lane, inside a lane to the first s).
+//   1. row (eight 16-byte loads), keep flags and float32 distances of the listed points; a slot that is empty or filtered out carries -1;
+//   2. todo / todo_count (one atomic per wavefront) / piece_list as in the octet form;
+//   3. the drops: the CH largest survivor distances in a sorted register chain (one v_med3 per link and slot; distances are >= 0 or -1, so
+//      the integer order of their bits is their order), the threshold at the lane's own excess, every survivor above it and the first
+//      `need` survivors AT it in bit order.  CH >= k_list - k_nrm is the caller's business (nfl_lane_chain);
+//   4. moments: P_r = the kept slots r, r + 8, r + 16, r + 24 added to zero in that order, then ((P0 + P1) + (P2 + P3)) + ((P4 + P5) +
+//      (P6 + P7)) = pcr_octet_sum of the octet form (IEEE addition commutes).  A slot that is not kept adds +0 and 0 * 0: no partial sum
+//      is ever -0, so that leaves every bit.  The count is the popcount.  The kept points are gathered a second time (they are hot in
+//      the cache) and the first quad's sums wait in LDS while the second is formed: three partial sets in registers, not four.
+// (gathers as global loads at a uniform base + a 32-bit byte offset: one address register and one shift per gather, not a 64-bit flat address)
+#define NFL_GLOBAL __attribute__((address_space(1)))
+typedef int nfl_int4 __attribute__((ext_vector_type(4)));
+__device__ static inline const NFL_GLOBAL float *nfl_point(const float4 *pts, int id) {
+    return (const NFL_GLOBAL float *)((const NFL_GLOBAL char *)pts + ((unsigned)id << 4));
+}
+template <int CH>
+__device__ static inline void d_normals_from_lists_lane(const NflArgs &a) {
+    __shared__ double quad0_lds[9][KNN_BS];
+    // (volatile: the store and the load of a lane's own cells are not to be forwarded through registers; the LDS address space: ds_ instructions)
+    volatile __attribute__((address_space(3))) double *quad0 = (volatile __attribute__((address_space(3))) double *)&quad0_lds[0][threadIdx.x];
+    const float4 *__restrict__ pts = a.pts; const uint8_t *__restrict__ keep = a.keep;
+    const int k_list = a.k_list, k_nrm = a.k_nrm;
+    const int n = *a.n_ptr;
+    const int lane = threadIdx.x & 63;
+    const int base = (blockIdx.x * (KNN_BS / 64) + (threadIdx.x >> 6)) * 64;
+    if (base >= n) return;
+    const int i = base + lane;
+    const bool act = i < n && keep[i < n ? i : 0] != 0;
+    const int32_t *__restrict__ row = a.lidx + (size_t)(act ? i : 0) * 32;
+    const float4 qp = pts[act ? i : 0];
+    const int klim = act ? k_list : 0;                    // slots of this lane's row that count
+    int d[32];                                            // bits of the float32 distances
+    int lc = -32; unsigned okm = 0;                        // lc: the listed slots = 32 - the empty ones
+    // four slots at a time: their four points and keep flags are gathered TOGETHER (one round trip; the empty asm statements are what makes
+    // the compiler issue the loads of a group first and keep the groups apart: left alone it either gathers all 32 at once and spills, or
+    // waits for every load by itself), while the next 16 bytes of the row are on their way
+    nfl_int4 v4 = ((const NFL_GLOBAL nfl_int4 *)row)[0];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        nfl_int4 nx = ((const NFL_GLOBAL nfl_int4 *)row)[q < 7 ? q + 1 : 7];
+        const int v[4] = {v4.x, v4.y, v4.z, v4.w};
+        int id[4]; float px[4], py[4], pz[4]; unsigned kb[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            id[e] = 4 * q + e < klim ? v[e] : -1;
+            const int idc = max(id[e], 0);
+            const NFL_GLOBAL float *pn = nfl_point(pts, idc);
+            px[e] = pn[0]; py[e] = pn[1]; pz[e] = pn[2];
+            kb[e] = *((const NFL_GLOBAL uint8_t *)keep + (unsigned)idc);      // (both loads unconditional: no branch per slot)
+        }
+        asm volatile("" : "+v"(px[0]), "+v"(py[0]), "+v"(pz[0]), "+v"(kb[0]), "+v"(px[1]), "+v"(py[1]), "+v"(pz[1]), "+v"(kb[1]),
+                          "+v"(px[2]), "+v"(py[2]), "+v"(pz[2]), "+v"(kb[2]), "+v"(px[3]), "+v"(py[3]), "+v"(pz[3]), "+v"(kb[3]),
+                          "+v"(nx.x), "+v"(nx.y), "+v"(nx.z), "+v"(nx.w));
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int slot = 4 * q + e, bit = 4 * (slot & 7) + (slot >> 3);
+            const float dd = pcr_d2(px[e] - qp.x, py[e] - qp.y, pz[e] - qp.z);    // the search's own float32 distance
+            const unsigned ok = (unsigned)min((int)kb[e], 1) & ~(unsigned)(id[e] >> 31);
+            d[slot] = ok ? __float_as_int(dd) : __float_as_int(-1.0f);
+            lc -= id[e] >> 31; okm |= ok << bit;
+        }
+        // (formed HERE: sunk into the drop branch below, the distances would keep 32 points alive, the counts 32 ids and 32 lane masks)
+        asm volatile("" : "+v"(d[4 * q]), "+v"(d[4 * q + 1]), "+v"(d[4 * q + 2]), "+v"(d[4 * q + 3]), "+v"(okm), "+v"(lc));
+        v4 = nx;
+    }
+    const int vc = __popc(okm);
+    const bool exact = act && (vc >= k_nrm || -lc < k_list);
+    const int j = act ? a.pos[i] : 0;
+    if (act) a.todo[j] = exact ? 0 : 1;
+    const unsigned long long tb = __ballot(act && !exact);
+    if (tb != 0ull && lane == 0) atomicAdd(a.todo_count, __popcll(tb));
+    // the fallback search serves exactly the listed pieces (see the octet form): piece [base + 8 o, + 8) once, by its first lane
+    if (a.piece_list && (lane & 7) == 0 && ((tb >> lane) & 0xffull) != 0ull) a.piece_list[atomicAdd(a.piece_count, 1)] = base + lane;
+    const int excess = exact ? vc - k_nrm : 0;
+    unsigned dropm = 0;
+    if (__ballot(excess > 0) != 0ull) {
+        int ch[CH];                                       // descending: ch[0] the largest
+#pragma unroll
+        for (int t = 0; t < CH; t++) ch[t] = __float_as_int(-1.0f);
+#pragma unroll
+        for (int s = 0; s < 32; s++) {
+#pragma unroll
+            for (int t = CH - 1; t >= 1; t--) ch[t] = max(min(ch[t - 1], ch[t]), min(max(ch[t - 1], ch[t]), d[s]));      // v_med3_i32
+            ch[0] = max(ch[0], d[s]);
+        }
+        int thr = ch[0];
+#pragma unroll
+        for (int t = 1; t < CH; t++) thr = excess > t ? ch[t] : thr;
+        thr = excess > 0 ? thr : 0x7fffffff;              // (nothing is above or at it)
+        unsigned gtm = 0, eqm = 0;
+#pragma unroll
+        for (int s = 0; s < 32; s++) {
+            const int bit = 4 * (s & 7) + (s >> 3);
+            gtm |= (d[s] > thr ? 1u : 0u) << bit; eqm |= (d[s] == thr ? 1u : 0u) << bit;
+            if ((s & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+        int need = excess > 0 ? excess - __popc(gtm) : 0;
+        unsigned eq_kept = eqm;
+        while (__ballot(need > 0) != 0ull) {              // (one turn unless distances tie at the threshold)
+            if (need > 0) { eq_kept &= eq_kept - 1u; need--; }
+        }
+        dropm = gtm | (eqm & ~eq_kept);
+    }
+    const unsigned keptm = exact ? okm & ~dropm : 0u;
+    const NFL_GLOBAL int32_t *row2 = (const NFL_GLOBAL int32_t *)row;                           // the ids are read AGAIN (one cache line): carried over from the first pass they would
+    asm volatile("" : "+v"(row2));                        // hold 32 registers through the drops
+    // (a real loop: unrolled, the compiler gathers far ahead of the sums and spills the points)
+    double pair[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, lone[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 1
+    for (int r = 0; r < OCT; r++) {
+        double P[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const int kr = (int)(keptm >> (4 * r));
+        int id4[4]; float px[4], py[4], pz[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) id4[s] = row2[r + OCT * s];
+        asm volatile("" : "+v"(id4[0]), "+v"(id4[1]), "+v"(id4[2]), "+v"(id4[3]));
+#pragma unroll
+        for (int s = 0; s < 4; s++) {                      // the four points of this round together
+            const NFL_GLOBAL float *pn = nfl_point(pts, id4[s] & __builtin_amdgcn_sbfe(kr, s, 1));      // (all ones: kept)
+            px[s] = pn[0]; py[s] = pn[1]; pz[s] = pn[2];
+        }
+        asm volatile("" : "+v"(px[0]), "+v"(py[0]), "+v"(pz[0]), "+v"(px[1]), "+v"(py[1]), "+v"(pz[1]),
+                          "+v"(px[2]), "+v"(py[2]), "+v"(pz[2]), "+v"(px[3]), "+v"(py[3]), "+v"(pz[3]));
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            int m = kr;
+            asm volatile("" : "+v"(m));                    // (the mask again, not four of them kept across the gathers)
+            m = __builtin_amdgcn_sbfe(m, s, 1);
+            nfl_add_moments(P, __int_as_float(__float_as_int(px[s]) & m), __int_as_float(__float_as_int(py[s]) & m), __int_as_float(__float_as_int(pz[s]) & m));
+        }
+        if ((r & 1) == 0) {
+#pragma unroll
+            for (int t = 0; t < 9; t++) lone[t] = P[t];
+        } else if ((r & 2) == 0) {
+#pragma unroll
+            for (int t = 0; t < 9; t++) pair[t] = lone[t] + P[t];                // P(r-1) + P(r)
+        } else {
+#pragma unroll
+            for (int t = 0; t < 9; t++) pair[t] = pair[t] + (lone[t] + P[t]);    // (P(r-3) + P(r-2)) + (P(r-1) + P(r))
+            if (r == 3) {
+#pragma unroll
+                for (int t = 0; t < 9; t++) quad0[t * KNN_BS] = pair[t];
+            }
+        }
+    }
+    double my_cu[9];
+#pragma unroll
+    for (int t = 0; t < 9; t++) my_cu[t] = quad0[t * KNN_BS] + pair[t];
+    if (!exact) return;
+    int my_j = j;
+    asm volatile("" : "+v"(my_j));                        // (one register through the loop: widened before it, the index takes two)
+    nfl_solve_and_store(a, my_cu, (double)__popc(keptm), my_j);
+}
+// (the chain length is an instance, not a loop bound: 10 serves the product's 30 / 20 and every k_list - k_nrm below it, 31 the rest)
+static int nfl_lane_chain(int k_list, int k_nrm) { return k_list - k_nrm <= 10 ? 10 : 31; }
+
 struct OpNormalsFromLists : PcrOp<NflArgs, KNN_BS> { __device__ static inline void run(const NflArgs &a) { d_normals_from_lists(a); } };
+template <int CH> struct OpNormalsFromListsLane : PcrOp<NflArgs, KNN_BS> {
+    static constexpr int kWavesMin = 6, kWavesMax = 8;        // the octet form's occupancy: the gathers are latency, and the scheduler would spend 160 registers on them
+    __device__ static inline void run(const NflArgs &a) { [[clang::always_inline]] d_normals_from_lists_lane<CH>(a); }
+};
+// the instance the option and the list lengths ask for (chosen here, on the host: a union of both forms in one kernel pays in registers)
+static int launch_normals_from_lists(pcr_context *ctx, const NflArgs *args, int count, dim3 grid) {
+    if (pcr_options().nfl_form.load(std::memory_order_relaxed) == 0) return PCR_BATCH_LAUNCH(ctx, OpNormalsFromLists, args, count, grid);
+    int chain = 10;
+    for (int k = 0; k < count; k++) if (args[k].pts && nfl_lane_chain(args[k].k_list, args[k].k_nrm) > chain) chain = 31;
+    if (chain == 10) return PCR_BATCH_LAUNCH(ctx, OpNormalsFromListsLane<10>, args, count, grid);
+    return PCR_BATCH_LAUNCH(ctx, OpNormalsFromListsLane<31>, args, count, grid);
+}
 
 // ============================================================================ SOR (K4)
 // mean / Bessel std of the per-point mean neighbour distance in ONE pass over <= 128 workgroups: shifted moments
@@ -1884,8 +2066,8 @@ static int sor_batch(pcr_context *ctx, SorProblem *pr, int count, int nb_neighbo
     PCR_TRY(flag_scan_batch(ctx, cb, m));
     PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpCompactCloud, mb, m, dim3((mc + BS - 1) / BS, m)));
     if (any_todo) {
-        if (fuse_all) PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpNormalsFromLists, nb_, m, dim3((unsigned)(((size_t)mc + KNN_BS - 1) / KNN_BS), m)));
-        else for (int k = 0; k < m; k++) if (nb_[k].pts) PCR_TRY(PCR_BATCH_LAUNCH(ctx, OpNormalsFromLists, nb_ + k, 1, dim3((unsigned)(((size_t)caps[k] + KNN_BS - 1) / KNN_BS))));
+        if (fuse_all) PCR_TRY(launch_normals_from_lists(ctx, nb_, m, dim3((unsigned)(((size_t)mc + KNN_BS - 1) / KNN_BS), m)));
+        else for (int k = 0; k < m; k++) if (nb_[k].pts) PCR_TRY(launch_normals_from_lists(ctx, nb_ + k, 1, dim3((unsigned)(((size_t)caps[k] + KNN_BS - 1) / KNN_BS))));
         if (fallback_here && normal_k > 0) {
             bool listed = fuse_all && piece_counts != nullptr;
             for (int k = 0; k < m; k++) listed = listed && fb[k].hard_list != nullptr;
