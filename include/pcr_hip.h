@@ -807,6 +807,63 @@ int pcr_normalize_normals(pcr_context *ctx, float *normals, int64_t n);
 int pcr_boundary_points(pcr_context *ctx, const float *xyz, const float *normals, int64_t n, double radius, int max_nn, double angle_threshold,
                         uint8_t *boundary_mask, float *out_xyz, int64_t *out_index, int64_t *out_n, double *max_gap, int32_t *counts);
 
+/* == Scan Context place recognition (Kim and Kim, "Scan Context: egocentric spatial descriptor for place recognition within 3D point cloud
+ *    map", IROS 2018; the reference calls nothing like it): a polar height image of a ring-LiDAR scan, and the distance of two images that
+ *    tells whether two scans were taken at the same place, whatever the heading.  The rule is stated here and this statement is the
+ *    specification; tests/scan_context_reference.py restates it in numpy and the device gives its rows bit for bit, the same bits every run.
+ *    PARAMETERS.  num_rings R in 1..64 (default 20), num_sectors S in 4..128 and a multiple of 4 (default 60), max_range L > 0 (default 80.0),
+ *    height_offset h finite (default 2.0: the sensor's height, so that the ground is near 0).
+ *    TABLES.  No transcendental function evaluated on the device decides a bin (atan2 and sqrt of different libms differ in the last bit, and a
+ *    bin boundary would turn that into another descriptor).  The host passes, in float64: ring_bound2[k - 1] = ((double)k * L / R)^2 for
+ *    k = 1..R-1; cos_k[k - 1] = cos(2 pi k / S) and sin_k[k - 1] = sin(2 pi k / S) for k = 1..S/4-1; range2 = L * L.
+ *    DESCRIPTOR of a cloud of float32 points in the sensor's frame, z up:
+ *    1. A row with a non-finite coordinate is dropped.
+ *    2. With x, y widened to float64, rho2 = x * x + y * y (the products are exact, the sum is rounded once).  The row is dropped when
+ *       rho2 >= range2 or rho2 == 0.
+ *    3. ring = the number of k with rho2 >= ring_bound2[k - 1].
+ *    4. The quadrant q is 0 for x > 0, y >= 0; 1 for x <= 0, y > 0; 2 for x < 0, y <= 0; 3 for x >= 0, y < 0.  (u, v) = (x, y), (y, -x),
+ *       (-x, -y), (-y, x) for q = 0, 1, 2, 3, so u > 0 and v >= 0.
+ *    5. within = the number of k in 1..S/4-1 with v * cos_k >= u * sin_k, each product rounded once in float64, nothing contracted.
+ *       sector = q * S / 4 + within.
+ *    6. The value of the row is (float)z + (float)h in float32.  The cell (ring, sector) holds the maximum value of its rows; a maximum of
+ *       -0.0 is stored as +0.0; a cell without rows holds 0.  The descriptor is (R, S) float32, row-major.
+ *    7. The info record counts the rows used, dropped as non-finite (rule 1) and dropped by range (rule 2).
+ *    DISTANCE of descriptor A (the query) and descriptor B (the candidate), both widened to float64:
+ *    1. nA[j] = the sum over r = 0..R-1, in that order, of A[r,j]^2; nB[j] likewise.  G[j,j'] = the sum over r, in that order, of
+ *       A[r,j] * B[r,j'].  No multiply-add is contracted.
+ *    2. A column pair (j, j') is valid when nA[j] > 0 and nB[j'] > 0; then C[j,j'] = G[j,j'] / (sqrt(nA[j]) * sqrt(nB[j'])).
+ *    3. For the shift n in 0..S-1, with j' = (j - n) mod S (column j of B rolled right by n): m_n = the number of valid pairs (j, j'),
+ *       d_n = 1 - (the sum over j ascending of the valid C[j,j']) / m_n, and d_n = 1 when m_n = 0.
+ *    4. The distance is the smallest d_n, the shift the smallest n that attains it.
+ *    MEANING OF THE SHIFT.  Turning B's cloud by +2 pi n / S about z lines it up with A's: Rz(2 pi n / S) is the initial pose of a
+ *    registration with B's cloud as source and A's cloud as target.
+ *    ARITHMETIC.  sqrt and the division of float64 are correctly rounded on gfx950 under this library's flags (measured against numpy on
+ *    2^21 operands each), so the rule stands as the method's authors wrote it.  Descriptors with non-finite entries are outside
+ *    the rule (their cosines are not numbers; the kernel marks a pair that is not valid with a NaN of its own).
+ *    ERRORS.  PCR_EINVAL with a message naming scan_context / scan_context_distance: null params, tables, output or (with rows) input
+ *    pointers; R or S out of range, S not a multiple of 4; max_range or range2 not finite or <= 0; height_offset not finite (as float32);
+ *    a missing table that the shape needs, or ring bounds that are not positive and ascending; a negative row count, or one over the int range.
+ * pcr_scan_context: xyz device, n x 3 float32; params, tables (and the arrays they name) host; out_desc device, R x S float32; out_info
+ * optional, host (the call waits for the counts when it is given).  n == 0 gives the all-zero descriptor.  pcr_scan_context_distance: descA
+ * (nA x R x S) and descB (nB x R x S) device float32; out_dist device, nA x nB float64, out_shift device, nA x nB int32, row-major.  nA == 0
+ * or nB == 0 returns PCR_OK and writes nothing.  Both run asynchronously on the context's stream. */
+typedef struct {
+    int32_t num_rings, num_sectors;
+    double max_range, height_offset;
+} pcr_scan_context_params;
+typedef struct {
+    const double *ring_bound2;        /* R - 1 entries (may be null for R == 1) */
+    const double *cos_k, *sin_k;      /* S / 4 - 1 entries each (may be null for S == 4) */
+    double range2;
+} pcr_scan_context_tables;
+typedef struct {
+    int64_t used, dropped_nonfinite, dropped_range;
+} pcr_scan_context_info;
+int pcr_scan_context(pcr_context *ctx, const float *xyz, int64_t n, const pcr_scan_context_params *params, const pcr_scan_context_tables *tables,
+                     float *out_desc, pcr_scan_context_info *out_info);
+int pcr_scan_context_distance(pcr_context *ctx, const float *descA, int64_t nA, const float *descB, int64_t nB, int R, int S, double *out_dist,
+                              int32_t *out_shift);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

@@ -82,6 +82,18 @@ class PcrOrientInfo(C.Structure):
     _fields_ = [("emst_rounds", C.c_int32), ("tree_rounds", C.c_int32), ("walked_rows", C.c_int64), ("n_flipped", C.c_int64), ("root", C.c_int64)]
 
 
+class PcrScanContextParams(C.Structure):
+    _fields_ = [("num_rings", C.c_int32), ("num_sectors", C.c_int32), ("max_range", C.c_double), ("height_offset", C.c_double)]
+
+
+class PcrScanContextTables(C.Structure):
+    _fields_ = [("ring_bound2", C.POINTER(C.c_double)), ("cos_k", C.POINTER(C.c_double)), ("sin_k", C.POINTER(C.c_double)), ("range2", C.c_double)]
+
+
+class PcrScanContextInfo(C.Structure):
+    _fields_ = [("used", C.c_int64), ("dropped_nonfinite", C.c_int64), ("dropped_range", C.c_int64)]
+
+
 class PcrScaleRecord(C.Structure):
     _fields_ = [("n_voxel", C.c_int64 * 2), ("n_clean", C.c_int64 * 2), ("icp", PcrResult)]
 
@@ -140,6 +152,7 @@ EXPORTS = [
     "pcr_voxel_map_create", "pcr_voxel_map_destroy", "pcr_voxel_map_size", "pcr_voxel_map_read", "pcr_voxel_map_correspondences",
     "pcr_registration_voxelized_gicp",
     "pcr_voxel_map_create_on_grid", "pcr_voxel_map_insert", "pcr_voxel_map_merge", "pcr_voxel_map_remove_far", "pcr_voxel_map_grid",
+    "pcr_scan_context", "pcr_scan_context_distance",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list and the boundary detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -191,6 +204,9 @@ QUERY_PROTOTYPES = {
     "pcr_voxel_map_merge": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_voxel_map_remove_far": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)], C.c_int),
     "pcr_voxel_map_grid": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+    "pcr_scan_context": ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PcrScanContextParams), C.POINTER(PcrScanContextTables), C.c_void_p,
+                          C.POINTER(PcrScanContextInfo)], C.c_int),
+    "pcr_scan_context_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

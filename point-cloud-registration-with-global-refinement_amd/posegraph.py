@@ -275,3 +275,55 @@ def full_registration(lista_nuvens, voxel_size, k, verbose=False) -> PoseGraph:
     g.successes = ok
     g.attempted = len(g.edges)
     return g
+
+
+# ------------------------------------------------------------------------- from an odometry chain and detected loop closures
+def loop_closure_edges(clouds, closures, voxel_size, num_sectors=60, register_fn=None, information_fn=None, min_fitness=None):
+    """One `uncertain` edge per row `(i, j, shift)` of `closures` (what `place.ScanContextDatabase.detect_loop_closures` returns: scan i
+    came back to the place of the earlier scan j, and turning scan j by `shift` sectors about z lines it up with scan i).  The earlier scan
+    is the source, as in `full_registration`: the edge is `PoseGraphEdge(j, i, T, info, uncertain=True)` with
+    `T = register_fn(clouds[j], clouds[i], init).transformation` and `init = place.shift_to_transformation(shift, num_sectors)`.
+    `register_fn(source, target, init)` returns a `RegistrationResult`; by default it is `Multiscale_GICP(source, target, 3, 100, init)`,
+    the refinement `Coarse_to_fine_FGR_M_GICP` runs after its FGR (the Scan Context shift takes the place of the FGR).
+    `information_fn(source, target, voxel_size, T)` is `get_information_matrix_from_point_clouds` by default.  With `min_fitness`, a closure
+    whose registration ends with a fitness below it gives no edge."""
+    from .place import shift_to_transformation
+    if register_fn is None:
+        from .functions import Multiscale_GICP
+        register_fn = lambda source, target, init: Multiscale_GICP(source, target, 3, 100, init)
+    if information_fn is None:
+        from .registration import get_information_matrix_from_point_clouds as information_fn
+    rows = np.asarray(closures, dtype=np.int64).reshape(-1, 3)
+    n = len(clouds)
+    edges = []
+    for i, j, shift in rows:
+        i, j = int(i), int(j)
+        if not (0 <= i < n and 0 <= j < n) or i == j:
+            raise ValueError(f"loop_closure_edges: closure ({i}, {j}) does not name two different clouds of the {n} given")
+        res = register_fn(clouds[j], clouds[i], shift_to_transformation(int(shift), num_sectors))
+        if min_fitness is not None and res.fitness < min_fitness:
+            continue
+        T = np.array(res.transformation, dtype=np.float64).reshape(4, 4)
+        edges.append(PoseGraphEdge(j, i, T, information_fn(clouds[j], clouds[i], voxel_size, T), uncertain=True))
+    return edges
+
+
+def pose_graph_from_odometry(clouds, poses, closures=(), voxel_size=0.1, num_sectors=60, register_fn=None, information_fn=None, min_fitness=None) -> PoseGraph:
+    """The graph `global_optimization` takes after `scan_to_map_odometry`: node i has the pose `poses[i]` (scan i in the map's frame); the
+    certain edge i -> i+1 carries `X = inv(poses[i+1]) @ poses[i]` -- scan i in the frame of scan i+1, so that the chain as it stands has
+    residual zero -- with the information matrix of (cloud i, cloud i+1) at X; the edges of `loop_closure_edges(clouds, closures, ...)`
+    are appended."""
+    if information_fn is None:
+        from .registration import get_information_matrix_from_point_clouds as information_fn
+    n = len(clouds)
+    if len(poses) != n:
+        raise ValueError(f"pose_graph_from_odometry: {n} clouds but {len(poses)} poses")
+    P = [np.array(T, dtype=np.float64).reshape(4, 4) for T in poses]
+    g = PoseGraph()
+    for T in P:
+        g.nodes.append(PoseGraphNode(T))
+    for i in range(n - 1):
+        X = np.linalg.inv(P[i + 1]) @ P[i]
+        g.edges.append(PoseGraphEdge(i, i + 1, X, information_fn(clouds[i], clouds[i + 1], voxel_size, X), uncertain=False))
+    g.edges.extend(loop_closure_edges(clouds, closures, voxel_size, num_sectors, register_fn, information_fn, min_fitness))
+    return g
