@@ -518,7 +518,13 @@ int pcr_evaluate_registration(pcr_context *ctx, const float *src_xyz, int64_t n_
 int pcr_information_matrix(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt,
                            double max_correspondence_distance, const double *T, double *info36);
 
-/* == compute_fpfh_feature (ALL_FUNCTIONS.py:186-187); feat33: n x 33 float32 (device) */
+/* == compute_fpfh_feature (ALL_FUNCTIONS.py:186-187); feat33: n x 33 float32 (device)
+ * Normals are used AS GIVEN, not normalised (Open3D does not normalise them either): with a normal longer than 1 a pair's
+ * |n . dp| / |dp| can exceed 1, acos of it is NaN and the pair keeps the frame of its first point, as in Open3D.
+ * Coincident points: a pair at distance 0 votes in the bins of f = 0 (bin 5 of each histogram) and has no weight in the sum.
+ * A point with more than k coincident copies (KNN(k), or Hybrid(r, k)) lists k of them, itself among them or not; either way
+ * all its pairs are at distance 0 and its row is 100 in bins 5, 16 and 27, which is also Open3D's row (k >= 2; k = 1 lists
+ * nothing: a zero row).  tests/test_gpu_fpfh_rows.py */
 int pcr_compute_fpfh_feature(pcr_context *ctx, const float *xyz, const float *normals, int64_t n, int search_kind,
                              int knn, double radius, float *feat33);
 

@@ -67,6 +67,14 @@ __device__ static inline bool pair_bins_fast(const float4 p1, const float4 n1, c
     const float il = __builtin_amdgcn_rsqf(l2);
     const float a1 = (n1.x * dx + n1.y * dy + n1.z * dz) * il, a2 = (n2.x * dx + n2.y * dy + n2.z * dz) * il;
     const float fa1 = fabsf(a1), fa2 = fabsf(a2);
+    // Normals are used as given (Open3D does not normalise them, pcr_import_cloud neither).  A normal longer than 1 can give |angle| > 1: acos is
+    // NaN in pair_bins, its comparison false and the frame stays, whatever fa1 < fa2 says below -- so such a pair is not for float, nor one
+    // whose float |angle| could be on the other side of 1: the error of a1 is below 10 * 2^-24 |n| (dp, three products, two sums, l2, the rsq), 7e-7
+    // for the |n| <= 1.1 admitted here (longer normals: the error bounds of this function's margins, stated for unit normals, would not hold either;
+    // nearly all of their pairs have an |angle| > 1 anyway).  Unit normals: a frame normal passes vn2 * il * il > 0.01 below only with
+    // |angle| < 0.995, and it is the normal of the LARGER |angle|, so these two tests decline no pair that was answered before.
+    if (!(n1.x * n1.x + n1.y * n1.y + n1.z * n1.z <= 1.21f) || !(n2.x * n2.x + n2.y * n2.y + n2.z * n2.z <= 1.21f)) return false;
+    if (!(fa1 < 1.0f - 1e-5f) || !(fa2 < 1.0f - 1e-5f)) return false;
     // (equal normals -- the (0, 0, 1) of points without a neighbourhood, by the hundred on sparse scans: the float64 angles are the same
     // expression of the same operands, equal, and the frame stays with the first point)
     const bool same = n1.x == n2.x && n1.y == n2.y && n1.z == n2.z;

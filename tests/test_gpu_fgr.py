@@ -30,6 +30,15 @@ def test_fpfh_matches_oracle(P, oracle, fgr_inputs):
         assert_fpfh_explained(feat.data.T, ref)
 
 
+def test_fpfh_knn_matches_oracle(P, oracle, fgr_inputs):
+    """KDTreeSearchParamKNN takes another list kernel than Hybrid.  Open3D's KNN(100) is the 100 nearest with the point itself, of which FPFH skips
+    the first: 99 neighbours.  The device drops the point itself from its 100-list: the same 99."""
+    for pc, _ in fgr_inputs:
+        feat = P.registration.compute_fpfh_feature(pc, P.KDTreeSearchParamKNN(100))
+        ref = oracle.compute_fpfh(pc.points, pc.normals, oracle.SEARCH_KNN, 100, 0.0)
+        assert_fpfh_explained(feat.data.T, ref, "FPFH KNN(100)")
+
+
 def test_fpfh_float_filter_gives_the_float64_histograms(P, fgr_inputs):
     """The SPFH pass decides a pair's three bins in float where float can (pair_bins_fast: margins to the bin edges, conditioning guards) and queues
     the other pairs for a float64 pass; option "spfh_float64" = 1 evaluates every pair in float64.  Same histograms -> the same feature bits."""
