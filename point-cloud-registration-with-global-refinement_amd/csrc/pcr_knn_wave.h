@@ -24,22 +24,66 @@
 // to the leaves of 6-16 points saved a third of the candidates but cost ~45 dependent node loads per pass: the kernel sat in load
 // latency.)  Pass 2 does not walk at all when the candidates that beat some bound in pass 1 fit a log in LDS (they are a superset of
 // every lane's k-best): it replays the log.  Results are exact (ties aside), as before: tests/test_gpu_stages.py::
-// test_knn_index_is_exact, test_knn_wave_equals_octet, test_sor_mask_is_exact.
+// test_knn_index_is_exact, test_knn_wave_equals_octet, test_sor_mask_is_exact; tests/test_gpu_knn_wave_trim.py (ties with the bound,
+// zero distances, short lists under a cap, batch tails, log overflow).
+//
+// VALU instructions of the <SOR, 30> instance, from its listing (a wavefront of the benchmark's clouds scans 681 candidates in 175
+// steps of four and logs 327 events in pass 1; profiles/knn_wave_trim.md):
+//   * pass 1, per candidate: 7 (three v_sub, v_mul, two v_fmac, v_cmp) + 1/4 (the LDS address of a step's four 16-B reads);
+//   * pass 1, per event: 32 (the chain: v_min_i32, v_max_i32, 28 v_med3_f32, v_min_i32; and the LDS address of the log slot -- the
+//     event counter itself is a scalar register);
+//   * pass 2, per replayed candidate that some lane takes: 7 + 4 when no lane ties with its bound (the compare with the bound, the
+//     compare for the tie, the advance of the lane's write pointer and its copy);
+//   * the walk's state (pending ranges, batch fill, level, child list, masks, ancestor) is scalar, 122 VGPRs and no scratch: every
+//     branch of the walk is wave-uniform, and the one value that did not look so to the compiler (`contained`) is read first-lane.
 #pragma once
 
 #define KW_BS 128                       // 2 wavefronts per workgroup (LDS: ~6 KB per wavefront at K <= 32, ~9 KB above)
 
-// candidate batch in LDS, structure of arrays: a step of 4 candidates is three wave-uniform 16-B reads (and their register pairs could
+// candidate batch in LDS, structure of arrays: a step of 4 candidates is four wave-uniform 16-B reads (and their register pairs could
 // feed packed float32 math, see PK below)
-#ifndef KW_STEP
-#define KW_STEP 4          // candidates per scan step (read back from LDS with a wave-uniform address); 2: diagnostic variant
-#endif
 struct KwStage { float x[68], y[68], z[68]; int i[68]; };          // 64 + one step of read-ahead
 typedef float kw_f2 __attribute__((ext_vector_type(2)));
 // squared distances of two staged candidates to the lane's query, same operation order as pcr_d2 (bit-identical values)
 __device__ static inline kw_f2 kw_d2x2(kw_f2 px, kw_f2 py, kw_f2 pz, kw_f2 qx, kw_f2 qy, kw_f2 qz) {
     const kw_f2 dx = px - qx, dy = py - qy, dz = pz - qz;
     return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+}
+// The scan of one staged batch: use(d2, index) for the candidates [0, nb rounded up to 4) in order, nb >= 1 (slots beyond nb hold
+// infinity).  The LDS reads of a step are in flight while the step before it is worked on (indices included: fetching one at the moment
+// it is needed drained the read-ahead).  Two register sets take the reads in turn -- the loop is unrolled by two steps -- so nothing is
+// copied at the loop tail (one set that is handed on cost 9 v_mov per step).  The read-ahead of the second half is issued only when
+// candidates remain, so the reads end at slot 67.
+struct KwStep { float4 X, Y, Z; int4 I; };
+template <bool PK, class UseFn>
+__device__ static inline void kw_scan(const KwStage &st, int nb, float qx, float qy, float qz, UseFn use) {
+    auto load = [&](int j) -> KwStep {
+        KwStep s;
+        s.X = *(const float4 *)&st.x[j]; s.Y = *(const float4 *)&st.y[j]; s.Z = *(const float4 *)&st.z[j]; s.I = *(const int4 *)&st.i[j];
+        return s;
+    };
+    auto work = [&](const KwStep &s) {
+        float d4[4];
+        if (PK) {
+            const kw_f2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
+            const kw_f2 da = kw_d2x2(kw_f2{s.X.x, s.X.y}, kw_f2{s.Y.x, s.Y.y}, kw_f2{s.Z.x, s.Z.y}, qx2, qy2, qz2);
+            const kw_f2 db = kw_d2x2(kw_f2{s.X.z, s.X.w}, kw_f2{s.Y.z, s.Y.w}, kw_f2{s.Z.z, s.Z.w}, qx2, qy2, qz2);
+            d4[0] = da.x; d4[1] = da.y; d4[2] = db.x; d4[3] = db.y;
+        } else {
+            d4[0] = pcr_d2(s.X.x - qx, s.Y.x - qy, s.Z.x - qz); d4[1] = pcr_d2(s.X.y - qx, s.Y.y - qy, s.Z.y - qz);
+            d4[2] = pcr_d2(s.X.z - qx, s.Y.z - qy, s.Z.z - qz); d4[3] = pcr_d2(s.X.w - qx, s.Y.w - qy, s.Z.w - qz);
+        }
+        use(d4[0], s.I.x); use(d4[1], s.I.y); use(d4[2], s.I.z); use(d4[3], s.I.w);
+    };
+    KwStep A = load(0);
+    for (int j = 0;; j += 8) {
+        const KwStep B = load(j + 4);
+        work(A);
+        if (j + 4 >= nb) break;
+        A = load(j + 8);
+        work(B);
+        if (j + 8 >= nb) break;
+    }
 }
 
 struct KwStack {                        // per wavefront (LDS)
@@ -52,7 +96,7 @@ struct KwStack {                        // per wavefront (LDS)
 };
 template <int K>
 struct KwShared {
-    static constexpr int LOG = K <= 32 ? 768 : 1536;   // pass-1 log capacity (events per wavefront at k = 30: mean 260, p99 580)
+    static constexpr int LOG = K <= 32 ? 768 : 1536;   // pass-1 log capacity (events per wavefront at k = 30 on the benchmark's clouds: mean 327, 2 % above 768)
     KwStage stage;                      // candidate batch
     int log[LOG];                       // indices of the candidates that beat the bound of some lane in pass 1
     KwStack stk;
@@ -148,7 +192,9 @@ __device__ static inline bool kw_pass(const OctView &t, const OctMeta &m, KwStac
         return __builtin_ctz((unsigned)(__ballot(g == k) & 0xffull));
     };
     auto contained = [&](int lvl, uint32_t ix, uint32_t iy, uint32_t iz) -> bool {
-        const float wmax = kw_wave_fmax(worst());
+        // (the maximum is the same in every lane, but only a readfirstlane tells the compiler so: a branch on the bare value counts as
+        // divergent, and with it the walk's whole state -- r0f, r0c, nb, li, cs, mask, anc, the caller's event counter -- moves to VGPRs)
+        const float wmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(kw_wave_fmax(worst()))));
         if (!(wmax < 3.0e38f)) return false;
         const float r = sqrtf(fmaxf(wmax, 0.0f)) * 1.00001f;
         const float w = (float)(1u << lvl);
@@ -300,8 +346,7 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
         plo = __builtin_amdgcn_readfirstlane(pa.y); phi = __builtin_amdgcn_readfirstlane(pb.y + pb.z - 1); start_node = __builtin_amdgcn_readfirstlane(pa.x);
     }
     // pass 1: distances only; every candidate that beats the bound of some lane is logged for pass 2
-    int nlog = 0;
-    const kw_f2 qx2 = {q.x, q.x}, qy2 = {q.y, q.y}, qz2 = {q.z, q.z};
+    int nlog = 0;                                               // wave-uniform: a scalar register (the log slot's LDS address is all the VALU sees of it)
     // x replaces the largest entry when it is smaller, else the chain leaves the list as it is; entries are >= 0 or -1, so they order like
     // their bit patterns (integer min / max: no NaN canonicalisation).  (A lambda of its own since round 5: written out inside the four-way
     // unrolled step the same chain cost the 30-NN instance 12 spilled VGPRs, so 3.)
@@ -319,44 +364,13 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
         }
     };
     auto scan1 = [&](int nb) {
-#if KW_STEP == 2         // two candidates per step: 16 VGPRs of read-ahead instead of 32
-        float2 nX = *(const float2 *)&sh.stage.x[0], nY = *(const float2 *)&sh.stage.y[0], nZ = *(const float2 *)&sh.stage.z[0];
-        int2 nI = *(const int2 *)&sh.stage.i[0];
-        for (int j4 = 0; j4 < nb; j4 += 2) {
-            const float2 X = nX, Y = nY, Z = nZ;
-            const int i4[2] = {nI.x, nI.y};
-            nX = *(const float2 *)&sh.stage.x[j4 + 2]; nY = *(const float2 *)&sh.stage.y[j4 + 2]; nZ = *(const float2 *)&sh.stage.z[j4 + 2];
-            nI = *(const int2 *)&sh.stage.i[j4 + 2];
-            float d4[2];
-            d4[0] = pcr_d2(X.x - q.x, Y.x - q.y, Z.x - q.z); d4[1] = pcr_d2(X.y - q.x, Y.y - q.y, Z.y - q.z);
-#else
-        float4 nX = *(const float4 *)&sh.stage.x[0], nY = *(const float4 *)&sh.stage.y[0], nZ = *(const float4 *)&sh.stage.z[0];
-        int4 nI = *(const int4 *)&sh.stage.i[0];
-        for (int j4 = 0; j4 < nb; j4 += 4) {
-            const float4 X = nX, Y = nY, Z = nZ;           // the LDS reads of the next step are in flight while this one is worked on
-            const int i4[4] = {nI.x, nI.y, nI.z, nI.w};    // (indices included: fetching one at the moment it is needed drained the read-ahead)
-            nX = *(const float4 *)&sh.stage.x[j4 + 4]; nY = *(const float4 *)&sh.stage.y[j4 + 4]; nZ = *(const float4 *)&sh.stage.z[j4 + 4];
-            nI = *(const int4 *)&sh.stage.i[j4 + 4];
-            float d4[4];
-            if (PK) {
-                const kw_f2 da = kw_d2x2(kw_f2{X.x, X.y}, kw_f2{Y.x, Y.y}, kw_f2{Z.x, Z.y}, qx2, qy2, qz2);
-                const kw_f2 db = kw_d2x2(kw_f2{X.z, X.w}, kw_f2{Y.z, Y.w}, kw_f2{Z.z, Z.w}, qx2, qy2, qz2);
-                d4[0] = da.x; d4[1] = da.y; d4[2] = db.x; d4[3] = db.y;
-            } else {
-                d4[0] = pcr_d2(X.x - q.x, Y.x - q.y, Z.x - q.z); d4[1] = pcr_d2(X.y - q.x, Y.y - q.y, Z.y - q.z);
-                d4[2] = pcr_d2(X.z - q.x, Y.z - q.y, Z.z - q.z); d4[3] = pcr_d2(X.w - q.x, Y.w - q.y, Z.w - q.z);
-            }
-#endif
-#pragma unroll
-            for (int u = 0; u < KW_STEP; u++) {
-            const float d2 = d4[u];
+        kw_scan<PK>(sh.stage, nb, q.x, q.y, q.z, [&](const float d2, const int id) {
             if (__ballot(d2 < sd[0]) != 0ull) {
-                sh.log[nlog < KwShared<K>::LOG ? nlog : KwShared<K>::LOG - 1] = i4[u];      // all lanes, one address, one value
-                nlog = __builtin_amdgcn_readfirstlane(nlog + 1);
+                sh.log[nlog < KwShared<K>::LOG ? nlog : KwShared<K>::LOG - 1] = id;      // all lanes, one address, one value
+                nlog++;
                 insert(d2);
             }
-            }
-        }
+        });
     };
     // A wavefront whose 64 queries lie far apart (sparse regions, a jump of the Morton curve inside the group) would drag all its lanes
     // through the neighbourhoods of each: ~1 % of the wavefronts took 3-6x the mean and set the length of the launch.  They stop after
@@ -377,48 +391,26 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
 #pragma unroll
     for (int j = 0; j < K; j++) ties += (sd[j] == bound) ? 1 : 0;
     if (!live || bound == a.r2cap_f) ties = 0;
-    int cnt = 0, tcnt = 0;
+    // A candidate under the bound goes to the row, and so do the first `ties` candidates AT the bound.  No count is tested: with a full
+    // list exactly k - ties candidates lie under the bound, with a list that is not full fewer than k, and no point is staged twice (the
+    // log holds a point once; the walk leaves the seed range out).  A tie with the bound of any lane is rare, so the step is split on it
+    // wave-wide: without one a candidate costs a compare, a predicated store through the lane's write pointer and the pointer's advance.
+    int32_t *wp = row;
+    int tcnt = 0;
     auto scan2 = [&](int nb) {
-#if KW_STEP == 2         // two candidates per step: 16 VGPRs of read-ahead instead of 32
-        float2 nX = *(const float2 *)&sh.stage.x[0], nY = *(const float2 *)&sh.stage.y[0], nZ = *(const float2 *)&sh.stage.z[0];
-        int2 nI = *(const int2 *)&sh.stage.i[0];
-        for (int j4 = 0; j4 < nb; j4 += 2) {
-            const float2 X = nX, Y = nY, Z = nZ;
-            const int i4[2] = {nI.x, nI.y};
-            nX = *(const float2 *)&sh.stage.x[j4 + 2]; nY = *(const float2 *)&sh.stage.y[j4 + 2]; nZ = *(const float2 *)&sh.stage.z[j4 + 2];
-            nI = *(const int2 *)&sh.stage.i[j4 + 2];
-            float d4[2];
-            d4[0] = pcr_d2(X.x - q.x, Y.x - q.y, Z.x - q.z); d4[1] = pcr_d2(X.y - q.x, Y.y - q.y, Z.y - q.z);
-#else
-        float4 nX = *(const float4 *)&sh.stage.x[0], nY = *(const float4 *)&sh.stage.y[0], nZ = *(const float4 *)&sh.stage.z[0];
-        int4 nI = *(const int4 *)&sh.stage.i[0];
-        for (int j4 = 0; j4 < nb; j4 += 4) {
-            const float4 X = nX, Y = nY, Z = nZ;           // the LDS reads of the next step are in flight while this one is worked on
-            const int i4[4] = {nI.x, nI.y, nI.z, nI.w};    // (indices included: fetching one at the moment it is needed drained the read-ahead)
-            nX = *(const float4 *)&sh.stage.x[j4 + 4]; nY = *(const float4 *)&sh.stage.y[j4 + 4]; nZ = *(const float4 *)&sh.stage.z[j4 + 4];
-            nI = *(const int4 *)&sh.stage.i[j4 + 4];
-            float d4[4];
-            if (PK) {
-                const kw_f2 da = kw_d2x2(kw_f2{X.x, X.y}, kw_f2{Y.x, Y.y}, kw_f2{Z.x, Z.y}, qx2, qy2, qz2);
-                const kw_f2 db = kw_d2x2(kw_f2{X.z, X.w}, kw_f2{Y.z, Y.w}, kw_f2{Z.z, Z.w}, qx2, qy2, qz2);
-                d4[0] = da.x; d4[1] = da.y; d4[2] = db.x; d4[3] = db.y;
-            } else {
-                d4[0] = pcr_d2(X.x - q.x, Y.x - q.y, Z.x - q.z); d4[1] = pcr_d2(X.y - q.x, Y.y - q.y, Z.y - q.z);
-                d4[2] = pcr_d2(X.z - q.x, Y.z - q.y, Z.z - q.z); d4[3] = pcr_d2(X.w - q.x, Y.w - q.y, Z.w - q.z);
-            }
-#endif
-#pragma unroll
-            for (int u = 0; u < KW_STEP; u++) {
-            const float d2 = d4[u];
+        kw_scan<PK>(sh.stage, nb, q.x, q.y, q.z, [&](const float d2, const int id) {
             const bool le = d2 <= bound;
             if (__ballot(le) != 0ull) {
                 const bool eq = d2 == bound;
-                const bool take = le && (!eq || tcnt < ties) && cnt < k;
-                if (take) row[cnt] = i4[u];
-                cnt += take ? 1 : 0; tcnt += (take && eq) ? 1 : 0;
+                bool take = le;
+                if (__ballot(eq) != 0ull) {                     // some lane ties: it takes the candidate while its ties last
+                    asm volatile("");                           // (keeps this a branch: flattened into selects, every candidate paid for the tie logic)
+                    take = le && (!eq || tcnt < ties);
+                    tcnt += (take && eq) ? 1 : 0;
+                }
+                if (take) { *wp = id; wp++; }
             }
-            }
-        }
+        });
     };
     if (nlog <= KwShared<K>::LOG) {
         // every member of a lane's k-best beat that lane's bound when pass 1 saw it, so the log holds them all: replay it, the gather of
@@ -438,6 +430,7 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
         }
     } else kw_pass<true>(a.t, m, sh.stk, live, start_node, g0, q.x, q.y, q.z, plo, phi, a.keep, sh.stage, 0x7fffffff, [&]() { return bound; }, scan2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the rows this wavefront has just stored are read back below
+    const int cnt = (int)(wp - row);
 
     // ---- epilogue in float64 on the selected neighbours (inputs are exact float32 -> same values as the oracle), one query per lane
     const double qx = q.x, qy = q.y, qz = q.z;
@@ -502,8 +495,9 @@ __device__ static inline void d_knn_wave(const KnnArgs &a) {
     }
 }
 
-// 4 wavefronts per SIMD up to K = 32 (128 VGPRs, 18 spilled; in the default bench, groups of 6 x 4 in flight: 3 wavefronts, 144 VGPRs and no
-// spill 617 pairs/s, 4 wavefronts 643, 5 wavefronts, 96 VGPRs and 64 spilled 588)
+// 4 wavefronts per SIMD up to K = 32 (113-122 VGPRs, no scratch.  With the walk's state in VGPRs the same bound meant 128 VGPRs and 8-16 B
+// of scratch; then, in the default bench, groups of 6 x 4 in flight: 3 wavefronts, 144 VGPRs and no spill 617 pairs/s, 4 wavefronts 643,
+// 5 wavefronts, 96 VGPRs and 64 spilled 588)
 template <int MODE, int K> struct OpKnnWave : PcrOp<KnnArgs, KW_BS> {
     static constexpr int kWavesMin = K <= 32 ? 4 : 2, kWavesMax = K <= 32 ? 4 : 3;
     __device__ static inline void run(const KnnArgs &a) { [[clang::always_inline]] d_knn_wave<MODE, K>(a); }
