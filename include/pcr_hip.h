@@ -870,6 +870,63 @@ int pcr_scan_context(pcr_context *ctx, const float *xyz, int64_t n, const pcr_sc
 int pcr_scan_context_distance(pcr_context *ctx, const float *descA, int64_t nA, const float *descB, int64_t nB, int R, int S, double *out_dist,
                               int32_t *out_shift);
 
+/* == Joint multiway registration of a set of scans (Lu and Milios 1997; Borrmann et al., "Globally consistent 3D mapping with scan matching",
+ *    RAS 2008; PCL ships it as registration::LUM.  Open3D has no such call and the reference's "LUM" works on poses alone).  All scans of a
+ *    graph go into one least-squares problem whose correspondences are searched again, edge by edge, at the current poses of every
+ *    iteration.  The device part is the linearisation of a whole edge list in one call; the assembly, the gauge, the solve and the loop are
+ *    host float64 (multiway.py).  This statement is the specification; tests/multiway_reference.py restates it in numpy.
+ *    PROBLEM.  n clouds; cloud i has float32 points and, where the estimator needs them, float32 normals.  A node pose T_i is float64 4x4 and
+ *    maps cloud i into the common frame (PoseGraphNode.pose, poses_relativas_para_absolutas).  An edge (a, b), a != b, makes cloud a the source
+ *    and cloud b the searched target.  The same pair may appear in both directions and more than once.
+ *    ROWS OF AN EDGE AT M (M = the pose of a in the frame of b, float64, row-major 4x4 of which the first three rows are read, given by the
+ *    caller; the loop passes inv(T_b) T_a with the rigid inverse (R^T, -R^T t)).
+ *    1. For a source point p = (x, y, z): q_r = ((M_r0 x + M_r1 y) + M_r2 z) + M_r3 in float64, every product and sum rounded once, nothing
+ *       contracted (numpy's elementwise expression gives the same bits).
+ *    2. qf = (float)q, component by component.
+ *    3. The correspondence is the row of the index rule (pcr_index_hybrid with max_nn = 1 and radius = max_correspondence_distance) for the
+ *       query qf in cloud b: the smallest (float64 d^2, caller index) with d^2 < radius * radius, strict, or none.  A non-finite qf finds
+ *       nothing, and so does every query in an empty cloud b.
+ *    SUMS OF AN EDGE, in the frame of b.  s = q (the float64 of step 1, not qf), t and n_t the matched point and its normal as stored, widened
+ *    to float64, w = the robust kernel's weight of a row's r as pcr_estimation_compute_transformation forms it (L2: 1, L1:
+ *    1 / max(|r|, 1e-300), GM: k / (k + r^2)^2).
+ *      PCR_EST_POINT_TO_PLANE    one row per match: r = (s - t).n_t, J = [s x n_t, n_t].
+ *      PCR_EST_POINT_TO_POINT    three unweighted rows per match: r = s - t, J = [-skew(s) | I].  with_scaling != 0 is PCR_EINVAL.
+ *      PCR_EST_GENERALIZED_ICP   from normals, the rows of pcr_registration_generalized_icp at the pose M: both normals normalised, e1 where
+ *                                n.x < -0.99, C = I - (1 - epsilon) n n^T, W = (C_t + R C_s R^T)^(-1/2) with R the rotation of M, three rows
+ *                                r = W (s - t), J = W [-skew(s) | I], each weighted by the kernel's weight of its own r.
+ *    Per edge: JTJ = sum w J^T J (6 x 6, unknowns ordered rotation then translation), JTr = sum w J r (6), rows = the number of matched source
+ *    points, stats = {sum_d2, sum_r2, sum_wr2}: the sums of the search's float64 d^2, of r^2 and of w r^2 over the rows.
+ *    Everything is summed in float64 without floating-point atomics.  The source points are taken in the Morton order of the source's own
+ *    index, in tiles of PCR_MULTIWAY_TILE; a tile's sum is a fixed tree over its points and an edge's sum adds its tiles in ascending order.
+ *    The order of an edge's sum therefore depends on that edge's two clouds and the launch geometry only, not on what else is in the list:
+ *    the same edge gives the same bits on every run, in any position of any list.
+ *    JOINT SYSTEM (host).  The update is T_i <- V(x_i) T_i with V = TransformVector6dToMatrix4d (Rz Ry Rx, then the translation).  With
+ *    A = Ad(inv(T_b)), for (R, t) the block matrix [[R, 0], [skew(t) R, R]], an edge contributes H_w = A^T JTJ A and g_w = A^T JTr: H_w is
+ *    added to the blocks (a, a) and (b, b) and subtracted from (a, b) and (b, a); g_w is added to g_a and subtracted from g_b.  The step
+ *    solves H x = -g.  GAUGE: the unknowns of reference_node are removed; a node touched by no edge with rows > 0 is removed too and keeps its
+ *    pose; every connected component (over the edges with rows > 0) that does not hold the reference node has its lowest-numbered node
+ *    removed as well.  A solve that fails or gives a non-finite x ends the loop: converged = false, the poses stay those of the last
+ *    completed step.
+ *    LOOP.  RegistrationICP's: linearise at the given poses, then update / linearise until |d fitness| < relative_fitness and
+ *    |d rmse| < relative_rmse, or max_iteration updates; fitness = sum rows / sum over the edges of n_a, inlier_rmse =
+ *    sqrt(sum sum_d2 / sum rows).
+ *    ERRORS.  PCR_EINVAL with a message naming the argument: edges (an index outside [0, n_clouds), a == b), max_correspondence_distance
+ *    (not finite or <= 0), M (a non-finite entry), estimation (null, an unknown kind or loss, with_scaling), normals (an estimator that needs
+ *    normals a cloud does not carry: point-to-plane the target's, GICP both; the message names the cloud).
+ * pcr_multiway_create: xyz[i] device, n[i] x 3 float32 (may be null when n[i] == 0, which is valid); normals may be null, and so may single
+ * entries; the problem keeps a search index (pcr_index_create) and a copy of the normals per cloud in device memory of its own until
+ * pcr_multiway_destroy, so the caller's arrays may be freed when it returns.  pcr_multiway_linearize: edges2 host int32 E x 2 rows (a, b); M
+ * host float64 E x 16; JTJ host E x 36 (full symmetric matrices), JTr host E x 6, stats host E x 3, rows host int64 E; match optional, device
+ * int32 with one entry per source point of every edge in edge order (edge e starts at the sum of n_a over the edges before it; entry i is
+ * the caller index in b matched to caller point i of a, or -1).  E == 0 is valid.  The call is finished when it returns. */
+#define PCR_MULTIWAY_TILE 256
+typedef struct pcr_multiway pcr_multiway;
+int pcr_multiway_create(pcr_context *ctx, int n_clouds, const float *const *xyz, const float *const *normals, const int64_t *n, pcr_multiway **problem);
+int pcr_multiway_destroy(pcr_multiway *problem);
+int pcr_multiway_linearize(pcr_context *ctx, const pcr_multiway *problem, const int32_t *edges2, int64_t E, const double *M,
+                           double max_correspondence_distance, const pcr_estimation *estimation, double *JTJ, double *JTr, double *stats,
+                           int64_t *rows, int32_t *match);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

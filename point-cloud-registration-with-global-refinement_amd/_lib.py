@@ -59,6 +59,7 @@ class PcrRansacInfo(C.Structure):
 
 
 EST_POINT_TO_POINT, EST_POINT_TO_PLANE, EST_GENERALIZED_ICP = 1, 2, 3          # pcr_estimation_kind
+MULTIWAY_TILE = 256          # PCR_MULTIWAY_TILE: source points per tile of pcr_multiway_linearize
 
 
 class PcrEstimation(C.Structure):
@@ -153,9 +154,10 @@ EXPORTS = [
     "pcr_registration_voxelized_gicp",
     "pcr_voxel_map_create_on_grid", "pcr_voxel_map_insert", "pcr_voxel_map_merge", "pcr_voxel_map_remove_far", "pcr_voxel_map_grid",
     "pcr_scan_context", "pcr_scan_context_distance",
+    "pcr_multiway_create", "pcr_multiway_destroy", "pcr_multiway_linearize",
 ]
 
-# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list and the boundary detector (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
+# prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
 QUERY_PROTOTYPES = {
     "pcr_nearest_neighbor_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "pcr_point_cloud_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p], C.c_int),
@@ -207,6 +209,10 @@ QUERY_PROTOTYPES = {
     "pcr_scan_context": ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PcrScanContextParams), C.POINTER(PcrScanContextTables), C.c_void_p,
                           C.POINTER(PcrScanContextInfo)], C.c_int),
     "pcr_scan_context_distance": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_multiway_create": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_multiway_destroy": ([C.c_void_p], C.c_int),
+    "pcr_multiway_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.POINTER(PcrEstimation), C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

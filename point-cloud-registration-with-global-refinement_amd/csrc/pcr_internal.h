@@ -251,6 +251,10 @@ int pcr_dev_tagged_knn(pcr_context *ctx, const DevCloud *c, const float *query_x
 int pcr_dev_tagged_hybrid(pcr_context *ctx, const DevCloud *c, const float *query_xyz, int64_t m, const uint32_t *qperm, double radius, int max_nn, int32_t *idx, double *d2,
                           int32_t *counts);
 
+// the sorted cloud of a search index (points tagged with their caller row in w, octree; all null for an index without points), its device and
+// its point count: for the units that walk an index with a kernel of their own (pcr_multiway.hip)
+const DevCloud *pcr_index_cloud(const pcr_index *index, int *device, int64_t *n);
+
 int pcr_registro_fgr_impl(pcr_context *ctx, const float *src_xyz, const float *src_prior, int64_t ns, const float *tgt_xyz, const float *tgt_prior, int64_t nt,
                           const pcr_fgr_params *p, float *src_normals_out, float *tgt_normals_out, pcr_result *result, int32_t *correspondences);
 // registro_FGR of G pairs through the same launches (pcr_fgr.hip); 1 = declined (sizes / parameters): run the pairs one by one

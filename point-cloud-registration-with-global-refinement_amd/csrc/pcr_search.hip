@@ -323,6 +323,13 @@ extern "C" int pcr_index_destroy(pcr_index *index) {
     return PCR_OK;
 }
 
+// what a unit that walks an index with a kernel of its own needs of it (pcr_multiway.hip): the sorted cloud and the device it lives on
+const DevCloud *pcr_index_cloud(const pcr_index *index, int *device, int64_t *n) {
+    if (device) *device = index->device;
+    if (n) *n = index->n;
+    return &index->c;
+}
+
 static int search_check(pcr_context *ctx, const pcr_index *index, const float *q, int64_t m, const char *what) {
     if (!index || m < 0 || m > SRCH_MAX_POINTS || (m > 0 && !q)) { ctx->err = std::string(what) + ": bad index, query pointer or query count"; return PCR_EINVAL; }
     if (index->device != ctx->device) { ctx->err = std::string(what) + ": the index lives on another device than the context"; return PCR_EINVAL; }

@@ -327,3 +327,31 @@ def pose_graph_from_odometry(clouds, poses, closures=(), voxel_size=0.1, num_sec
         g.edges.append(PoseGraphEdge(i, i + 1, X, information_fn(clouds[i], clouds[i + 1], voxel_size, X), uncertain=False))
     g.edges.extend(loop_closure_edges(clouds, closures, voxel_size, num_sectors, register_fn, information_fn, min_fitness))
     return g
+
+
+# ------------------------------------------------------------------------------------- joint refinement on the points themselves
+def refine_pose_graph(clouds, pose_graph: PoseGraph, max_correspondence_distance, estimation_method=None, criteria=None, reference_node=0, symmetric=True):
+    """The last stage after `pose_graph_from_odometry` and `global_optimization`, which see relative poses and one frozen information matrix per
+    edge: `multiway.multiway_registration` over the graph's edges, whose correspondences are searched again in the clouds at every iteration.
+    The edges are the graph's `(source_node_id, target_node_id)` in order, each followed by its reverse with `symmetric`; the start poses are
+    the node poses.  `clouds` is a list of clouds, one per node, or an open `multiway.MultiwayProblem` over them.  The refined poses are
+    written back to the nodes and the `MultiwayResult` is returned; edge transformations, information matrices and `uncertain` flags are left
+    as they are."""
+    from .multiway import multiway_registration
+    n = len(pose_graph.nodes)
+    count = len(clouds.sizes) if hasattr(clouds, "linearize") else len(clouds)
+    if count != n:
+        raise ValueError(f"refine_pose_graph: {count} clouds but {n} nodes")
+    edges = []
+    for e in pose_graph.edges:
+        s, t = int(e.source_node_id), int(e.target_node_id)
+        if not (0 <= s < n and 0 <= t < n) or s == t:
+            raise ValueError(f"refine_pose_graph: edge ({s}, {t}) does not join two different nodes of the {n} in the graph")
+        edges.append((s, t))
+        if symmetric:
+            edges.append((t, s))
+    result = multiway_registration(clouds, [nd.pose for nd in pose_graph.nodes], np.array(edges, dtype=np.int32).reshape(-1, 2), max_correspondence_distance,
+                                   estimation_method, criteria, reference_node)
+    for nd, T in zip(pose_graph.nodes, result.poses):
+        nd.pose = np.array(T, dtype=np.float64)
+    return result
