@@ -415,6 +415,74 @@ int pcr_voxel_map_remove_far(pcr_context *ctx, pcr_voxel_map *map, const double 
 /* the grid of a map, each output optional (host): grid_min3, origin3 = grid_min3 - voxel_size / 2, voxel_size */
 int pcr_voxel_map_grid(const pcr_voxel_map *map, double *grid_min3, double *origin3, double *voxel_size);
 
+/* ============================================================================================ NDT on a normal-distributions voxel map
+ * The Normal Distributions Transform (Biber & Strasser, IROS 2003; Magnusson, 2009; PCL's NormalDistributionsTransform, ndt_omp): the target
+ * becomes a grid of cells, each with the mean and the SAMPLE covariance of its member positions, and a source point is scored against the normal
+ * distribution of the cell it falls into (or of that cell and its neighbours).  Nothing is needed per point, neither normals nor covariances, and
+ * there is no nearest-neighbour search.  Open3D has no such call and the reference never makes one, so this statement is the specification.
+ *
+ * MAP.  Input: n >= 1 target points (float32), voxel_size, min_points_per_voxel >= 2 (PCL's default: 6) and eigenvalue_ratio in (0, 1] (PCL's
+ *   min_covar_eigvalue_mult, default 0.01).  The grid, the cells, the counts N_v, the means mu_v (float32) and the Morton row order are exactly MAP
+ *   of the voxelized GICP section above.  The member statistic of point i in cell v: d = float64(p_i) - float64(mu_v); its six products
+ *   d_x d_x, d_x d_y, d_x d_z, d_y d_y, d_y d_z, d_z d_z are each rounded once to float64 and then to float32.  C_v = per channel (float64 sum of the
+ *   members' values in input order) / N_v, rounded to float32: the ordered-sum rule that section applies to a member cov6.
+ *   A cell is VALID iff N_v >= min_points_per_voxel and the largest eigenvalue lambda_max of S_v = C_v N_v / (N_v - 1) (float64) is > 0.
+ *   The information matrix of a valid cell is A_v = V diag(1 / max(lambda_k, eigenvalue_ratio lambda_max)) V^T, in float64 from the symmetric
+ *   eigendecomposition S_v = V diag(lambda) V^T, computed once at map creation and kept in float64 (six numbers per cell: xx,xy,xz,yy,yz,zz).
+ *   An invalid cell keeps its row (count, mean, C_v) and has A_v = 0.
+ * ROWS AT A POSE T.  Exactly ROWS of the voxelized GICP section with "valid" in place of "N_v >= min_points_per_voxel": the same expression for
+ *   q, the same candidate offsets for the neighbourhoods 1, 7 and 27, the same order (by i, then by offset order).
+ * SCORE CONSTANTS (Magnusson's and PCL's), from outlier_ratio p (default 0.55) and r = voxel_size, in float64 on the host:
+ *   c1 = 10 (1 - p), c2 = p / r^3, d3 = -log c2, d1 = -log(c1 + c2) - d3, d2 = -2 log((-log(c1 e^(-1/2) + c2) - d3) / d1).
+ * UPDATE.  Row (i, v): delta = q_i - float64(mu_v), m = delta^T A_v delta, e = exp(-d2 m / 2), w = -d1 d2 e (> 0), J = [-skew(q_i) | I].  The row
+ *   adds w J^T A_v J to the 6x6 matrix and w J^T A_v delta to the right-hand side (the sign convention of the GICP update) and -d1 e to the score.
+ *   Rows are NOT weighted by N_v.  The system is solved and turned into a pose exactly as the GICP update (LDLT, Rz Ry Rx, left-multiplied).
+ *   No rows: the identity.  This is the Gauss-Newton (IRLS) form of the NDT objective: the exact gradient of the score, and its Hessian without the
+ *   negative term and without the second-derivative terms, so the matrix is positive semi-definite.  PCL's Newton step with the More-Thuente line
+ *   search is NOT what runs.
+ * LOOP.  RegistrationICP's, as in the voxelized GICP section: rows at init, then update / left-multiply / rows, until |d fitness| <
+ *   relative_fitness and |d RMSE| < relative_rmse, or max_iteration.  fitness = (source points with at least one row) / n_src,
+ *   inlier_rmse = sqrt(sum over the rows of |q_i - mu_v|^2 / rows), n_correspondences = the number of rows.  The loop does not use the score.
+ * All cloud and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed and is never changed;
+ * any context on the same device may use it for any number of calls. */
+typedef struct pcr_ndt_map pcr_ndt_map;
+typedef struct {
+    double relative_fitness;
+    double relative_rmse;
+    int32_t max_iteration;
+    int32_t neighborhood;     /* 1, 7 or 27 candidate cells per source point */
+    double outlier_ratio;     /* p of the score constants, in (0, 1) */
+} pcr_ndt_params;
+
+/* n >= 1.  A non-finite value in xyz, voxel_size <= 0 (or not finite), min_points_per_voxel < 2, eigenvalue_ratio outside (0, 1], cell indices
+ * that do not fit 21 bits: PCR_EINVAL with a message naming the argument.  Finished when it returns. */
+int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n, double voxel_size, int min_points_per_voxel, double eigenvalue_ratio,
+                       pcr_ndt_map **out);
+/* Frees the map (waits for the device, so no call is still reading it).  NULL is allowed. */
+int pcr_ndt_map_destroy(pcr_ndt_map *map);
+/* number of occupied cells = map rows (valid or not) */
+int pcr_ndt_map_size(const pcr_ndt_map *map, int64_t *cells);
+/* the map's rows in Morton order, each output optional (device): cell3 (cells x 3 int32), count (cells int32), mean3 (cells x 3 float32),
+ * cov6 (cells x 6 float32: C_v), info6 (cells x 6 float64: A_v), valid (cells uint8).  Asynchronous on the context's stream. */
+int pcr_ndt_map_read(pcr_context *ctx, const pcr_ndt_map *map, int32_t *cell3, int32_t *count, float *mean3, float *cov6, double *info6,
+                     uint8_t *valid);
+/* the grid of a map, each output optional (host): origin3 = the target's minimum - voxel_size / 2, voxel_size */
+int pcr_ndt_map_grid(const pcr_ndt_map *map, double *origin3, double *voxel_size);
+/* the rows (i, v) of the rule at the pose T: rows2 = int32 pairs, capacity n_src x neighborhood rows; *n_rows on the host.  A neighborhood that is
+ * not 1, 7 or 27, a non-finite value in src_xyz / T, a map on another device than the context: PCR_EINVAL naming the argument. */
+int pcr_ndt_map_correspondences(pcr_context *ctx, const pcr_ndt_map *map, const float *src_xyz, int64_t n_src, const double *T, int neighborhood,
+                                int32_t *rows2, int64_t *n_rows);
+/* UPDATE's sums at the pose T in ONE kernel launch, all outputs on the host and each optional: JTJ (36, the full symmetric matrix), JTr (6),
+ * *score, *rows, *points_with_rows, *sum_d2 (sum over the rows of |q_i - mu_v|^2).  The sums are taken in a fixed order: the same bits on every
+ * run.  outlier_ratio outside (0, 1) and the refusals of pcr_ndt_map_correspondences: PCR_EINVAL naming the argument. */
+int pcr_ndt_linearize(pcr_context *ctx, const pcr_ndt_map *map, const float *src_xyz, int64_t n_src, const double *T, int neighborhood,
+                      double outlier_ratio, double *JTJ, double *JTr, double *score, int64_t *rows, int64_t *points_with_rows, double *sum_d2);
+/* the loop of the rule from init_T.  max_iteration < 0, outlier_ratio outside (0, 1), a neighborhood that is not 1, 7 or 27, a non-finite value
+ * in src_xyz / init_T, a map on another device: PCR_EINVAL naming the argument.  A map without a valid cell is no error: no rows, the pose stays
+ * init_T, fitness 0.  correspondences: optional device int32, capacity n_src x neighborhood rows: the rows at the returned pose. */
+int pcr_registration_ndt(pcr_context *ctx, const float *src_xyz, int64_t n_src, const pcr_ndt_map *map, const double *init_T,
+                         const pcr_ndt_params *params, pcr_result *result, int32_t *correspondences);
+
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)
  * -> registration_generalized_icp, chained.  src/tgt_normals optional (AF flow orientation prior).

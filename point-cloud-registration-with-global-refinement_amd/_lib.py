@@ -48,6 +48,11 @@ class PcrVgicpParams(C.Structure):
                 ("relative_rmse", C.c_double), ("max_iteration", C.c_int32), ("neighborhood", C.c_int32), ("min_points_per_voxel", C.c_int32)]
 
 
+class PcrNdtParams(C.Structure):
+    _fields_ = [("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("max_iteration", C.c_int32), ("neighborhood", C.c_int32),
+                ("outlier_ratio", C.c_double)]
+
+
 class PcrRansacParams(C.Structure):
     _fields_ = [("ransac_n", C.c_int32), ("with_scaling", C.c_int32), ("max_iteration", C.c_int32), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("edge_length_threshold", C.c_double), ("distance_threshold", C.c_double),
@@ -155,6 +160,8 @@ EXPORTS = [
     "pcr_voxel_map_create_on_grid", "pcr_voxel_map_insert", "pcr_voxel_map_merge", "pcr_voxel_map_remove_far", "pcr_voxel_map_grid",
     "pcr_scan_context", "pcr_scan_context_distance",
     "pcr_multiway_create", "pcr_multiway_destroy", "pcr_multiway_linearize",
+    "pcr_ndt_map_create", "pcr_ndt_map_destroy", "pcr_ndt_map_size", "pcr_ndt_map_read", "pcr_ndt_map_grid", "pcr_ndt_map_correspondences",
+    "pcr_ndt_linearize", "pcr_registration_ndt",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -213,6 +220,15 @@ QUERY_PROTOTYPES = {
     "pcr_multiway_destroy": ([C.c_void_p], C.c_int),
     "pcr_multiway_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.POINTER(PcrEstimation), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+    "pcr_ndt_map_create": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_ndt_map_destroy": ([C.c_void_p], C.c_int),
+    "pcr_ndt_map_size": ([C.c_void_p, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_ndt_map_read": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_ndt_map_grid": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+    "pcr_ndt_map_correspondences": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_ndt_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
+    "pcr_registration_ndt": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrNdtParams), C.POINTER(PcrResult), C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

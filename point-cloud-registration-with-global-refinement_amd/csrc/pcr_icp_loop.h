@@ -1,7 +1,7 @@
 // pcr_icp_loop.h -- what the iteration kernels of the ICP loops share, and the host side of a loop: the problem state and the argument block, the
 // end of an iteration (icp_finish: workgroup reduction, last-workgroup gather, convergence test, 6x6 solve, pose update), the graph cache and the
-// chunk pump.  Included by pcr_gicp.hip (GICP, the three ICP estimators, colored ICP, the lockstep groups) and by pcr_vgicp.hip (voxelized GICP),
-// which is a unit of its own so that the search kernels of pcr_gicp.hip compile to what they compiled to before it existed.
+// chunk pump.  Included by pcr_gicp.hip (GICP, the three ICP estimators, colored ICP, the lockstep groups), by pcr_vgicp.hip (voxelized GICP) and by
+// pcr_ndt.hip (NDT), each of which is a unit of its own so that the search kernels of pcr_gicp.hip compile to what they compiled to before it existed.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -22,7 +22,9 @@
 // COLORED: registration_colored_icp -- k_icp_nn + k_icp_iter_colored, a sibling of k_icp_iter with its own argument block (IcpColorArgs)
 // VGICP: registration_voxelized_gicp -- k_icp_iter_vgicp alone (no search kernel), a sibling with its own argument block (IcpVoxelArgs); to
 //   icp_finish the mode means one thing: sums[27] counts the source points with a row (the fitness), sums[29] the rows
-enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2, ICP_MODE_P2PL = 3, ICP_MODE_P2P = 4, ICP_MODE_P2P_SCALED = 5, ICP_MODE_COLORED = 6, ICP_MODE_VGICP = 7 };
+// NDT: registration_ndt -- k_icp_iter_ndt alone (pcr_ndt.hip), a sibling with its own argument block (IcpNdtArgs); to icp_finish it is VGICP
+enum { ICP_MODE_GICP = 0, ICP_MODE_EVAL = 1, ICP_MODE_GICP_COV = 2, ICP_MODE_P2PL = 3, ICP_MODE_P2P = 4, ICP_MODE_P2P_SCALED = 5, ICP_MODE_COLORED = 6, ICP_MODE_VGICP = 7,
+       ICP_MODE_NDT = 8 };
 
 struct IcpState {
     double T[16];
@@ -167,7 +169,7 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
         }
         const double *S = fin[0];
         const long long count = (long long)(S[29] + 0.5);
-        const long long hits = MODE == ICP_MODE_VGICP ? (long long)(S[27] + 0.5) : count;      // (a constant copy of count for every other mode)
+        const long long hits = (MODE == ICP_MODE_VGICP || MODE == ICP_MODE_NDT) ? (long long)(S[27] + 0.5) : count;      // (a constant copy of count for every other mode)
         const double fit = ns > 0 ? (double)hits / (double)ns : 0.0;
         const double rmse = count > 0 ? sqrt(S[28] / (double)count) : 0.0;
         const double fit_prev = st->fitness, rmse_prev = st->rmse; const int iter_prev = st->iter;

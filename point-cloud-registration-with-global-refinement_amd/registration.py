@@ -711,6 +711,217 @@ def scan_to_map_odometry(scans, voxel_size, init=np.eye(4), estimation_method=No
     return poses, results, vmap
 
 
+# ---- NDT on a normal-distributions voxel map (pcr_ndt_map_*, pcr_ndt_linearize, pcr_registration_ndt; the rule: include/pcr_hip.h)
+def _check_ndt_rule(fn: str, neighborhood=7, outlier_ratio=0.55, min_points_per_voxel=6, eigenvalue_ratio=0.01):
+    if neighborhood not in (1, 7, 27):
+        raise ValueError(f"{fn}: neighborhood must be 1, 7 or 27, got {neighborhood!r}")
+    if not isinstance(min_points_per_voxel, (int, np.integer)) or min_points_per_voxel < 2:
+        raise ValueError(f"{fn}: min_points_per_voxel must be an integer >= 2, got {min_points_per_voxel!r}")
+    for name, v, closed in (("outlier_ratio", outlier_ratio, False), ("eigenvalue_ratio", eigenvalue_ratio, True)):
+        try:
+            x = float(v)
+        except (TypeError, ValueError):
+            x = float("nan")
+        if not (0.0 < x < 1.0 or (closed and x == 1.0)):
+            raise ValueError(f"{fn}: {name} must lie in (0, 1{']' if closed else ')'}, got {v!r}")
+
+
+class NdtLinearization:
+    """What ``NormalDistributionsMap.linearize`` returns: ``JTJ`` (6, 6), ``JTr`` (6,), ``score``, ``rows``, ``points_with_rows``, ``sum_d2``."""
+
+    def __init__(self, JTJ, JTr, score, rows, points_with_rows, sum_d2):
+        self.JTJ, self.JTr, self.score, self.rows, self.points_with_rows, self.sum_d2 = JTJ, JTr, score, rows, points_with_rows, sum_d2
+
+    def __repr__(self):
+        return f"NdtLinearization(score={self.score!r}, rows={self.rows}, points_with_rows={self.points_with_rows}, sum_d2={self.sum_d2!r})"
+
+
+class NormalDistributionsMap:
+    """The target of NDT registration (Biber & Strasser 2003; Magnusson 2009; PCL's ``NormalDistributionsTransform``): per occupied cell of
+    ``voxel_down_sample``'s grid the member count, the mean, the covariance ``C_v`` of the member positions about it and -- for a cell with at
+    least ``min_points_per_voxel`` members that do not coincide -- the float64 information matrix ``A_v``, the inverse of the sample covariance
+    with its eigenvalues raised to ``eigenvalue_ratio`` times the largest.  Built once from the target's positions alone (no normals, no
+    covariances) and good for any number of registrations until ``close()``.  Rows are in Morton order of the cell index.  The map does not
+    grow: build a new one."""
+
+    _handle = None
+
+    def __init__(self, target: PointCloud, voxel_size: float, min_points_per_voxel: int = 6, eigenvalue_ratio: float = 0.01):
+        fn = "NormalDistributionsMap"
+        self._voxel_size = _check_voxel_size(fn, voxel_size)
+        _check_ndt_rule(fn, min_points_per_voxel=min_points_per_voxel, eigenvalue_ratio=eigenvalue_ratio)
+        self.min_points_per_voxel, self.eigenvalue_ratio = int(min_points_per_voxel), float(eigenvalue_ratio)
+        if not isinstance(target, PointCloud) or len(target) == 0:
+            raise RuntimeError(f"{fn}: the target must be a PointCloud with at least one point")
+        ctx = _lib.Context.current()
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pcr_ndt_map_create(ctx.handle, _ptr(target.device_xyz()), C.c_int64(len(target)), C.c_double(self._voxel_size),
+                                             C.c_int(self.min_points_per_voxel), C.c_double(self.eigenvalue_ratio), C.byref(h)), fn)
+        self._handle = h
+        self._lib = ctx.lib
+        m = C.c_int64(0)
+        self._lib.pcr_ndt_map_size(h, C.byref(m))
+        self._cells = int(m.value)
+
+    def close(self):
+        """Destroy the map (waits for the device)."""
+        h, self._handle = self._handle, None
+        if h is not None and h.value:
+            self._lib.pcr_ndt_map_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _open(self):
+        if self._handle is None:
+            raise RuntimeError("NormalDistributionsMap: the map is closed")
+        return self._handle
+
+    def __len__(self):
+        self._open()
+        return self._cells
+
+    @property
+    def voxel_size(self) -> float:
+        self._open()
+        return self._voxel_size
+
+    @property
+    def origin(self) -> np.ndarray:
+        """(3,) float64: the target's minimum - ``voxel_size / 2``, the corner of cell (0, 0, 0)"""
+        h = self._open()
+        o = (C.c_double * 3)()
+        self._lib.pcr_ndt_map_grid(h, o, None)
+        return np.array(o, np.float64)
+
+    _COLUMNS = {"cells": (3, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "covariances": (6, "float32"), "information": (6, "float64"),
+                "valid": (None, "uint8")}
+
+    def _read(self, what: str):
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        cols, dtype = self._COLUMNS[what]
+        t = torch.empty((self._cells,) if cols is None else (self._cells, cols), dtype=getattr(torch, dtype), device="cuda")
+        args = [_ptr(t if k == what else None) for k in self._COLUMNS]
+        ctx.check(ctx.lib.pcr_ndt_map_read(ctx.handle, h, *args), "NormalDistributionsMap." + what)
+        return t
+
+    @property
+    def cells(self) -> np.ndarray:
+        """(cells, 3) int32: the cell index (ix, iy, iz) of every row"""
+        return self._read("cells").cpu().numpy()
+
+    @property
+    def counts(self) -> np.ndarray:
+        """(cells,) int32: the member count N_v"""
+        return self._read("counts").cpu().numpy()
+
+    @property
+    def points(self) -> np.ndarray:
+        """(cells, 3) float32: the mean of every cell"""
+        return self._read("points").cpu().numpy()
+
+    @property
+    def covariances(self) -> np.ndarray:
+        """(cells, 6) float32: C_v, the mean of the members' products about the cell mean, xx,xy,xz,yy,yz,zz"""
+        return self._read("covariances").cpu().numpy()
+
+    @property
+    def information(self) -> np.ndarray:
+        """(cells, 6) float64: A_v, xx,xy,xz,yy,yz,zz; zero for an invalid cell"""
+        return self._read("information").cpu().numpy()
+
+    @property
+    def valid(self) -> np.ndarray:
+        """(cells,) bool: the cells that give rows"""
+        return self._read("valid").cpu().numpy().astype(bool)
+
+    def to_point_cloud(self) -> PointCloud:
+        """The cells' means as a cloud that carries the cells' covariances ``C_v``."""
+        pc = PointCloud()
+        pc._xyz = self._read("points")
+        pc._cov = self._read("covariances")
+        return pc
+
+    def correspondences(self, source: PointCloud, T=np.eye(4), neighborhood: int = 7):
+        """The rows (source index, map row) of the rule at the pose ``T``, ordered by source index and then by the neighbourhood's offset
+        order: a device tensor (rows, 2) int32."""
+        fn = "NormalDistributionsMap.correspondences"
+        _check_ndt_rule(fn, neighborhood)
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        rows = torch.empty((max(ns, 1) * int(neighborhood), 2), dtype=torch.int32, device="cuda")
+        n = C.c_int64(0)
+        _, Tp = _T(T)
+        ctx.check(ctx.lib.pcr_ndt_map_correspondences(ctx.handle, h, _ptr(source.device_xyz()), C.c_int64(ns), Tp, C.c_int(int(neighborhood)), _ptr(rows), C.byref(n)), fn)
+        return rows[: n.value]
+
+    def linearize(self, source: PointCloud, T=np.eye(4), neighborhood: int = 7, outlier_ratio: float = 0.55) -> NdtLinearization:
+        """The sums of one update at the pose ``T`` (``pcr_ndt_linearize``, one kernel launch, the same bits on every run): the 6x6 matrix, the
+        right-hand side, the NDT score, the number of rows, of source points with a row, and the rows' summed squared distances."""
+        fn = "NormalDistributionsMap.linearize"
+        _check_ndt_rule(fn, neighborhood, outlier_ratio)
+        h = self._open()
+        ctx = _lib.Context.current()
+        JTJ, JTr = np.zeros((6, 6), np.float64), np.zeros(6, np.float64)
+        score, sum_d2, rows, hits = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int64(0)
+        _, Tp = _T(T)
+        dp = C.POINTER(C.c_double)
+        ctx.check(ctx.lib.pcr_ndt_linearize(ctx.handle, h, _ptr(source.device_xyz()), C.c_int64(len(source)), Tp, C.c_int(int(neighborhood)), C.c_double(float(outlier_ratio)),
+                                            JTJ.ctypes.data_as(dp), JTr.ctypes.data_as(dp), C.byref(score), C.byref(rows), C.byref(hits), C.byref(sum_d2)), fn)
+        return NdtLinearization(JTJ, JTr, float(score.value), int(rows.value), int(hits.value), float(sum_d2.value))
+
+
+def registration_ndt(source: PointCloud, target_or_map, voxel_size=None, init=np.eye(4), criteria=None, neighborhood: int = 7, outlier_ratio: float = 0.55,
+                     min_points_per_voxel: int = 6) -> RegistrationResult:
+    """NDT registration (``pcr_registration_ndt``, include/pcr_hip.h): RegistrationICP's loop in which a source point is scored against the
+    normal distribution of the cell of the target's ``NormalDistributionsMap`` it falls into (``neighborhood`` 1), or of that cell and its
+    6 / 26 neighbours (7 / 27).  Neither cloud needs normals or covariances.  The update is the Gauss-Newton (IRLS) step of Magnusson's
+    score with ``outlier_ratio``, not PCL's Newton step with a line search.  ``target_or_map`` is a ``NormalDistributionsMap``
+    (``voxel_size`` and ``min_points_per_voxel`` are then the map's own) or a ``PointCloud``, for which a map of ``voxel_size`` is built and
+    closed inside the call.  ``correspondence_set`` holds (source index, map row)."""
+    fn = "registration_ndt"
+    _check_ndt_rule(fn, neighborhood, outlier_ratio, min_points_per_voxel)
+    criteria = criteria or ICPConvergenceCriteria()
+    own = None
+    if isinstance(target_or_map, NormalDistributionsMap):
+        nmap = target_or_map
+        nmap._open()
+    elif isinstance(target_or_map, PointCloud):
+        if voxel_size is None:
+            raise ValueError(f"{fn}: voxel_size is required when the target is a PointCloud")
+        _check_voxel_size(fn, voxel_size)
+        own = nmap = NormalDistributionsMap(target_or_map, voxel_size, min_points_per_voxel)
+    else:
+        raise TypeError(f"{fn}: the target must be a PointCloud or a NormalDistributionsMap, got {type(target_or_map).__name__}")
+    try:
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        corr = torch.empty((max(ns, 1) * int(neighborhood), 2), dtype=torch.int32, device="cuda")
+        res = _lib.PcrResult()
+        _, Tp = _T(init)
+        p = _lib.PcrNdtParams(float(criteria.relative_fitness), float(criteria.relative_rmse), int(criteria.max_iteration), int(neighborhood), float(outlier_ratio))
+        ctx.check(ctx.lib.pcr_registration_ndt(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), nmap._open(), Tp, C.byref(p), C.byref(res), _ptr(corr)), fn)
+        return _result(res, corr)
+    finally:
+        if own is not None:
+            own.close()
+
+
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
                     estimation_method=None, criteria=None, nb_neighbors: int = 30, std_ratio: float = 1.0,
                     normal_knn: int = 20) -> RegistrationResult:
