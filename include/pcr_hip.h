@@ -644,6 +644,59 @@ int pcr_registration_ransac_feature_matching(pcr_context *ctx, const float *src_
                                              double max_distance, const pcr_ransac_params *params, pcr_result *result, int32_t *correspondences,
                                              pcr_ransac_info *info);
 
+/* == registration_sc2_based_on_correspondence / spatial_compatibility: global registration by second-order spatial compatibility (after SC2-PCR,
+ *    Chen et al., CVPR 2022; Open3D has no such call, so this statement is the specification).  Deterministic: no random numbers, exact integer
+ *    counts, float64 sums in a fixed order, no floating-point atomics.
+ *    POINTS.  The list is range-checked as every call on a list checks it (PCR_EINVAL with a message).  s_i = source[corres[i,0]],
+ *    t_i = target[corres[i,1]], the float32 coordinates widened to float64.  N = n_corres.
+ *    LENGTHS.  d2(a, b) = dx*dx + dy*dy + dz*dz in float64, every difference, product and sum rounded once, summed in the order x, y, z (no fused
+ *    multiply-add); ls_ij = sqrt(d2(s_i, s_j)), lt_ij = sqrt(d2(t_i, t_j)), IEEE square roots.
+ *    COMPATIBLE.  C_ij = (i != j) and |ls_ij - lt_ij| < tau (strict), tau = inlier_threshold.  Symmetric; repeated rows are compatible with each other.
+ *    BITS.  bits is N x ceil(N / 64) words of 64 bits; bit b of word w of row i is C_{i, 64 w + b}; the bits past column N - 1 are zero.
+ *    COUNTS.  deg_i = sum_j C_ij.  SC2_ij = C_ij * |{k : C_ik and C_jk}|.  score_i = sum_j SC2_ij (int64: twice the triangles through i).
+ *    ORDER.  i comes before j iff score_i > score_j, or the scores are equal and i < j.
+ *    SEEDS.  i is suppressed iff some j before it has ls_ij < nms_radius (strict; whether j is itself suppressed does not matter; nms_radius = 0
+ *    suppresses nothing).  Candidates: the unsuppressed rows with score_i > 0.  The seeds are the first
+ *    min(candidates, max(1, (int64)(seed_ratio * N)), max_seeds) candidates in order.
+ *    PER SEED m.  K1 = m followed by the first up to k1 rows j with C_mj taken by (SC2_mj descending, j ascending).  Inside K1,
+ *    L_ab = C_ab * |{c in K1 : C_ac and C_bc}|.  Of the members a != m of K1 take the first up to k2 by (L_ma descending, position in K1 ascending);
+ *    K2 = m followed by those of them with 2 L_ma >= max_a L_ma (the maximum over the members a != m), in that order.  |K2| < 3: the seed is
+ *    invalid.  T_m = the Umeyama fit without scaling over the rows of K2; a non-finite T_m is invalid.
+ *    SCORE.  As RANSAC: count_m = rows with d2(T s, t) < tau^2 where T s is ((T00 sx + T01 sy) + T02 sz) + T03 per coordinate, err2_m = the sum of
+ *    those d2 in float64 in a fixed order.
+ *    BEST.  A larger count wins; at equal counts the strictly smaller err2; otherwise the earlier seed stays; a count of 0 is never best.
+ *    REFINEMENT.  At most refine_iterations times: I = the inlier rows under T in input order, T' = the point-to-point fit over I (Umeyama without
+ *    scaling); T' replaces T iff its count is larger, or equal with a smaller err2; otherwise the loop stops and T stays.
+ *    RESULT.  transformation = T, fitness = count / N, inlier_rmse = sqrt(err2 / count) (over the list, as RANSAC), iterations = refinement passes
+ *    run, converged = a best seed exists; correspondences (optional, device int32, capacity N rows) = the inlier rows of the list in input order.
+ *    N < 3, no seed or no valid seed: the empty result (identity, fitness 0), not an error.
+ *    LIMITS (PCR_EINVAL with a message): N <= 65536 (the bit matrix is at most 512 MB; refused before anything is allocated: use the mutual
+ *    filter or a keypoint subset), 2 <= k1 <= 63 (K1 fits one wavefront), 1 <= k2 <= k1, tau > 0 and finite, nms_radius >= 0,
+ *    0 < seed_ratio <= 1, 1 <= max_seeds <= 65536, refine_iterations >= 0. */
+typedef struct {
+    double inlier_threshold;          /* tau; no default */
+    double nms_radius;                /* the Python layer passes inlier_threshold for None */
+    int32_t k1;                       /* 30 */
+    int32_t k2;                       /* 20 */
+    double seed_ratio;                /* 0.2 */
+    int32_t max_seeds;                /* 2048 */
+    int32_t refine_iterations;        /* 20 */
+} pcr_sc2_option;
+typedef struct {
+    int64_t n_corres;                 /* rows of the list */
+    int64_t n_seeds;
+    int64_t n_valid;                  /* seeds with a hypothesis */
+    int64_t best_seed;                /* position of the best seed in the order of the seeds; -1: none */
+    int64_t best_seed_count;          /* its count before refinement */
+    int64_t refine_iterations_run;
+} pcr_sc2_info;
+/* corres: device int32 [n_corres x 2]; correspondences and info optional */
+int pcr_registration_sc2_correspondence(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt, const int32_t *corres,
+                                        int64_t n_corres, const pcr_sc2_option *option, pcr_result *result, int32_t *correspondences, pcr_sc2_info *info);
+/* the compatibility graph alone; each output is optional (device): bits n_corres x ceil(n_corres / 64) int64, degrees n_corres int32, scores n_corres int64 */
+int pcr_spatial_compatibility(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt, const int32_t *corres, int64_t n_corres,
+                              double inlier_threshold, int64_t *bits, int32_t *degrees, int64_t *scores);
+
 /* == TransformationEstimationPointToPoint / PointToPlane / ForGeneralizedICP .compute_transformation(source, target, corres) and
  *    .compute_rmse(source, target, corres) (ALL_FUNCTIONS.py:438-439, registro_manual: picked point pairs give the starting pose of a registration).
  *    One fit, or one error figure, over a correspondence list the caller holds.  This statement is the specification.
@@ -1060,6 +1113,15 @@ int pcr_debug_feature_nn(pcr_context *ctx, const float *f0, int64_t n0, const fl
 int pcr_debug_ransac_hypotheses(pcr_context *ctx, const float *src_xyz, const float *src_normals, int64_t n_src, const float *tgt_xyz, const float *tgt_normals,
                                 int64_t n_tgt, const int32_t *corres, int64_t n_corres, double max_distance, const pcr_ransac_params *params, int64_t first,
                                 int64_t count, uint8_t *valid_out, double *T_out, int32_t *inliers_out, double *err2_out);
+
+/* what the SC2 kernels compute for the seeds of pcr_registration_sc2_correspondence with these arguments, in the order of the seeds (refine_iterations
+ * is checked, not used).  *n_seeds (host) = the number of seeds; the other outputs are device arrays with room for min(max(1, (int64)(seed_ratio *
+ * n_corres)), max_seeds) seeds: seed_rows int32 (the seed's row), k1_rows and k2_rows int32 x 64 per seed (the rows of K1 and of K2 in their order,
+ * the seed first, -1 beyond the members), T_out 16 float64 per seed (zeros above the last row for an invalid seed), valid_out bytes, inliers_out
+ * int32 (-1: invalid), err2_out float64.  Fewer than 3 rows: PCR_EINVAL. */
+int pcr_debug_sc2_seeds(pcr_context *ctx, const float *src_xyz, int64_t n_src, const float *tgt_xyz, int64_t n_tgt, const int32_t *corres, int64_t n_corres,
+                        const pcr_sc2_option *option, int64_t *n_seeds, int32_t *seed_rows, int32_t *k1_rows, int32_t *k2_rows, double *T_out, uint8_t *valid_out,
+                        int32_t *inliers_out, double *err2_out);
 
 /* what the plane kernels compute for iterations [first, first + count) of pcr_segment_plane with these arguments, no early stop (num_iterations and
  * probability are checked, not used).  All four outputs are device arrays: valid_out count bytes, plane_out count x 4 float64 (zeros for an

@@ -14,6 +14,8 @@ from .geometry import (KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSear
 from .place import ScanContextDatabase, scan_context, scan_context_distance, shift_to_transformation  # noqa: F401
 from .multiway import MultiwayProblem, MultiwayResult, circuit_edges, expand_edge, multiway_registration  # noqa: F401
 from .posegraph import loop_closure_edges, pose_graph_from_odometry, refine_pose_graph  # noqa: F401
+from .registration import (SpatialCompatibility, SpatialCompatibilityOption, registration_sc2_based_on_correspondence,  # noqa: F401
+                           registration_sc2_based_on_feature_matching, spatial_compatibility)
 from .search import KDTreeFlann, NearestNeighborSearch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -63,6 +63,16 @@ class PcrRansacInfo(C.Structure):
     _fields_ = [("iterations_run", C.c_int64), ("best_iteration", C.c_int64), ("n_valid", C.c_int64), ("n_corres", C.c_int64)]
 
 
+class PcrSc2Option(C.Structure):
+    _fields_ = [("inlier_threshold", C.c_double), ("nms_radius", C.c_double), ("k1", C.c_int32), ("k2", C.c_int32), ("seed_ratio", C.c_double),
+                ("max_seeds", C.c_int32), ("refine_iterations", C.c_int32)]
+
+
+class PcrSc2Info(C.Structure):
+    _fields_ = [("n_corres", C.c_int64), ("n_seeds", C.c_int64), ("n_valid", C.c_int64), ("best_seed", C.c_int64), ("best_seed_count", C.c_int64),
+                ("refine_iterations_run", C.c_int64)]
+
+
 EST_POINT_TO_POINT, EST_POINT_TO_PLANE, EST_GENERALIZED_ICP = 1, 2, 3          # pcr_estimation_kind
 MULTIWAY_TILE = 256          # PCR_MULTIWAY_TILE: source points per tile of pcr_multiway_linearize
 
@@ -162,6 +172,7 @@ EXPORTS = [
     "pcr_multiway_create", "pcr_multiway_destroy", "pcr_multiway_linearize",
     "pcr_ndt_map_create", "pcr_ndt_map_destroy", "pcr_ndt_map_size", "pcr_ndt_map_read", "pcr_ndt_map_grid", "pcr_ndt_map_correspondences",
     "pcr_ndt_linearize", "pcr_registration_ndt",
+    "pcr_registration_sc2_correspondence", "pcr_spatial_compatibility", "pcr_debug_sc2_seeds",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -229,6 +240,12 @@ QUERY_PROTOTYPES = {
     "pcr_ndt_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                            C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
     "pcr_registration_ndt": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrNdtParams), C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_registration_sc2_correspondence": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrSc2Option),
+                                             C.POINTER(PcrResult), C.c_void_p, C.POINTER(PcrSc2Info)], C.c_int),
+    "pcr_spatial_compatibility": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p], C.c_int),
+    "pcr_debug_sc2_seeds": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrSc2Option), C.POINTER(C.c_int64),
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

@@ -1393,6 +1393,149 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     return _ransac_result(res, info, out)
 
 
+SC2_MAX_CORRESPONDENCES = 65536
+
+
+class SpatialCompatibilityOption:
+    """Options of ``registration_sc2_based_on_correspondence`` (``pcr_sc2_option``, include/pcr_hip.h states the rule): ``inlier_threshold``
+    is the compatibility tolerance and the inlier distance (no default), ``nms_radius`` the source-space radius inside which a better row
+    suppresses a seed (``None``: ``inlier_threshold``), ``k1`` / ``k2`` the sizes of the two consensus stages of a seed, ``seed_ratio`` and
+    ``max_seeds`` bound the seeds, ``refine_iterations`` the refits over the inlier rows."""
+
+    def __init__(self, inlier_threshold, nms_radius=None, k1=30, k2=20, seed_ratio=0.2, max_seeds=2048, refine_iterations=20):
+        self.inlier_threshold = float(inlier_threshold)
+        self.nms_radius = None if nms_radius is None else float(nms_radius)
+        self.k1 = int(k1)
+        self.k2 = int(k2)
+        self.seed_ratio = float(seed_ratio)
+        self.max_seeds = int(max_seeds)
+        self.refine_iterations = int(refine_iterations)
+
+
+def _sc2_threshold(fn, tau):
+    tau = float(tau)
+    if not (tau > 0.0 and np.isfinite(tau)):
+        raise RuntimeError(f"{fn}: inlier_threshold must be positive and finite (got {tau})")
+    return tau
+
+
+def _sc2_rows(fn, corres) -> int:
+    """Rows of a caller's list, read from its shape alone; more than the limit is refused before anything touches a device."""
+    shape = tuple(corres.shape) if hasattr(corres, "shape") else np.shape(corres)
+    n = int(shape[0]) if len(shape) == 2 else int(np.prod(shape, dtype=np.int64)) // 2
+    if n > SC2_MAX_CORRESPONDENCES:
+        raise RuntimeError(f"{fn}: {n} correspondences, the limit is {SC2_MAX_CORRESPONDENCES} (the bit matrix would exceed 512 MB): use the mutual "
+                           "filter of correspondences_from_features or a keypoint subset")
+    return n
+
+
+def _sc2_option(fn, option) -> _lib.PcrSc2Option:
+    """``SpatialCompatibilityOption`` -> ``pcr_sc2_option``; every limit of the header raises here, from the arguments alone."""
+    if not isinstance(option, SpatialCompatibilityOption):
+        raise RuntimeError(f"{fn}: option must be a SpatialCompatibilityOption")
+    tau = _sc2_threshold(fn, option.inlier_threshold)
+    nms = tau if option.nms_radius is None else float(option.nms_radius)
+    if not nms >= 0.0:
+        raise RuntimeError(f"{fn}: nms_radius must be >= 0 (got {nms})")
+    if not 2 <= option.k1 <= 63:
+        raise RuntimeError(f"{fn}: k1 must be in 2..63 (got {option.k1})")
+    if not 1 <= option.k2 <= option.k1:
+        raise RuntimeError(f"{fn}: k2 must be in 1..k1 (got {option.k2})")
+    if not 0.0 < option.seed_ratio <= 1.0:
+        raise RuntimeError(f"{fn}: seed_ratio must be in (0, 1] (got {option.seed_ratio})")
+    if not 1 <= option.max_seeds <= 65536:
+        raise RuntimeError(f"{fn}: max_seeds must be in 1..65536 (got {option.max_seeds})")
+    if option.refine_iterations < 0:
+        raise RuntimeError(f"{fn}: refine_iterations must be >= 0 (got {option.refine_iterations})")
+    return _lib.PcrSc2Option(tau, nms, option.k1, option.k2, option.seed_ratio, option.max_seeds, option.refine_iterations)
+
+
+def registration_sc2_based_on_correspondence(source, target, corres, option):
+    """Global registration on a correspondence list by second-order spatial compatibility (after SC2-PCR; include/pcr_hip.h states the
+    rule): true matches preserve the distance between them AND share many other matches that do, so the second-order count separates
+    inliers from outliers at inlier rates where sampling gives up.  Deterministic: no random numbers.  ``corres`` is (C, 2) rows of (source
+    index, target index), at most 65536 of them; fitness and RMSE are taken over that list, ``correspondence_set`` holds its inlier rows in
+    input order.  The result also carries ``info``: ``n_corres``, ``n_seeds``, ``n_valid``, ``best_seed``, ``best_seed_count``,
+    ``refine_iterations_run`` (``pcr_sc2_info``).  Fewer than 3 rows or no valid seed: the empty result."""
+    fn = "registration_sc2_based_on_correspondence"
+    o = _sc2_option(fn, option)
+    _sc2_rows(fn, corres)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = len(source), len(target)
+    cd = _corres_device(fn, corres, ns, nt)
+    nc = int(cd.shape[0])
+    out = torch.empty((max(nc, 1), 2), dtype=torch.int32, device="cuda")
+    res, info = _lib.PcrResult(), _lib.PcrSc2Info()
+    ctx.check(ctx.lib.pcr_registration_sc2_correspondence(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), C.c_int64(nt),
+                                                          _ptr(cd), C.c_int64(nc), C.byref(o), C.byref(res), _ptr(out), C.byref(info)), fn)
+    r = _result(res, out)
+    r.info = {name: int(getattr(info, name)) for name, _ in _lib.PcrSc2Info._fields_}
+    return r
+
+
+def registration_sc2_based_on_feature_matching(source, target, source_feature, target_feature, option, mutual_filter=True, mutual_consistency_ratio=0.1):
+    """``correspondences_from_features(source_feature, target_feature, mutual_filter, mutual_consistency_ratio)`` followed by
+    ``registration_sc2_based_on_correspondence`` on that list."""
+    fn = "registration_sc2_based_on_feature_matching"
+    _sc2_option(fn, option)
+    if source_feature.num() != len(source) or target_feature.num() != len(target):
+        raise RuntimeError(f"{fn}: one feature row per point is required")
+    corres = correspondences_from_features(source_feature, target_feature, mutual_filter, mutual_consistency_ratio)
+    return registration_sc2_based_on_correspondence(source, target, corres, option)
+
+
+class SpatialCompatibility:
+    """The compatibility graph of a correspondence list (device tensors): ``bits`` (N, ceil(N / 64)) int64 -- bit b of word w of row i says
+    that rows i and 64 w + b preserve their distance within the threshold --, ``degrees`` int32 (compatible rows per row) and ``scores`` int64
+    (the second-order count: twice the triangles through the row)."""
+
+    def __init__(self, bits, degrees, scores):
+        self.bits, self.degrees, self.scores = bits, degrees, scores
+
+
+def spatial_compatibility(source, target, corres, inlier_threshold) -> SpatialCompatibility:
+    """First- and second-order spatial compatibility of a correspondence list (``pcr_spatial_compatibility``, include/pcr_hip.h): a row's
+    degree or score is a filter on its own, e.g. before ``registration_fgr_based_on_correspondence``.  At most 65536 rows."""
+    fn = "spatial_compatibility"
+    tau = _sc2_threshold(fn, inlier_threshold)
+    _sc2_rows(fn, corres)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = len(source), len(target)
+    cd = _corres_device(fn, corres, ns, nt)
+    nc = int(cd.shape[0])
+    bits = torch.zeros((nc, (nc + 63) // 64), dtype=torch.int64, device="cuda")
+    deg = torch.zeros((nc,), dtype=torch.int32, device="cuda")
+    score = torch.zeros((nc,), dtype=torch.int64, device="cuda")
+    ctx.check(ctx.lib.pcr_spatial_compatibility(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), C.c_int64(nt), _ptr(cd),
+                                                C.c_int64(nc), C.c_double(tau), _ptr(bits), _ptr(deg), _ptr(score)), fn)
+    return SpatialCompatibility(bits, deg, score)
+
+
+def debug_sc2_seeds(source, target, corres, option):
+    """Test hook ``pcr_debug_sc2_seeds``: per seed, in order, its row, the rows of K1 and K2 (-1 padded to 64), the 4 x 4 hypothesis, validity,
+    count and err2, as numpy arrays in a dict."""
+    fn = "debug_sc2_seeds"
+    o = _sc2_option(fn, option)
+    n = _sc2_rows(fn, corres)
+    ctx = _lib.Context.current()
+    torch = _torch()
+    ns, nt = len(source), len(target)
+    cd = _corres_device(fn, corres, ns, nt)
+    cap = max(1, min(max(1, int(o.seed_ratio * n)), o.max_seeds))
+    dev = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+    seed, k1, k2 = dev((cap,), torch.int32), dev((cap, 64), torch.int32), dev((cap, 64), torch.int32)
+    T, valid, cnt, err2 = dev((cap, 4, 4), torch.float64), dev((cap,), torch.uint8), dev((cap,), torch.int32), dev((cap,), torch.float64)
+    m = C.c_int64(0)
+    ctx.check(ctx.lib.pcr_debug_sc2_seeds(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), _ptr(target.device_xyz()), C.c_int64(nt), _ptr(cd),
+                                          C.c_int64(int(cd.shape[0])), C.byref(o), C.byref(m), _ptr(seed), _ptr(k1), _ptr(k2), _ptr(T), _ptr(valid), _ptr(cnt),
+                                          _ptr(err2)), fn)
+    k = m.value
+    return {"seeds": seed[:k].cpu().numpy(), "k1": k1[:k].cpu().numpy(), "k2": k2[:k].cpu().numpy(), "T": T[:k].cpu().numpy(),
+            "valid": valid[:k].cpu().numpy().astype(bool), "count": cnt[:k].cpu().numpy(), "err2": err2[:k].cpu().numpy()}
+
+
 # pose-graph slice of o3d.pipelines.registration (3_Global_Optimizations...py:292-358; host side, posegraph.py)
 from .posegraph import (GlobalOptimizationConvergenceCriteria, GlobalOptimizationLevenbergMarquardt,  # noqa: E402,F401
                         GlobalOptimizationOption, PoseGraph, PoseGraphEdge, PoseGraphNode, global_optimization)
