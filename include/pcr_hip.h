@@ -443,8 +443,8 @@ int pcr_voxel_map_grid(const pcr_voxel_map *map, double *grid_min3, double *orig
  * LOOP.  RegistrationICP's, as in the voxelized GICP section: rows at init, then update / left-multiply / rows, until |d fitness| <
  *   relative_fitness and |d RMSE| < relative_rmse, or max_iteration.  fitness = (source points with at least one row) / n_src,
  *   inlier_rmse = sqrt(sum over the rows of |q_i - mu_v|^2 / rows), n_correspondences = the number of rows.  The loop does not use the score.
- * All cloud and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed and is never changed;
- * any context on the same device may use it for any number of calls. */
+ * All cloud and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed and changes only through
+ * the calls of "A normal-distributions map that grows" below; any context on the same device may use it for any number of calls. */
 typedef struct pcr_ndt_map pcr_ndt_map;
 typedef struct {
     double relative_fitness;
@@ -466,7 +466,8 @@ int pcr_ndt_map_size(const pcr_ndt_map *map, int64_t *cells);
  * cov6 (cells x 6 float32: C_v), info6 (cells x 6 float64: A_v), valid (cells uint8).  Asynchronous on the context's stream. */
 int pcr_ndt_map_read(pcr_context *ctx, const pcr_ndt_map *map, int32_t *cell3, int32_t *count, float *mean3, float *cov6, double *info6,
                      uint8_t *valid);
-/* the grid of a map, each output optional (host): origin3 = the target's minimum - voxel_size / 2, voxel_size */
+/* the grid of a map, each output optional (host): origin3 = grid_min - voxel_size / 2 (grid_min: the target's minimum, or what
+ * pcr_ndt_map_create_on_grid was given; pcr_ndt_map_rule reads it), voxel_size */
 int pcr_ndt_map_grid(const pcr_ndt_map *map, double *origin3, double *voxel_size);
 /* the rows (i, v) of the rule at the pose T: rows2 = int32 pairs, capacity n_src x neighborhood rows; *n_rows on the host.  A neighborhood that is
  * not 1, 7 or 27, a non-finite value in src_xyz / T, a map on another device than the context: PCR_EINVAL naming the argument. */
@@ -482,6 +483,50 @@ int pcr_ndt_linearize(pcr_context *ctx, const pcr_ndt_map *map, const float *src
  * init_T, fitness 0.  correspondences: optional device int32, capacity n_src x neighborhood rows: the rows at the returned pose. */
 int pcr_registration_ndt(pcr_context *ctx, const float *src_xyz, int64_t n_src, const pcr_ndt_map *map, const double *init_T,
                          const pcr_ndt_params *params, pcr_result *result, int32_t *correspondences);
+
+/* A normal-distributions map that grows (pcr_ndt_map_create_on_grid / _insert / _merge / _remove_far).  PCL and ndt_omp rebuild their target
+ * grid; this is the specification of these calls.  All arithmetic is float64 on float32 inputs, every operation rounded once, no fused
+ * multiply-add.
+ * RULE OF A MAP.  A map carries voxel_size, grid_min g (three float64; its origin is g - voxel_size / 2 per axis in float64, the GRID rule of the
+ *   voxel covariance map), min_points_per_voxel and eigenvalue_ratio.  A map made by pcr_ndt_map_create has g = the target's minimum.  Two maps are
+ *   compatible iff all four are equal bit for bit.  In every row of every map, validity and A_v are a pure function of
+ *   (N_v, C_v, min_points_per_voxel, eigenvalue_ratio): the one MAP states.
+ * MAP ON A GIVEN GRID, AT A POSE.  Input: n >= 1 points, a rule, and an optional pose T (float64 4x4, row-major; none is the identity, applied all
+ *   the same).  Member point: p' = float32(q) with q the float64 expression of ROWS, ((T_r0 x + T_r1 y) + T_r2 z) + T_r3.  The result is exactly
+ *   MAP of this section over p' on the given grid: counts, float32 means, C_v, validity, A_v, Morton order.  A member whose cell index lies outside
+ *   [0, 2^21) on any axis -- below the origin counts too -- is PCR_EINVAL: xyz lies outside the map's grid; nothing is changed.  With the cloud's
+ *   own minimum as grid_min and no pose the result is that of pcr_ndt_map_create row for row and bit for bit.
+ * MERGE(A, B).  A and B are compatible (otherwise PCR_EINVAL).  One row per cell occupied in A or in B, in Morton order.  A cell in only one of them
+ *   keeps that row bit for bit: count, mean, C_v, A_v, validity.  A cell in both gets N = N_a + N_b (a sum above 2^31 - 1 is PCR_EINVAL and nothing
+ *   is changed) and, per channel of the mean, mu = float32((float64(N_a) a + float64(N_b) b) / float64(N)): the two products, the sum, the
+ *   division, one rounding to float32 -- the mean rule of the voxel covariance map's MERGE.  The covariances are taken about two different means, so
+ *   they are moved to the new one by the parallel-axis term: with d_a = float64(mu_a) - float64(mu), d_b likewise and mu the NEW float32 mean,
+ *   each channel rc of xx, xy, xz, yy, yz, zz is M_a = float64(C_a[rc]) + d_a[r] d_a[c] (the product rounded first, then the sum), M_b likewise,
+ *   and C[rc] = float32((float64(N_a) M_a + float64(N_b) M_b) / float64(N)).  Validity and A_v of the merged cell are those of MAP from (N, C):
+ *   A_v is recomputed, never averaged.  MERGE is commutative bit for bit (only sums and products swap their operands); it is not associative.
+ * INSERT(map, cloud, T) = MERGE(map, the map of the cloud at T on the map's grid with the map's rule).
+ * REMOVE_FAR(map, center c (float64 x3), max_distance r).  The voxel covariance map's rule on the float32 means: a row is kept iff d^2 < r^2
+ *   (strict), d^2 in float64 by differences, squares and sums in the order x, y, z, and r^2 = r r.  Kept rows keep all their bits, A_v included,
+ *   and their relative order.  A map never has zero rows: an operation that would leave none is PCR_EINVAL (would leave the map empty).
+ * _insert, _merge and _remove_far change the map, all or nothing and finished when they return: the new block with its cell hash is built, swapped
+ * in, and the old one freed (which waits for the device); on any error the map is exactly as before.  While such a call runs no other call may
+ * use the map, and map rows in an earlier correspondence set are stale afterwards (row indices change). */
+/* The map of a cloud on the grid (grid_min3, voxel_size) at the pose T (MAP ON A GIVEN GRID; T optional: NULL is the identity).  The arguments of
+ * pcr_ndt_map_create and their refusals, plus: a non-finite value in grid_min3 or T (named), a member outside the grid (xyz lies outside the
+ * map's grid).  Finished when it returns. */
+int pcr_ndt_map_create_on_grid(pcr_context *ctx, const float *xyz, int64_t n, double voxel_size, int min_points_per_voxel, double eigenvalue_ratio,
+                               const double *grid_min3, const double *T, pcr_ndt_map **out);
+/* map <- INSERT(map, cloud, T); T optional.  A NULL map, a map on another device than the context, the cloud refusals of the call above. */
+int pcr_ndt_map_insert(pcr_context *ctx, pcr_ndt_map *map, const float *xyz, int64_t n, const double *T);
+/* map <- MERGE(map, other); other is unchanged.  other == map (itself), a NULL map, maps on another device, on different grids (not on the map's
+ * grid) or with another min_points_per_voxel / eigenvalue_ratio (does not follow the map's rule): PCR_EINVAL. */
+int pcr_ndt_map_merge(pcr_context *ctx, pcr_ndt_map *map, const pcr_ndt_map *other);
+/* map <- REMOVE_FAR(map, center3, max_distance); *removed (optional, host) = rows dropped.  A non-finite center3, a max_distance that is not
+ * finite or <= 0: PCR_EINVAL naming the argument. */
+int pcr_ndt_map_remove_far(pcr_context *ctx, pcr_ndt_map *map, const double *center3, double max_distance, int64_t *removed);
+/* the rule of a map, each output optional (host): grid_min3 (origin3 of pcr_ndt_map_grid = grid_min3 - voxel_size / 2), min_points_per_voxel,
+ * eigenvalue_ratio */
+int pcr_ndt_map_rule(const pcr_ndt_map *map, double *grid_min3, int *min_points_per_voxel, double *eigenvalue_ratio);
 
 /* == the whole body of Multiscale_GICP (ALL_FUNCTIONS.py:286-312 / 2_MGICP...py:140-163), device resident:
  * per scale voxel_down_sample -> remove_statistical_outlier(sor_k, sor_std) -> estimate_normals(KNN normal_k)

@@ -172,6 +172,7 @@ EXPORTS = [
     "pcr_multiway_create", "pcr_multiway_destroy", "pcr_multiway_linearize",
     "pcr_ndt_map_create", "pcr_ndt_map_destroy", "pcr_ndt_map_size", "pcr_ndt_map_read", "pcr_ndt_map_grid", "pcr_ndt_map_correspondences",
     "pcr_ndt_linearize", "pcr_registration_ndt",
+    "pcr_ndt_map_create_on_grid", "pcr_ndt_map_insert", "pcr_ndt_map_merge", "pcr_ndt_map_remove_far", "pcr_ndt_map_rule",
     "pcr_registration_sc2_correspondence", "pcr_spatial_compatibility", "pcr_debug_sc2_seeds",
 ]
 
@@ -240,6 +241,12 @@ QUERY_PROTOTYPES = {
     "pcr_ndt_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                            C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
     "pcr_registration_ndt": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(PcrNdtParams), C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_ndt_map_create_on_grid": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_ndt_map_insert": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)], C.c_int),
+    "pcr_ndt_map_merge": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_ndt_map_remove_far": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_ndt_map_rule": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
     "pcr_registration_sc2_correspondence": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrSc2Option),
                                              C.POINTER(PcrResult), C.c_void_p, C.POINTER(PcrSc2Info)], C.c_int),
     "pcr_spatial_compatibility": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,

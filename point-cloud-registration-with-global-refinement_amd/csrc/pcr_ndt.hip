@@ -5,7 +5,9 @@
 //                  of level 0 inside the map's own allocation; k_ndt_member forms the six products of every member against its cell's float32
 //                  mean, found through that hash, as two 3-vectors that ride in the attribute slot of two more voxel passes (the same keys, the
 //                  same stable sort: row v of all three passes is the same cell) and counts the members; k_ndt_cell lays the rows out and
-//                  computes A_v with a float64 Jacobi eigen-solve
+//                  computes A_v with a float64 Jacobi eigen-solve (ndt_cell_information, pcr_ndt.h).  One builder, ndt_map_build, on the
+//                  cloud's own grid or on a given one, with the members as they lie or placed at a pose (k_ndt_place): pcr_ndt_map_create and
+//                  the calls of pcr_nmap.hip (the map that grows) all make their rows through it
 //   k_icp_iter_ndt the whole iteration, a sibling of k_icp_iter_vgicp: one lane per source point, 1 / 7 / 27 hash probes, per hit one gather of
 //                  (mean, +-N_v) and one of A_v (80 B with the probe), the row added straight into the 30 sums that icp_finish reduces
 //   k_ndt_lin      the same row plus the score for one pose, with a reduction of its own in a fixed order
@@ -14,36 +16,10 @@
 #include <cmath>
 #include <cstring>
 #include "pcr_icp_loop.h"
-#include "pcr_vgicp.h"
+#include "pcr_ndt.h"
 
 #define NDT_BS 256
 #define NDT_NL 32                      // sums of the linearisation: the loop's 30, the score, one unused
-
-// One map row per occupied cell, in Morton order of the cell: mean4[v] = (mean, w = bit pattern of +N_v for a valid cell and of -N_v for an invalid
-// one), info6[6 v ...] = A_v (xx,xy,xz,yy,yz,zz; zero for an invalid cell), cov8[2 v], cov8[2 v + 1] = C_v as in VgicpMapView; `tab`: cell -> (row, 1)
-struct NdtMapView {
-    const GridEntry *tab; const unsigned *dmask;
-    const float4 *mean4, *cov8;
-    const double *info6;
-    double org[3], voxel;
-};
-struct pcr_ndt_map {
-    int device = 0;
-    int64_t cells = 0;
-    char *block = nullptr;       // the one allocation: rows, keys, count word, cell hash
-    size_t bytes = 0;
-    NdtMapView view;
-    uint64_t *keys = nullptr;    // Morton keys of the rows (ascending)
-    int *n_dev = nullptr;
-};
-static inline size_t ndt_block_bytes(int64_t cells) {
-    return (size_t)cells * (sizeof(float4) * 3 + sizeof(double) * 6 + sizeof(uint64_t)) + (size_t)pcr_grid_slots((unsigned)cells) * sizeof(GridEntry) + 16 * 256;
-}
-__device__ static inline VgicpMapView ndt_hash(const NdtMapView &m) {      // what vg_row reads of a map
-    VgicpMapView g;
-    g.tab = m.tab; g.dmask = m.dmask; g.mean4 = m.mean4; g.cov8 = m.cov8;
-    return g;
-}
 
 // ================================================================ the row
 // Row (i, v) of UPDATE: delta = q - mu, m = delta^T A delta, e = exp(-d2 m / 2), w = -d1 d2 e, J = [S | I] with S = -skew(q).  With B = A J = [A S | A]
@@ -258,65 +234,35 @@ __global__ void __launch_bounds__(NDT_BS) k_ndt_member(const float *__restrict__
     lo3[(size_t)i * 3] = l0; lo3[(size_t)i * 3 + 1] = l1; lo3[(size_t)i * 3 + 2] = l2;
     hi3[(size_t)i * 3] = h0; hi3[(size_t)i * 3 + 1] = h1; hi3[(size_t)i * 3 + 2] = h2;
 }
-// ---- one lane per cell: the row, and A_v = V diag(1 / max(lambda_k, ratio lambda_max)) V^T of S_v = C_v N_v / (N_v - 1) by cyclic Jacobi sweeps in
-// float64 (the sweeps of vg_sym3_inv_sqrt, pcr_vgicp.hip).  The clamp bounds the condition number of A_v by 1 / ratio, so the rounding of the
-// eigenvectors of clamped (nearly equal after the clamp) eigenvalues does not show in A_v.
+// ---- one lane per cell: the row, with validity and A_v by ndt_cell_information (pcr_ndt.h)
 __global__ void __launch_bounds__(NDT_BS) k_ndt_cell(const float4 *__restrict__ mean, const float4 *__restrict__ lo, const float4 *__restrict__ hi,
                                                      const int *__restrict__ count, int cells, int min_points, double ratio,
                                                      float4 *__restrict__ mean4, float4 *__restrict__ cov8, double *__restrict__ info6) {
 #pragma clang fp contract(off)
     const int v = blockIdx.x * NDT_BS + threadIdx.x;
     if (v >= cells) return;
-    const float4 p = mean[v], c0 = lo[v], c1 = hi[v];
+    const float4 p = mean[v], l = lo[v], h = hi[v];
     const int nv = count[v];
-    cov8[2 * (size_t)v] = make_float4(c0.x, c0.y, c0.z, c1.x);
-    cov8[2 * (size_t)v + 1] = make_float4(c1.y, c1.z, 0.0f, 0.0f);
-    double A6[6] = {0, 0, 0, 0, 0, 0};
-    bool valid = false;
-    if (nv >= min_points && nv >= 2) {
-        const double N = (double)nv, N1 = N - 1.0;
-        const double sxx = (double)c0.x * N / N1, sxy = (double)c0.y * N / N1, sxz = (double)c0.z * N / N1, syy = (double)c1.x * N / N1, syz = (double)c1.y * N / N1,
-                     szz = (double)c1.z * N / N1;
-        double a[9] = {sxx, sxy, sxz, sxy, syy, syz, sxz, syz, szz}, V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int sweep = 0; sweep < 64; sweep++) {
-            double off = a[1] * a[1]; off = off + a[2] * a[2]; off = off + a[5] * a[5];
-            double diag = a[0] * a[0]; diag = diag + a[4] * a[4]; diag = diag + a[8] * a[8];
-            if (off <= 1e-300 || off <= 1e-34 * diag) break;
-#pragma unroll
-            for (int pq = 0; pq < 3; pq++) {
-                const int p_ = pq == 2 ? 1 : 0, q_ = pq == 0 ? 1 : 2;
-                const double apq = a[p_ * 3 + q_];
-                if (apq != 0.0) {
-                    const double theta = (a[q_ * 3 + q_] - a[p_ * 3 + p_]) / (2.0 * apq);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { const double akp = a[k * 3 + p_], akq = a[k * 3 + q_]; a[k * 3 + p_] = c * akp - sn * akq; a[k * 3 + q_] = sn * akp + c * akq; }
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { const double apk = a[p_ * 3 + k], aqk = a[q_ * 3 + k]; a[p_ * 3 + k] = c * apk - sn * aqk; a[q_ * 3 + k] = sn * apk + c * aqk; }
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { const double vkp = V[k * 3 + p_], vkq = V[k * 3 + q_]; V[k * 3 + p_] = c * vkp - sn * vkq; V[k * 3 + q_] = sn * vkp + c * vkq; }
-                }
-            }
-        }
-        const double lmax = fmax(a[0], fmax(a[4], a[8]));
-        if (lmax > 0.0 && isfinite(lmax)) {
-            valid = true;
-            const double fl = ratio * lmax;
-            const double i0 = 1.0 / fmax(a[0], fl), i1 = 1.0 / fmax(a[4], fl), i2 = 1.0 / fmax(a[8], fl);
-            int t = 0;
-#pragma unroll
-            for (int r = 0; r < 3; r++)
-#pragma unroll
-                for (int c = r; c < 3; c++) {
-                    double s = V[r * 3] * V[c * 3] * i0; s = s + V[r * 3 + 1] * V[c * 3 + 1] * i1; s = s + V[r * 3 + 2] * V[c * 3 + 2] * i2;
-                    A6[t++] = s;
-                }
-        }
-    }
+    const float4 c0 = make_float4(l.x, l.y, l.z, h.x), c1 = make_float4(h.y, h.z, 0.0f, 0.0f);
+    cov8[2 * (size_t)v] = c0;
+    cov8[2 * (size_t)v + 1] = c1;
+    double A6[6];
+    const bool valid = ndt_cell_information(nv, c0, c1, min_points, ratio, A6);
     mean4[v] = make_float4(p.x, p.y, p.z, __int_as_float(valid ? nv : -nv));
 #pragma unroll
     for (int t = 0; t < 6; t++) info6[6 * (size_t)v + t] = A6[t];
+}
+// ---- p' = float32(q) with q the ROWS expression (vg_transform), the point half of k_vmap_place; bad: set when a placed coordinate is not finite
+struct NdtPlace { double T[12]; };
+__global__ void __launch_bounds__(NDT_BS) k_ndt_place(const float *__restrict__ xyz, int n, NdtPlace pose, float *__restrict__ out_xyz, int *__restrict__ bad) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * NDT_BS + threadIdx.x;
+    if (i >= n) return;
+    double qx, qy, qz;
+    vg_transform(pose.T, xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2], qx, qy, qz);
+    const float px = (float)qx, py = (float)qy, pz = (float)qz;
+    out_xyz[(size_t)i * 3] = px; out_xyz[(size_t)i * 3 + 1] = py; out_xyz[(size_t)i * 3 + 2] = pz;
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) atomicOr(bad, 1);
 }
 __global__ void __launch_bounds__(NDT_BS) k_ndt_read(const uint64_t *__restrict__ keys, NdtMapView m, int cells, int32_t *__restrict__ cell3, int32_t *__restrict__ count,
                                                      float *__restrict__ mean3, float *__restrict__ cov6, double *__restrict__ info6, uint8_t *__restrict__ valid) {
@@ -365,7 +311,7 @@ __global__ void __launch_bounds__(NDT_BS) k_ndt_emit(const int32_t *__restrict__
 
 static unsigned ndt_blocks(size_t n) { return (unsigned)((n + NDT_BS - 1) / NDT_BS); }
 
-static int ndt_check_map(pcr_context *ctx, const pcr_ndt_map *map, const char *call) {
+int ndt_check_map(pcr_context *ctx, const pcr_ndt_map *map, const char *call) {
     if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
     if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
     return PCR_OK;
@@ -389,22 +335,46 @@ static int ndt_score(pcr_context *ctx, const char *call, double outlier_ratio, d
     return PCR_OK;
 }
 
-extern "C" int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n, double voxel_size, int min_points_per_voxel, double eigenvalue_ratio, pcr_ndt_map **out) {
-    return pcr_api_call(ctx, [&]() -> int {
-    const char *call = "ndt_map_create";
-    if (!out) { ctx->err = "ndt_map_create: out is null"; return PCR_EINVAL; }
+int ndt_map_build(pcr_context *ctx, const char *call, const float *xyz, int64_t n, double voxel_size, int min_points_per_voxel, double eigenvalue_ratio,
+                  const double *grid_min3, const double *T, pcr_ndt_map **out) {
+    const std::string who(call);
+    if (!out) { ctx->err = who + ": out is null"; return PCR_EINVAL; }
     *out = nullptr;
-    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) { ctx->err = "ndt_map_create: voxel_size <= 0"; return PCR_EINVAL; }
-    if (min_points_per_voxel < 2) { ctx->err = "ndt_map_create: min_points_per_voxel < 2"; return PCR_EINVAL; }
-    if (!(eigenvalue_ratio > 0.0) || !(eigenvalue_ratio <= 1.0)) { ctx->err = "ndt_map_create: eigenvalue_ratio must lie in (0, 1]"; return PCR_EINVAL; }
-    if (n < 1 || n > 0x7fffffff / 8 || !xyz) { ctx->err = "ndt_map_create: xyz must hold 1 .. 2^28 - 1 points"; return PCR_EINVAL; }
-    PCR_TRY(pcr_arena_reserve(ctx, 3 * pcr_scratch_bytes_for(n) + (size_t)n * 96));
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) { ctx->err = who + ": voxel_size <= 0"; return PCR_EINVAL; }
+    if (min_points_per_voxel < 2) { ctx->err = who + ": min_points_per_voxel < 2"; return PCR_EINVAL; }
+    if (!(eigenvalue_ratio > 0.0) || !(eigenvalue_ratio <= 1.0)) { ctx->err = who + ": eigenvalue_ratio must lie in (0, 1]"; return PCR_EINVAL; }
+    if (n < 1 || n > 0x7fffffff / 8 || !xyz) { ctx->err = who + ": xyz must hold 1 .. 2^28 - 1 points"; return PCR_EINVAL; }
+    PCR_TRY(pcr_arena_reserve(ctx, 3 * pcr_scratch_bytes_for(n) + (size_t)n * 112 + 4096));
     {
         const float *ptr[1] = {xyz}; const size_t cnt[1] = {(size_t)n * 3}; const char *name[1] = {"xyz"};
         PCR_TRY(vg_check_finite(ctx, call, ptr, cnt, name, 1));
     }
+    int *bad = nullptr;
+    if (T) {      // the members at the pose
+        float *placed = arena<float>(ctx, (size_t)n * 3);
+        bad = arena<int>(ctx, 1);
+        if (!placed || !bad) return PCR_ENOMEM;
+        NdtPlace pose; memcpy(pose.T, T, sizeof pose.T);
+        PCR_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+        PCR_LAUNCH(ctx, k_ndt_place, dim3(ndt_blocks((size_t)n)), dim3(NDT_BS), 0, ctx->stream, xyz, (int)n, pose, placed, bad);
+        xyz = placed;
+    }
     double b6[6];
     PCR_TRY(pcr_dev_bounds(ctx, xyz, n, b6));
+    if (grid_min3) {
+        // both ends of the members against the grid before any key is formed (k_voxel_keys has no defence against a negative index); the voxel pass
+        // then runs with grid_min3 in place of the members' minimum
+        int64_t nonfinite = 0;
+        if (bad) PCR_TRY(pcr_read_count(ctx, bad, &nonfinite));
+        bool inside = nonfinite == 0;
+        for (int d = 0; d < 3 && inside; d++) {
+            const double org = grid_min3[d] - voxel_size * 0.5;
+            const double lo = floor((b6[d] - org) / voxel_size), hi = floor((b6[3 + d] - org) / voxel_size);
+            inside = lo >= 0.0 && hi < 2097152.0;
+        }
+        if (!inside) { ctx->err = who + ": xyz lies outside the map's grid (cell indices must stay in [0, 2^21) on every axis)"; return PCR_EINVAL; }
+        for (int d = 0; d < 3; d++) b6[d] = grid_min3[d];
+    }
     float *lo3 = arena<float>(ctx, (size_t)n * 3), *hi3 = arena<float>(ctx, (size_t)n * 3);
     if (!lo3 || !hi3) return PCR_ENOMEM;
     // the voxel pass three times over the same points: the same keys, the same stable sort, so row v of every pass is the same cell
@@ -415,10 +385,12 @@ extern "C" int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n,
     PCR_TRY(pcr_dev_voxel(ctx, xyz, nullptr, n, b6, voxel_size, &vm));
     int64_t cells = 0;
     PCR_TRY(pcr_read_count(ctx, vm.n, &cells));
-    if (cells < 1 || cells > n) { ctx->err = "ndt_map_create: the voxel pass returned no cells"; return PCR_EHIP; }
+    if (cells < 1 || cells > n) { ctx->err = who + ": the voxel pass returned no cells"; return PCR_EHIP; }
 
     pcr_ndt_map *m = new pcr_ndt_map();
     m->device = ctx->device; m->cells = cells;
+    for (int d = 0; d < 3; d++) m->grid_min[d] = b6[d];
+    m->min_points = min_points_per_voxel; m->ratio = eigenvalue_ratio;
     auto build = [&]() -> int {
         m->bytes = ndt_block_bytes(cells);
         if (hipMalloc((void **)&m->block, m->bytes) != hipSuccess) { m->block = nullptr; ctx->err = "hipMalloc(ndt map)"; return PCR_ENOMEM; }
@@ -436,7 +408,7 @@ extern "C" int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n,
             const DevCloud *pmc = &mc; const int level = 0;
             PCR_TRY(pcr_dev_build_grid_batch(ctx, &pmc, &level, 1, &gv));
         }
-        if (!gv.tab) { ctx->err = "ndt_map_create: no cell hash"; return PCR_EHIP; }
+        if (!gv.tab) { ctx->err = who + ": no cell hash"; return PCR_EHIP; }
         m->view.tab = gv.tab; m->view.dmask = gv.dmask; m->view.mean4 = mean4; m->view.cov8 = cov8; m->view.info6 = info6;
         for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
         m->view.voxel = voxel_size;
@@ -450,12 +422,18 @@ extern "C" int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n,
                    (const int *)count, (int)cells, min_points_per_voxel, eigenvalue_ratio, mean4, cov8, info6);
         // finished before the call returns: the caller may overwrite its buffers, and any context may use the map
         PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->launch_err != hipSuccess) return PCR_EHIP;      // (pcr_leave names the launch)
         return PCR_OK;
     };
     const int rc = build();
     if (rc != PCR_OK) { if (m->block) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(m->block); } delete m; return rc; }
     *out = m;
     return PCR_OK;
+}
+
+extern "C" int pcr_ndt_map_create(pcr_context *ctx, const float *xyz, int64_t n, double voxel_size, int min_points_per_voxel, double eigenvalue_ratio, pcr_ndt_map **out) {
+    return pcr_api_call(ctx, [&]() -> int {
+    return ndt_map_build(ctx, "ndt_map_create", xyz, n, voxel_size, min_points_per_voxel, eigenvalue_ratio, nullptr, nullptr, out);
     });
 }
 

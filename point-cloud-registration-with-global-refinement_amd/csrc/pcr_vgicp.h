@@ -70,6 +70,21 @@ __device__ static inline int vg_row(const VgicpMapView &m, unsigned mask, int x,
     const int2 r = pcr_grid_lookup(g, mask, x, y, z);
     return r.y > 0 ? r.x : -1;
 }
+// what the maps that grow share (pcr_vmap.hip, pcr_nmap.hip): first index of the ascending keys[0, n) that is not below key, the search of MERGE ...
+__device__ static inline int vg_lower_bound(const uint64_t *__restrict__ keys, int n, uint64_t key) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// ... and REMOVE_FAR's test d^2 < r^2 with d^2 in float64 from the float32 mean: differences, squares and sums in the order x, y, z, each rounded once
+__device__ static inline bool vg_within(const float4 p, double cx, double cy, double cz, double r2) {
+#pragma clang fp contract(off)
+    const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    double d2 = xx + yy;
+    d2 = d2 + zz;
+    return d2 < r2;
+}
 // c = a b and c = a b^T of row-major 3x3 matrices, every entry (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j with its zero terms and without contraction: the
 // oracle's m3_mul / m3_mul_bt
 __device__ static inline void vg_mul3(const double *a, const double *b, double *c) {

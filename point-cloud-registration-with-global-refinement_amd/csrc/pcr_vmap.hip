@@ -45,13 +45,6 @@ __global__ void __launch_bounds__(VM_BS) k_vmap_place(const float *__restrict__ 
     hi3[(size_t)i * 3] = (float)Cr[4]; hi3[(size_t)i * 3 + 1] = (float)Cr[5]; hi3[(size_t)i * 3 + 2] = (float)Cr[8];
 }
 
-// first index of the ascending keys[0, n) that is not below key
-__device__ static inline int vm_lower_bound(const uint64_t *__restrict__ keys, int n, uint64_t key) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // the Morton key of every point's cell on the map's grid (k_voxel_keys' float64 expression; the caller has checked that no index is negative or
 // past 2^21) and the point's index as the value the stable sort carries
 __global__ void __launch_bounds__(VM_BS) k_vmap_keys(const float *__restrict__ xyz, int n, double ox, double oy, double oz, double voxel,
@@ -97,10 +90,10 @@ __global__ void __launch_bounds__(VM_BS) k_vmap_cell_rows(const float *__restric
 __global__ void __launch_bounds__(VM_BS) k_vmap_merge_mark(VmRows a, VmRows b, int *__restrict__ where, uint8_t *__restrict__ only_b, int *__restrict__ overflow) {
     const int t = blockIdx.x * VM_BS + threadIdx.x;
     if (t >= a.n + b.n) return;
-    if (t < a.n) { where[t] = vm_lower_bound(b.keys, b.n, a.keys[t]); return; }
+    if (t < a.n) { where[t] = vg_lower_bound(b.keys, b.n, a.keys[t]); return; }
     const int j = t - a.n;
     const uint64_t key = b.keys[j];
-    const int i = vm_lower_bound(a.keys, a.n, key);
+    const int i = vg_lower_bound(a.keys, a.n, key);
     const bool shared = i < a.n && a.keys[i] == key;
     where[t] = i;
     only_b[j] = shared ? 0 : 1;
@@ -146,17 +139,11 @@ __global__ void __launch_bounds__(VM_BS) k_vmap_merge_write(VmRows a, VmRows b, 
     mean4[o] = m; cov8[2 * (size_t)o] = c0; cov8[2 * (size_t)o + 1] = c1; keys[o] = key;
 }
 
-// keep[v] = d^2 < r^2 with d^2 in float64 from the float32 mean: differences, squares and sums in the order x, y, z, each rounded once
+// keep[v] = d^2 < r^2 (vg_within, pcr_vgicp.h)
 __global__ void __launch_bounds__(VM_BS) k_vmap_far_flags(const float4 *__restrict__ mean4, int n, double cx, double cy, double cz, double r2, uint8_t *__restrict__ keep) {
-#pragma clang fp contract(off)
     const int v = blockIdx.x * VM_BS + threadIdx.x;
     if (v >= n) return;
-    const float4 p = mean4[v];
-    const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
-    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    double d2 = xx + yy;
-    d2 = d2 + zz;
-    keep[v] = d2 < r2 ? 1 : 0;
+    keep[v] = vg_within(mean4[v], cx, cy, cz, r2) ? 1 : 0;
 }
 __global__ void __launch_bounds__(VM_BS) k_vmap_gather(VmRows a, const uint8_t *__restrict__ keep, const int *__restrict__ pos, int cap, float4 *__restrict__ mean4,
                                                        float4 *__restrict__ cov8, uint64_t *__restrict__ keys) {

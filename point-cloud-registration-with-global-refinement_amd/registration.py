@@ -741,27 +741,124 @@ class NormalDistributionsMap:
     ``voxel_down_sample``'s grid the member count, the mean, the covariance ``C_v`` of the member positions about it and -- for a cell with at
     least ``min_points_per_voxel`` members that do not coincide -- the float64 information matrix ``A_v``, the inverse of the sample covariance
     with its eigenvalues raised to ``eigenvalue_ratio`` times the largest.  Built once from the target's positions alone (no normals, no
-    covariances) and good for any number of registrations until ``close()``.  Rows are in Morton order of the cell index.  The map does not
-    grow: build a new one."""
+    covariances) and good for any number of registrations until ``close()``.  Rows are in Morton order of the cell index.
+
+    ``NormalDistributionsMap(target, voxel_size)`` takes the grid from the target's own minimum, so nothing below that minimum can ever be
+    added.  A map that will grow is made by ``NormalDistributionsMap.on_grid(target, voxel_size, grid_min=centered_grid_min(point,
+    voxel_size))``, whose grid has ``point`` in its middle; then ``insert`` adds a scan at a pose, ``merge`` adds another map of the same grid
+    and rule, and ``remove_far`` drops the cells far from a point (RULE OF A MAP / MERGE / INSERT / REMOVE_FAR of include/pcr_hip.h).  A cell
+    held by both sides of a merge gets the summed count, the count-weighted mean, the covariances moved to that mean by the parallel-axis term,
+    and its validity and ``A_v`` computed anew -- so cells too thin after one scan become valid as scans accumulate.  Each of these calls
+    replaces the rows as a whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call may use the map while
+    one runs.  ``len(map)`` and every property read the map as it is after the call."""
 
     _handle = None
 
     def __init__(self, target: PointCloud, voxel_size: float, min_points_per_voxel: int = 6, eigenvalue_ratio: float = 0.01):
+        self._create(target, voxel_size, min_points_per_voxel, eigenvalue_ratio, None, None)
+
+    @classmethod
+    def on_grid(cls, target: PointCloud, voxel_size: float, min_points_per_voxel: int = 6, eigenvalue_ratio: float = 0.01, grid_min=None, transformation=None):
+        """The map of ``target`` placed at ``transformation`` (4x4; ``None``: as it lies) on the grid whose origin is
+        ``grid_min - voxel_size / 2`` (``pcr_ndt_map_create_on_grid``).  With both ``None`` this is
+        ``NormalDistributionsMap(target, voxel_size, min_points_per_voxel, eigenvalue_ratio)``, through the same call and with the same bits; a
+        pose needs a ``grid_min``.  A point outside the grid's 2^21 cells per axis -- below ``grid_min - voxel_size / 2`` too -- raises the
+        library's error."""
+        m = cls.__new__(cls)
+        m._create(target, voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, transformation)
+        return m
+
+    @staticmethod
+    def centered_grid_min(point, voxel_size) -> np.ndarray:
+        """``VoxelCovarianceMap.centered_grid_min``: the ``grid_min`` of a grid with ``point`` in the middle of its 2^21 cells per axis."""
+        return VoxelCovarianceMap.centered_grid_min(point, voxel_size)
+
+    def _create(self, target, voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, transformation):
         fn = "NormalDistributionsMap"
         self._voxel_size = _check_voxel_size(fn, voxel_size)
         _check_ndt_rule(fn, min_points_per_voxel=min_points_per_voxel, eigenvalue_ratio=eigenvalue_ratio)
         self.min_points_per_voxel, self.eigenvalue_ratio = int(min_points_per_voxel), float(eigenvalue_ratio)
         if not isinstance(target, PointCloud) or len(target) == 0:
             raise RuntimeError(f"{fn}: the target must be a PointCloud with at least one point")
+        T, Tp = VoxelCovarianceMap._pose(fn, transformation)
+        g = None
+        if grid_min is not None:
+            g = np.ascontiguousarray(np.asarray(grid_min, np.float64).reshape(-1))
+            if g.shape != (3,):
+                raise ValueError(f"{fn}: grid_min must hold three numbers, got {grid_min!r}")
+        if g is None and T is not None:
+            raise ValueError(f"{fn}: a transformation needs a grid_min (the placed target's minimum is not known before the call)")
         ctx = _lib.Context.current()
         h = C.c_void_p()
-        ctx.check(ctx.lib.pcr_ndt_map_create(ctx.handle, _ptr(target.device_xyz()), C.c_int64(len(target)), C.c_double(self._voxel_size),
-                                             C.c_int(self.min_points_per_voxel), C.c_double(self.eigenvalue_ratio), C.byref(h)), fn)
+        if g is None:
+            ctx.check(ctx.lib.pcr_ndt_map_create(ctx.handle, _ptr(target.device_xyz()), C.c_int64(len(target)), C.c_double(self._voxel_size),
+                                                 C.c_int(self.min_points_per_voxel), C.c_double(self.eigenvalue_ratio), C.byref(h)), fn)
+        else:
+            ctx.check(ctx.lib.pcr_ndt_map_create_on_grid(ctx.handle, _ptr(target.device_xyz()), C.c_int64(len(target)), C.c_double(self._voxel_size),
+                                                         C.c_int(self.min_points_per_voxel), C.c_double(self.eigenvalue_ratio),
+                                                         g.ctypes.data_as(C.POINTER(C.c_double)), Tp, C.byref(h)), fn)
         self._handle = h
         self._lib = ctx.lib
+        self._refresh()
+
+    def _refresh(self):
         m = C.c_int64(0)
-        self._lib.pcr_ndt_map_size(h, C.byref(m))
+        self._lib.pcr_ndt_map_size(self._handle, C.byref(m))
         self._cells = int(m.value)
+
+    @property
+    def grid_min(self) -> np.ndarray:
+        """(3,) float64: g of the RULE OF A MAP; for a map made without ``grid_min`` the target's minimum"""
+        h = self._open()
+        g = (C.c_double * 3)()
+        self._lib.pcr_ndt_map_rule(h, g, None, None)
+        return np.array(g, np.float64)
+
+    def insert(self, cloud: PointCloud, transformation=None):
+        """Add ``cloud`` placed at ``transformation`` (``pcr_ndt_map_insert``; ``None`` is the identity): the map becomes MERGE(map, the map of
+        the placed cloud on this grid with this map's rule).  A point outside the grid raises the library's error and leaves the map as it
+        was."""
+        fn = "NormalDistributionsMap.insert"
+        h = self._open()
+        if not isinstance(cloud, PointCloud) or len(cloud) == 0:
+            raise RuntimeError(f"{fn}: the cloud must be a PointCloud with at least one point")
+        T, Tp = VoxelCovarianceMap._pose(fn, np.eye(4) if transformation is None else transformation)
+        ctx = _lib.Context.current()
+        ctx.check(ctx.lib.pcr_ndt_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), C.c_int64(len(cloud)), Tp), fn)
+        self._refresh()
+
+    def merge(self, other: "NormalDistributionsMap"):
+        """Add the cells of ``other``, a map on the same grid with the same ``min_points_per_voxel`` and ``eigenvalue_ratio``
+        (``pcr_ndt_map_merge``); ``other`` is unchanged.  A cell in both gets the sum of the counts, the count-weighted mean, the covariance
+        about that mean, and a recomputed ``A_v``."""
+        fn = "NormalDistributionsMap.merge"
+        h = self._open()
+        if not isinstance(other, NormalDistributionsMap):
+            raise TypeError(f"{fn}: other must be a NormalDistributionsMap, got {type(other).__name__}")
+        ho = other._open()
+        ctx = _lib.Context.current()
+        ctx.check(ctx.lib.pcr_ndt_map_merge(ctx.handle, h, ho), fn)
+        self._refresh()
+
+    def remove_far(self, center, max_distance) -> int:
+        """Drop every cell whose mean is not closer to ``center`` than ``max_distance`` (``pcr_ndt_map_remove_far``; d^2 < r^2 keeps) and return
+        the number of rows removed.  A call that would keep nothing raises the library's error and leaves the map as it was."""
+        fn = "NormalDistributionsMap.remove_far"
+        h = self._open()
+        c = np.ascontiguousarray(np.asarray(center, np.float64).reshape(-1))
+        if c.shape != (3,):
+            raise ValueError(f"{fn}: center must hold three numbers, got {center!r}")
+        try:
+            r = float(max_distance)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: max_distance must be a number greater than 0, got {max_distance!r}") from None
+        if not np.isfinite(r) or not (r > 0.0):
+            raise ValueError(f"{fn}: max_distance must be a finite number greater than 0, got {max_distance!r}")
+        ctx = _lib.Context.current()
+        removed = C.c_int64(0)
+        ctx.check(ctx.lib.pcr_ndt_map_remove_far(ctx.handle, h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r), C.byref(removed)), fn)
+        self._refresh()
+        return int(removed.value)
 
     def close(self):
         """Destroy the map (waits for the device)."""
@@ -920,6 +1017,58 @@ def registration_ndt(source: PointCloud, target_or_map, voxel_size=None, init=np
     finally:
         if own is not None:
             own.close()
+
+
+def scan_to_map_odometry_ndt(scans, voxel_size, init=np.eye(4), criteria=None, neighborhood: int = 7, outlier_ratio: float = 0.55, min_points_per_voxel: int = 6,
+                             eigenvalue_ratio: float = 0.01, motion_model: str = "constant_velocity", max_range=None, grid_min=None):
+    """LiDAR odometry by scan-to-map NDT -> ``(poses, results, map)``: ``scan_to_map_odometry`` with a ``NormalDistributionsMap``, so the scans
+    need neither normals nor covariances.  Exactly these public calls, in this order (calling them by hand with the same arguments gives the
+    same poses bit for bit):
+
+    * ``map = NormalDistributionsMap.on_grid(scans[0], voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, init)``; ``grid_min=None``
+      is ``centered_grid_min`` of scan 0's centre (``get_center()``) placed at ``init``; ``poses[0] = init``, ``results[0] = None``;
+    * for every further scan k: ``results[k] = registration_ndt(scans[k], map, None, start, criteria, neighborhood, outlier_ratio,
+      min_points_per_voxel)`` with ``start = P[k-1] @ inv(P[k-2]) @ P[k-1]`` under ``"constant_velocity"`` and ``P[k-1]`` under ``"static"``
+      (and for scan 1 in either model); ``poses[k]`` is its transformation;
+    * ``map.insert(scans[k], poses[k])``, and with a ``max_range``, ``map.remove_far(poses[k][:3, 3], max_range)``.
+
+    A scan that would leave the grid raises the library's error (the map is closed then).  The caller owns the returned map and closes it."""
+    fn = "scan_to_map_odometry_ndt"
+    if motion_model not in ("constant_velocity", "static"):
+        raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
+    _check_voxel_size(fn, voxel_size)
+    _check_ndt_rule(fn, neighborhood, outlier_ratio, min_points_per_voxel, eigenvalue_ratio)
+    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
+        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
+    scans = list(scans)
+    if not scans:
+        raise ValueError(f"{fn}: at least one scan is needed")
+    for k, s in enumerate(scans):
+        if not isinstance(s, PointCloud) or len(s) == 0:
+            raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
+    P0 = np.array(np.asarray(init, np.float64), np.float64)
+    if P0.shape != (4, 4):
+        raise ValueError(f"{fn}: init must have shape (4, 4), got {P0.shape}")
+    if grid_min is None:
+        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
+        grid_min = NormalDistributionsMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
+    nmap = NormalDistributionsMap.on_grid(scans[0], voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, P0)
+    poses, results = [P0], [None]
+    try:
+        for k in range(1, len(scans)):
+            start = poses[-1]
+            if motion_model == "constant_velocity" and k >= 2:
+                start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
+            res = registration_ndt(scans[k], nmap, None, start, criteria, neighborhood, outlier_ratio, min_points_per_voxel)
+            poses.append(np.array(res.transformation, np.float64))
+            results.append(res)
+            nmap.insert(scans[k], poses[-1])
+            if max_range is not None:
+                nmap.remove_far(poses[-1][:3, 3], max_range)
+    except BaseException:
+        nmap.close()
+        raise
+    return poses, results, nmap
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
