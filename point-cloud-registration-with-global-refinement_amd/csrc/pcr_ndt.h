@@ -1,5 +1,6 @@
 // pcr_ndt.h -- what pcr_ndt.hip (the map of a cloud, the NDT iteration) and pcr_nmap.hip (the map that grows) share: the map as the kernels see it,
-// the map behind the C handle, the one device function that turns (N_v, C_v) into validity and A_v, and the builder of a map on a given grid.
+// the map behind the C handle, its row policy for the frame of the maps that grow (NmapRow; pcr_mapgrow.h), the one device function that turns
+// (N_v, C_v) into validity and A_v, and the builder of a map on a given grid.
 // The rule is the statement in include/pcr_hip.h.
 #pragma once
 #include "pcr_vgicp.h"
@@ -28,6 +29,27 @@ struct pcr_ndt_map {
 static inline size_t ndt_block_bytes(int64_t cells) {
     return (size_t)cells * (sizeof(float4) * 3 + sizeof(double) * 6 + sizeof(uint64_t)) + (size_t)pcr_grid_slots((unsigned)cells) * sizeof(GridEntry) + 16 * 256;
 }
+// The map's row policy for the frame of the maps that grow (pcr_mapgrow.h states what each member is); combine is pcr_nmap.hip's.
+struct NmapRow {
+    typedef pcr_ndt_map Map;
+    struct Rows { const float4 *mean4, *cov8; const double *info6; const uint64_t *keys; int n; };
+    struct Out { float4 *mean4, *cov8; double *info6; uint64_t *keys; };
+    struct Merged { int cap, min_points; double ratio; Out out; };
+    static constexpr int EXTRA = 6;
+    __device__ static inline const double *extra(const Rows &r) { return r.info6; }
+    __device__ static inline double *extra(const Out &o) { return o.info6; }
+    static size_t block_bytes(int64_t cells) { return ndt_block_bytes(cells); }
+    static bool carve(pcr_context *ctx, int64_t cells, Out *o) {
+        o->mean4 = arena<float4>(ctx, (size_t)cells); o->cov8 = arena<float4>(ctx, 2 * (size_t)cells); o->info6 = arena<double>(ctx, 6 * (size_t)cells);
+        o->keys = arena<uint64_t>(ctx, (size_t)cells);
+        return o->mean4 && o->cov8 && o->info6 && o->keys;
+    }
+    static Rows rows_of(const Map *m) { return Rows{m->view.mean4, m->view.cov8, m->view.info6, m->keys, (int)m->cells}; }
+    static void set_view(Map *m, const Out &o) { m->view.mean4 = o.mean4; m->view.cov8 = o.cov8; m->view.info6 = o.info6; }
+    static Merged merged(const Map *m, int cap, const Out &o) { return Merged{cap, m->min_points, m->ratio, o}; }
+    __device__ static inline int count(const float4 m) { const int w = __float_as_int(m.w); return w < 0 ? -w : w; }      // the sign carries the validity
+    __device__ static inline void combine(const Merged &g, float4 &m, float4 &c0, float4 &c1, double *x, const float4 mb, const float4 d0, const float4 d1);
+};
 __device__ static inline VgicpMapView ndt_hash(const NdtMapView &m) {      // what vg_row reads of a map
     VgicpMapView g;
     g.tab = m.tab; g.dmask = m.dmask; g.mean4 = m.mean4; g.cov8 = m.cov8;
@@ -88,7 +110,6 @@ __device__ static inline bool ndt_cell_information(int nv, const float4 c0, cons
 }
 
 // host helpers of pcr_ndt.hip that pcr_nmap.hip calls too
-struct pcr_context;
 int ndt_check_map(pcr_context *ctx, const pcr_ndt_map *map, const char *call);
 // A new map of the n points of xyz (MAP of the NDT section), finished when it returns.  grid_min3 == NULL: the grid of the cloud's own minimum;
 // otherwise the given grid, and a member outside its 2^21 cells per axis is PCR_EINVAL.  T (16 doubles) == NULL: the points as they lie, not even

@@ -2,7 +2,8 @@
 // its loop, the one-launch linearisation and the entry points; the specification is the statement in include/pcr_hip.h.  The grid, the cell
 // hash and the pose expression are voxelized GICP's (pcr_vgicp.h); what an ICP loop is made of is pcr_icp_loop.h.
 //   map build      the means through the voxel pass (pcr_dev_voxel: float64 sums in input order); the cells' Morton keys go into the cell hash
-//                  of level 0 inside the map's own allocation; k_ndt_member forms the six products of every member against its cell's float32
+//                  of level 0 inside the map's own allocation (map_build_block, pcr_mapgrow.h: the builder of every map block, here with what
+//                  follows in its after-hook); k_ndt_member forms the six products of every member against its cell's float32
 //                  mean, found through that hash, as two 3-vectors that ride in the attribute slot of two more voxel passes (the same keys, the
 //                  same stable sort: row v of all three passes is the same cell) and counts the members; k_ndt_cell lays the rows out and
 //                  computes A_v with a float64 Jacobi eigen-solve (ndt_cell_information, pcr_ndt.h).  One builder, ndt_map_build, on the
@@ -17,6 +18,7 @@
 #include <cstring>
 #include "pcr_icp_loop.h"
 #include "pcr_ndt.h"
+#include "pcr_mapgrow.h"
 
 #define NDT_BS 256
 #define NDT_NL 32                      // sums of the linearisation: the loop's 30, the score, one unused
@@ -252,17 +254,11 @@ __global__ void __launch_bounds__(NDT_BS) k_ndt_cell(const float4 *__restrict__ 
 #pragma unroll
     for (int t = 0; t < 6; t++) info6[6 * (size_t)v + t] = A6[t];
 }
-// ---- p' = float32(q) with q the ROWS expression (vg_transform), the point half of k_vmap_place; bad: set when a placed coordinate is not finite
+// ---- the members at a pose: vg_place_point (pcr_vgicp.h), which k_vmap_place calls too
 struct NdtPlace { double T[12]; };
 __global__ void __launch_bounds__(NDT_BS) k_ndt_place(const float *__restrict__ xyz, int n, NdtPlace pose, float *__restrict__ out_xyz, int *__restrict__ bad) {
-#pragma clang fp contract(off)
     const int i = blockIdx.x * NDT_BS + threadIdx.x;
-    if (i >= n) return;
-    double qx, qy, qz;
-    vg_transform(pose.T, xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2], qx, qy, qz);
-    const float px = (float)qx, py = (float)qy, pz = (float)qz;
-    out_xyz[(size_t)i * 3] = px; out_xyz[(size_t)i * 3 + 1] = py; out_xyz[(size_t)i * 3 + 2] = pz;
-    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) atomicOr(bad, 1);
+    if (i < n) vg_place_point(pose.T, xyz, i, out_xyz, bad);
 }
 __global__ void __launch_bounds__(NDT_BS) k_ndt_read(const uint64_t *__restrict__ keys, NdtMapView m, int cells, int32_t *__restrict__ cell3, int32_t *__restrict__ count,
                                                      float *__restrict__ mean3, float *__restrict__ cov6, double *__restrict__ info6, uint8_t *__restrict__ valid) {
@@ -362,17 +358,10 @@ int ndt_map_build(pcr_context *ctx, const char *call, const float *xyz, int64_t 
     double b6[6];
     PCR_TRY(pcr_dev_bounds(ctx, xyz, n, b6));
     if (grid_min3) {
-        // both ends of the members against the grid before any key is formed (k_voxel_keys has no defence against a negative index); the voxel pass
-        // then runs with grid_min3 in place of the members' minimum
+        // both ends of the members against the grid before any key is formed; the voxel pass then runs with grid_min3 in place of the members' minimum
         int64_t nonfinite = 0;
         if (bad) PCR_TRY(pcr_read_count(ctx, bad, &nonfinite));
-        bool inside = nonfinite == 0;
-        for (int d = 0; d < 3 && inside; d++) {
-            const double org = grid_min3[d] - voxel_size * 0.5;
-            const double lo = floor((b6[d] - org) / voxel_size), hi = floor((b6[3 + d] - org) / voxel_size);
-            inside = lo >= 0.0 && hi < 2097152.0;
-        }
-        if (!inside) { ctx->err = who + ": xyz lies outside the map's grid (cell indices must stay in [0, 2^21) on every axis)"; return PCR_EINVAL; }
+        if (nonfinite != 0 || !vg_inside_grid(b6, grid_min3, voxel_size)) { ctx->err = who + ": xyz lies outside the map's grid (cell indices must stay in [0, 2^21) on every axis)"; return PCR_EINVAL; }
         for (int d = 0; d < 3; d++) b6[d] = grid_min3[d];
     }
     float *lo3 = arena<float>(ctx, (size_t)n * 3), *hi3 = arena<float>(ctx, (size_t)n * 3);
@@ -388,30 +377,18 @@ int ndt_map_build(pcr_context *ctx, const char *call, const float *xyz, int64_t 
     if (cells < 1 || cells > n) { ctx->err = who + ": the voxel pass returned no cells"; return PCR_EHIP; }
 
     pcr_ndt_map *m = new pcr_ndt_map();
-    m->device = ctx->device; m->cells = cells;
+    m->device = ctx->device;
     for (int d = 0; d < 3; d++) m->grid_min[d] = b6[d];
     m->min_points = min_points_per_voxel; m->ratio = eigenvalue_ratio;
-    auto build = [&]() -> int {
-        m->bytes = ndt_block_bytes(cells);
-        if (hipMalloc((void **)&m->block, m->bytes) != hipSuccess) { m->block = nullptr; ctx->err = "hipMalloc(ndt map)"; return PCR_ENOMEM; }
-        float4 *mean4, *cov8; double *info6;
-        DevCloud mc;                                             // the cells as a voxel-lattice cloud: what the hash build reads (keys, count, lattice)
-        GridView gv;
-        {   // the map's arrays and the hash table come out of the map's block; everything else is scratch of the context's arena
-            SideLane own(ctx, m->block, m->bytes, ctx->stream);
-            mean4 = arena<float4>(ctx, (size_t)cells); cov8 = arena<float4>(ctx, 2 * (size_t)cells); info6 = arena<double>(ctx, 6 * (size_t)cells);
-            m->keys = arena<uint64_t>(ctx, (size_t)cells); m->n_dev = arena<int>(ctx, 1);
-            if (!mean4 || !cov8 || !info6 || !m->keys || !m->n_dev) return PCR_ENOMEM;
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(m->keys, vm.keys, sizeof(uint64_t) * (size_t)cells, hipMemcpyDeviceToDevice, ctx->stream));
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(m->n_dev, vm.n, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-            mc = vm; mc.pts = nullptr; mc.nrm = nullptr; mc.keys = m->keys; mc.n = m->n_dev; mc.cap = (int)cells;
-            const DevCloud *pmc = &mc; const int level = 0;
-            PCR_TRY(pcr_dev_build_grid_batch(ctx, &pmc, &level, 1, &gv));
-        }
-        if (!gv.tab) { ctx->err = who + ": no cell hash"; return PCR_EHIP; }
-        m->view.tab = gv.tab; m->view.dmask = gv.dmask; m->view.mean4 = mean4; m->view.cov8 = cov8; m->view.info6 = info6;
-        for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
-        m->view.voxel = voxel_size;
+    for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
+    m->view.voxel = voxel_size;
+    // the map's arrays and the hash table come out of the map's block; the member statistic, through that hash, is scratch of the context's arena
+    MapBlock<NmapRow> nb;
+    const int rc = map_build_block<NmapRow>(ctx, call, cells, &nb, [&](const NmapRow::Out &o) -> int {
+        PCR_HIP_CHECK(ctx, hipMemcpyAsync(o.keys, vm.keys, sizeof(uint64_t) * (size_t)cells, hipMemcpyDeviceToDevice, ctx->stream));
+        return PCR_OK;
+    }, [&](const MapBlock<NmapRow> &b) -> int {
+        map_adopt<NmapRow>(m, b, cells);      // (the builder frees the block if anything after this fails)
         int *count = arena<int>(ctx, (size_t)cells);
         if (!count) return PCR_ENOMEM;
         PCR_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(int) * (size_t)cells, ctx->stream));
@@ -419,14 +396,10 @@ int ndt_map_build(pcr_context *ctx, const char *call, const float *xyz, int64_t 
         PCR_TRY(pcr_dev_voxel(ctx, xyz, lo3, n, b6, voxel_size, &va));
         PCR_TRY(pcr_dev_voxel(ctx, xyz, hi3, n, b6, voxel_size, &vb));
         PCR_LAUNCH(ctx, k_ndt_cell, dim3(ndt_blocks((size_t)cells)), dim3(NDT_BS), 0, ctx->stream, (const float4 *)vm.pts, (const float4 *)va.nrm, (const float4 *)vb.nrm,
-                   (const int *)count, (int)cells, min_points_per_voxel, eigenvalue_ratio, mean4, cov8, info6);
-        // finished before the call returns: the caller may overwrite its buffers, and any context may use the map
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->launch_err != hipSuccess) return PCR_EHIP;      // (pcr_leave names the launch)
+                   (const int *)count, (int)cells, min_points_per_voxel, eigenvalue_ratio, b.out.mean4, b.out.cov8, b.out.info6);
         return PCR_OK;
-    };
-    const int rc = build();
-    if (rc != PCR_OK) { if (m->block) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(m->block); } delete m; return rc; }
+    });
+    if (rc != PCR_OK) { delete m; return rc; }
     *out = m;
     return PCR_OK;
 }

@@ -1,6 +1,7 @@
 // pcr_vgicp.h -- what the kernels of pcr_vgicp.hip share on the device (the map's count and row kernels, the voxelized GICP iteration kernel):
 // the map as they see it, the pose applied to a source point with every operation rounded once, the cell of the result, the neighbourhood's
-// offsets and the probe of the cell hash.  The rule is the statement in include/pcr_hip.h.
+// offsets and the probe of the cell hash; and what the maps that grow take from here: the map's row policy (VmapRow; pcr_mapgrow.h), the key
+// search, the far test, the placing of a point, the host checks.  The rule is the statement in include/pcr_hip.h.
 #pragma once
 #include "pcr_octree.h"
 
@@ -28,13 +29,37 @@ static inline size_t vg_block_bytes(int64_t cells) {
     return (size_t)cells * (sizeof(float4) * 3 + sizeof(uint64_t)) + (size_t)pcr_grid_slots((unsigned)cells) * sizeof(GridEntry) + 16 * 256;
 }
 
-// host helpers of pcr_vgicp.hip that pcr_vmap.hip calls too: PCR_EINVAL naming the first of up to three arrays that holds a non-finite value
-// (one read-back); the map / pose argument checks; the member covariances of n points as packed cov6 (enqueues only)
-struct pcr_context;
+// The map's row policy for the frame of the maps that grow (pcr_mapgrow.h states what each member is); count and combine are pcr_vmap.hip's.
+struct VmapRow {
+    typedef pcr_voxel_map Map;
+    struct Rows { const float4 *mean4, *cov8; const uint64_t *keys; int n; };
+    struct Out { float4 *mean4, *cov8; uint64_t *keys; };
+    struct Merged { int cap; Out out; };
+    static constexpr int EXTRA = 0;
+    __device__ static inline const double *extra(const Rows &) { return nullptr; }
+    __device__ static inline double *extra(const Out &) { return nullptr; }
+    static size_t block_bytes(int64_t cells) { return vg_block_bytes(cells); }
+    static bool carve(pcr_context *ctx, int64_t cells, Out *o) {
+        o->mean4 = arena<float4>(ctx, (size_t)cells); o->cov8 = arena<float4>(ctx, 2 * (size_t)cells); o->keys = arena<uint64_t>(ctx, (size_t)cells);
+        return o->mean4 && o->cov8 && o->keys;
+    }
+    static Rows rows_of(const Map *m) { return Rows{m->view.mean4, m->view.cov8, m->keys, (int)m->cells}; }
+    static void set_view(Map *m, const Out &o) { m->view.mean4 = o.mean4; m->view.cov8 = o.cov8; }
+    static Merged merged(const Map *, int cap, const Out &o) { return Merged{cap, o}; }
+    __device__ static inline int count(const float4 m) { return __float_as_int(m.w); }
+    __device__ static inline void combine(const Merged &g, float4 &m, float4 &c0, float4 &c1, double *x, const float4 mb, const float4 d0, const float4 d1);
+};
+
+// host helpers of pcr_vgicp.hip that the units of the maps that grow call too: PCR_EINVAL naming the first of up to three arrays that holds a
+// non-finite value (one read-back); the map / pose / grid_min3 argument checks; the member covariances of n points as packed cov6 (enqueues only);
+// whether both ends of the members (bounds6: minimum, maximum) lie inside the 2^21 cells per axis of the grid of grid_min3
 int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr, const size_t *count, const char *const *name, int arrays);
 int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call);
 int vg_check_T(pcr_context *ctx, const char *call, const char *name, const double *T);
+int vg_check_grid_min(pcr_context *ctx, const char *call, const double *grid_min3);
 int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, double eps, int64_t n, float *out6);
+bool vg_inside_grid(const double *bounds6, const double *grid_min3, double voxel);
+static const double vg_eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};      // no pose is the identity, applied all the same
 
 #define VG_NO_CELL (-4)                   // a coordinate with every candidate cell outside the grid (also: a non-finite coordinate)
 
@@ -49,6 +74,16 @@ __device__ static inline void vg_transform(const double *T, float x, float y, fl
     double sx = ax + bx, sy = ay + by, sz = az + bz;
     sx = sx + cx; sy = sy + cy; sz = sz + cz;
     qx = sx + T[3]; qy = sy + T[7]; qz = sz + T[11];
+}
+// the point half of placing a member at a pose: p' = float32(q) with q the ROWS expression above; *bad is set when a placed coordinate is not finite
+// (a pose whose products overflow)
+__device__ static inline void vg_place_point(const double *T, const float *__restrict__ xyz, int i, float *__restrict__ out_xyz, int *__restrict__ bad) {
+#pragma clang fp contract(off)
+    double qx, qy, qz;
+    vg_transform(T, xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2], qx, qy, qz);
+    const float px = (float)qx, py = (float)qy, pz = (float)qz;
+    out_xyz[(size_t)i * 3] = px; out_xyz[(size_t)i * 3 + 1] = py; out_xyz[(size_t)i * 3 + 2] = pz;
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) atomicOr(bad, 1);
 }
 // floor((q - origin) / voxel) of one axis as an int; everything from which no offset of -1, 0, +1 leads into [0, 2^21) becomes VG_NO_CELL
 __device__ static inline int vg_cell(double q, double org, double voxel) {

@@ -3,8 +3,10 @@
 // pcr_icp_loop.h, shared with pcr_gicp.hip.
 //   map build   the member covariances (given, or from the normals as the GICP estimator forms them) are split into two 3-vectors that ride
 //                in the attribute slot of the voxel pass (pcr_dev_voxel: float64 sums in input order), one pass each; the cells' Morton keys go
-//                into the cell hash of level 0 (pcr_dev_build_grid_batch) inside the map's own allocation; the member counts are integer
-//                atomics through that hash; k_vmap_pack lays the rows out as the iteration kernel gathers them
+//                into the cell hash of level 0 inside the map's own allocation (map_build_block, pcr_mapgrow.h: the builder of every map block,
+//                here with the count and pack kernels in its after-hook); the member counts are integer atomics through that hash; k_vmap_pack
+//                lays the rows out as the iteration kernel gathers them.  The host checks that pcr_vmap.hip and pcr_nmap.hip call too (vg_check_*,
+//                vg_inside_grid) are defined here and declared in pcr_vgicp.h
 //   k_vmap_rows  the candidate rows of every source point at a pose (slot k of point i = map row or -1); the correspondence set is their
 //                compaction by the flag scan (pcr_dev_flag_scan) and k_vmap_emit
 // Floating-point contraction per source expression only, as in pcr_gicp.hip; the expressions that decide a cell are not contracted at all.
@@ -12,7 +14,7 @@
 #include <cmath>
 #include <cstring>
 #include "pcr_icp_loop.h"
-#include "pcr_vgicp.h"
+#include "pcr_mapgrow.h"
 
 #define VG_BS 256
 
@@ -340,6 +342,20 @@ int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, do
     PCR_LAUNCH(ctx, k_vmap_member_cov, dim3(vg_blocks((size_t)n)), dim3(VG_BS), 0, ctx->stream, cov6, normals, eps, (int)n, (float *)nullptr, (float *)nullptr, out6);
     return PCR_OK;
 }
+int vg_check_grid_min(pcr_context *ctx, const char *call, const double *grid_min3) {
+    if (!grid_min3) { ctx->err = std::string(call) + ": grid_min3 is null"; return PCR_EINVAL; }
+    for (int d = 0; d < 3; d++) if (!std::isfinite(grid_min3[d])) { ctx->err = std::string(call) + ": grid_min3 holds a non-finite value"; return PCR_EINVAL; }
+    return PCR_OK;
+}
+// both ends of the members against the grid, on the host before any key is formed (k_voxel_keys has no defence against a negative index)
+bool vg_inside_grid(const double *bounds6, const double *grid_min3, double voxel) {
+    for (int d = 0; d < 3; d++) {
+        const double org = grid_min3[d] - voxel * 0.5;
+        const double lo = floor((bounds6[d] - org) / voxel), hi = floor((bounds6[3 + d] - org) / voxel);
+        if (!(lo >= 0.0 && hi < 2097152.0)) return false;
+    }
+    return true;
+}
 static int vg_check_rule(pcr_context *ctx, const char *call, int neighborhood, int min_points) {
     if (neighborhood != 1 && neighborhood != 7 && neighborhood != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
     if (min_points < 1) { ctx->err = std::string(call) + ": min_points_per_voxel < 1"; return PCR_EINVAL; }
@@ -377,41 +393,26 @@ extern "C" int pcr_voxel_map_create(pcr_context *ctx, const float *xyz, const fl
     if (cells < 1 || cells > n) { ctx->err = "voxel_map_create: the voxel pass returned no cells"; return PCR_EHIP; }
 
     pcr_voxel_map *m = new pcr_voxel_map();
-    m->device = ctx->device; m->cells = cells;
-    auto build = [&]() -> int {
-        m->bytes = vg_block_bytes(cells);
-        if (hipMalloc((void **)&m->block, m->bytes) != hipSuccess) { m->block = nullptr; ctx->err = "hipMalloc(voxel map)"; return PCR_ENOMEM; }
-        float4 *mean4, *cov8;
-        DevCloud mc;                                             // the cells as a voxel-lattice cloud: what the hash build reads (keys, count, lattice)
-        GridView gv;
-        {   // the map's arrays and the hash table come out of the map's block; everything else is scratch of the context's arena
-            SideLane own(ctx, m->block, m->bytes, ctx->stream);
-            mean4 = arena<float4>(ctx, (size_t)cells); cov8 = arena<float4>(ctx, 2 * (size_t)cells);
-            m->keys = arena<uint64_t>(ctx, (size_t)cells); m->n_dev = arena<int>(ctx, 1);
-            if (!mean4 || !cov8 || !m->keys || !m->n_dev) return PCR_ENOMEM;
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(m->keys, va.keys, sizeof(uint64_t) * (size_t)cells, hipMemcpyDeviceToDevice, ctx->stream));
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(m->n_dev, va.n, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-            mc = va; mc.pts = nullptr; mc.nrm = nullptr; mc.keys = m->keys; mc.n = m->n_dev; mc.cap = (int)cells;
-            const DevCloud *pmc = &mc; const int level = 0;
-            PCR_TRY(pcr_dev_build_grid_batch(ctx, &pmc, &level, 1, &gv));
-        }
-        if (!gv.tab) { ctx->err = "voxel_map_create: no cell hash"; return PCR_EHIP; }
-        m->view.tab = gv.tab; m->view.dmask = gv.dmask; m->view.mean4 = mean4; m->view.cov8 = cov8;
-        for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
-        m->view.voxel = voxel_size;
-        for (int d = 0; d < 3; d++) m->grid_min[d] = b6[d];
+    m->device = ctx->device;
+    for (int d = 0; d < 3; d++) m->view.org[d] = b6[d] - voxel_size * 0.5;      // (pcr_dev_voxel's origin)
+    m->view.voxel = voxel_size;
+    for (int d = 0; d < 3; d++) m->grid_min[d] = b6[d];
+    // the map's arrays and the hash table come out of the map's block; the counts, through that hash, are scratch of the context's arena
+    MapBlock<VmapRow> nb;
+    const int rc = map_build_block<VmapRow>(ctx, call, cells, &nb, [&](const VmapRow::Out &o) -> int {
+        PCR_HIP_CHECK(ctx, hipMemcpyAsync(o.keys, va.keys, sizeof(uint64_t) * (size_t)cells, hipMemcpyDeviceToDevice, ctx->stream));
+        return PCR_OK;
+    }, [&](const MapBlock<VmapRow> &b) -> int {
+        map_adopt<VmapRow>(m, b, cells);      // (the builder frees the block if anything after this fails)
         int *count = arena<int>(ctx, (size_t)cells);
         if (!count) return PCR_ENOMEM;
         PCR_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(int) * (size_t)cells, ctx->stream));
         PCR_LAUNCH(ctx, k_vmap_count, dim3(vg_blocks((size_t)n)), dim3(VG_BS), 0, ctx->stream, xyz, (int)n, m->view, (int)cells, count);
         PCR_LAUNCH(ctx, k_vmap_pack, dim3(vg_blocks((size_t)cells)), dim3(VG_BS), 0, ctx->stream, (const float4 *)va.pts, (const float4 *)va.nrm, (const float4 *)vb.nrm,
-                   (const int *)count, (int)cells, mean4, cov8);
-        // finished before the call returns: the caller may overwrite its buffers, and any context may use the map
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+                   (const int *)count, (int)cells, b.out.mean4, b.out.cov8);
         return PCR_OK;
-    };
-    const int rc = build();
-    if (rc != PCR_OK) { if (m->block) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(m->block); } delete m; return rc; }
+    });
+    if (rc != PCR_OK) { delete m; return rc; }
     *out = m;
     return PCR_OK;
     });

@@ -4,22 +4,21 @@
 //   k_vmap_place       one lane per point: p' = float32(T p), C' = float32((R C) R^T) of the member covariance, as the two 3-vectors the voxel pass carries
 //   rows of a cloud    one voxel pass for all nine channels: k_vmap_keys (the keys of k_voxel_keys on the map's grid), the project's stable radix sort,
 //                      k_vmap_heads and the flag scan, k_vmap_cell_rows (float64 sums over the members in input order; the count is the segment length)
-//   merge              k_vmap_merge_mark: every row searches its key in the other list; the rows of B that A does not hold are flagged and scanned
-//                      (pcr_dev_flag_scan), which gives every row its place in the union; k_vmap_merge_write copies or combines
-//   remove_far         k_vmap_far_flags, the flag scan, k_vmap_gather
-// Every mutating call builds a new block (rows, keys, count word, cell hash by pcr_dev_build_grid_batch), waits for it, swaps it in and frees the old
-// one; on an error the map is untouched.  The expressions of the rule are not contracted.
+//   merge, remove_far  the frame of the maps that grow (pcr_mapgrow.h: k_map_merge_mark, k_map_merge_write, k_map_far_flags, k_map_gather, the block
+//                      builder, map_merge_into, map_remove_far) with the row policy VmapRow (pcr_vgicp.h); what is this map's own is
+//                      VmapRow::combine, the count-weighted mean of the nine channels of a cell that both maps hold
+// Every mutating call builds a new block (rows, keys, count word, cell hash), waits for it, swaps it in and frees the old one; on an error the map
+// is untouched.  The expressions of the rule are not contracted.
 #pragma clang fp contract(off)
 #include <cmath>
 #include <cstring>
-#include "pcr_vgicp.h"
+#include "pcr_mapgrow.h"
 
 #define VM_BS 256
 
 static unsigned vm_blocks(size_t n) { return (unsigned)((n + VM_BS - 1) / VM_BS); }
 
-// ---- a list of map rows on the device, in ascending Morton order of the cell: what a map holds, and what a scan becomes before it is merged
-struct VmRows { const float4 *mean4, *cov8; const uint64_t *keys; int n; };
+typedef VmapRow::Rows VmRows;      // what a map holds, and what a scan becomes before it is merged
 struct VmPose { double T[12]; };
 
 // ================================================================ kernels
@@ -30,11 +29,7 @@ __global__ void __launch_bounds__(VM_BS) k_vmap_place(const float *__restrict__ 
 #pragma clang fp contract(off)
     const int i = blockIdx.x * VM_BS + threadIdx.x;
     if (i >= n) return;
-    double qx, qy, qz;
-    vg_transform(pose.T, xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2], qx, qy, qz);
-    const float px = (float)qx, py = (float)qy, pz = (float)qz;
-    out_xyz[(size_t)i * 3] = px; out_xyz[(size_t)i * 3 + 1] = py; out_xyz[(size_t)i * 3 + 2] = pz;
-    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) atomicOr(bad, 1);
+    vg_place_point(pose.T, xyz, i, out_xyz, bad);
     const float *c = cov6 + (size_t)i * 6;
     const double C[9] = {c[0], c[1], c[2], c[1], c[3], c[4], c[2], c[4], c[5]};
     const double R[9] = {pose.T[0], pose.T[1], pose.T[2], pose.T[4], pose.T[5], pose.T[6], pose.T[8], pose.T[9], pose.T[10]};
@@ -85,20 +80,6 @@ __global__ void __launch_bounds__(VM_BS) k_vmap_cell_rows(const float *__restric
     out_keys[o] = key;
 }
 
-// lane t < a.n: row t of A finds where its key stands in B (where[t] = lower bound); lane a.n + j: row j of B finds where it stands in A and is
-// flagged when A does not hold its cell.  A shared cell whose counts add up past 2^31 - 1 sets *overflow.
-__global__ void __launch_bounds__(VM_BS) k_vmap_merge_mark(VmRows a, VmRows b, int *__restrict__ where, uint8_t *__restrict__ only_b, int *__restrict__ overflow) {
-    const int t = blockIdx.x * VM_BS + threadIdx.x;
-    if (t >= a.n + b.n) return;
-    if (t < a.n) { where[t] = vg_lower_bound(b.keys, b.n, a.keys[t]); return; }
-    const int j = t - a.n;
-    const uint64_t key = b.keys[j];
-    const int i = vg_lower_bound(a.keys, a.n, key);
-    const bool shared = i < a.n && a.keys[i] == key;
-    where[t] = i;
-    only_b[j] = shared ? 0 : 1;
-    if (shared && (int64_t)__float_as_int(a.mean4[i].w) + (int64_t)__float_as_int(b.mean4[j].w) > 0x7fffffffll) atomicOr(overflow, 1);
-}
 // one channel of a cell in both maps: float32((N_a a + N_b b) / N) in float64, the sum, then the division, then one rounding
 __device__ static inline float vm_mix(double na, float a, double nb, float b, double n) {
 #pragma clang fp contract(off)
@@ -109,54 +90,16 @@ __device__ static inline float vm_mix(double na, float a, double nb, float b, do
 __device__ static inline float4 vm_mix4(double na, float4 a, double nb, float4 b, double n) {
     return make_float4(vm_mix(na, a.x, nb, b.x, n), vm_mix(na, a.y, nb, b.y, n), vm_mix(na, a.z, nb, b.z, n), vm_mix(na, a.w, nb, b.w, n));
 }
-// the union's rows: row t of A lands at t + (rows of B alone below it), combined with its partner where B holds the cell too; a row of B alone
-// lands at (rows of B alone before it) + (rows of A below it)
-__global__ void __launch_bounds__(VM_BS) k_vmap_merge_write(VmRows a, VmRows b, const int *__restrict__ where, const uint8_t *__restrict__ only_b,
-                                                            const int *__restrict__ pos_b, const int *__restrict__ total_b, int cap,
-                                                            float4 *__restrict__ mean4, float4 *__restrict__ cov8, uint64_t *__restrict__ keys) {
-    const int t = blockIdx.x * VM_BS + threadIdx.x;
-    if (t >= a.n + b.n) return;
-    float4 m, c0, c1; uint64_t key; int o;
-    if (t < a.n) {
-        const int j = where[t];
-        key = a.keys[t]; m = a.mean4[t]; c0 = a.cov8[2 * (size_t)t]; c1 = a.cov8[2 * (size_t)t + 1];
-        o = t + (j < b.n ? pos_b[j] : *total_b);
-        if (j < b.n && b.keys[j] == key) {
-            const float4 mb = b.mean4[j], d0 = b.cov8[2 * (size_t)j], d1 = b.cov8[2 * (size_t)j + 1];
-            const int na = __float_as_int(m.w), nb = __float_as_int(mb.w), n = na + nb;
-            const double fa = (double)na, fb = (double)nb, fn = (double)n;
-            m = make_float4(vm_mix(fa, m.x, fb, mb.x, fn), vm_mix(fa, m.y, fb, mb.y, fn), vm_mix(fa, m.z, fb, mb.z, fn), __int_as_float(n));
-            c0 = vm_mix4(fa, c0, fb, d0, fn);
-            c1 = make_float4(vm_mix(fa, c1.x, fb, d1.x, fn), vm_mix(fa, c1.y, fb, d1.y, fn), 0.0f, 0.0f);
-        }
-    } else {
-        const int j = t - a.n;
-        if (!only_b[j]) return;
-        key = b.keys[j]; m = b.mean4[j]; c0 = b.cov8[2 * (size_t)j]; c1 = b.cov8[2 * (size_t)j + 1];
-        o = pos_b[j] + where[t];
-    }
-    if (o < 0 || o >= cap) return;
-    mean4[o] = m; cov8[2 * (size_t)o] = c0; cov8[2 * (size_t)o + 1] = c1; keys[o] = key;
-}
-
-// keep[v] = d^2 < r^2 (vg_within, pcr_vgicp.h)
-__global__ void __launch_bounds__(VM_BS) k_vmap_far_flags(const float4 *__restrict__ mean4, int n, double cx, double cy, double cz, double r2, uint8_t *__restrict__ keep) {
-    const int v = blockIdx.x * VM_BS + threadIdx.x;
-    if (v >= n) return;
-    keep[v] = vg_within(mean4[v], cx, cy, cz, r2) ? 1 : 0;
-}
-__global__ void __launch_bounds__(VM_BS) k_vmap_gather(VmRows a, const uint8_t *__restrict__ keep, const int *__restrict__ pos, int cap, float4 *__restrict__ mean4,
-                                                       float4 *__restrict__ cov8, uint64_t *__restrict__ keys) {
-    const int v = blockIdx.x * VM_BS + threadIdx.x;
-    if (v >= a.n || !keep[v]) return;
-    const int o = pos[v];
-    if (o < 0 || o >= cap) return;
-    mean4[o] = a.mean4[v]; cov8[2 * (size_t)o] = a.cov8[2 * (size_t)v]; cov8[2 * (size_t)o + 1] = a.cov8[2 * (size_t)v + 1]; keys[o] = a.keys[v];
+// a cell in both maps: the counts add up, every one of the nine channels is the count-weighted mean
+__device__ inline void VmapRow::combine(const Merged &, float4 &m, float4 &c0, float4 &c1, double *, const float4 mb, const float4 d0, const float4 d1) {
+    const int na = __float_as_int(m.w), nb = __float_as_int(mb.w), n = na + nb;
+    const double fa = (double)na, fb = (double)nb, fn = (double)n;
+    m = make_float4(vm_mix(fa, m.x, fb, mb.x, fn), vm_mix(fa, m.y, fb, mb.y, fn), vm_mix(fa, m.z, fb, mb.z, fn), __int_as_float(n));
+    c0 = vm_mix4(fa, c0, fb, d0, fn);
+    c1 = make_float4(vm_mix(fa, c1.x, fb, d1.x, fn), vm_mix(fa, c1.y, fb, d1.y, fn), 0.0f, 0.0f);
 }
 
 // ================================================================ host
-static VmRows vm_rows_of(const pcr_voxel_map *m) { return VmRows{m->view.mean4, m->view.cov8, m->keys, (int)m->cells}; }
-
 struct VmGrid { double grid_min[3], voxel; };
 static void vm_origin(const VmGrid &g, double *org) { for (int d = 0; d < 3; d++) org[d] = g.grid_min[d] - g.voxel * 0.5; }      // (pcr_dev_voxel's expression)
 
@@ -179,8 +122,7 @@ static int vm_cloud_rows(pcr_context *ctx, const char *call, const float *xyz, c
         PCR_TRY(vg_check_finite(ctx, call, ptr, cnt, name, 3));
     }
     VmPose pose;
-    static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    memcpy(pose.T, T ? T : eye, sizeof pose.T);
+    memcpy(pose.T, T ? T : vg_eye, sizeof pose.T);
     const float *member = cov6;
     if (!member) {
         float *c6 = arena<float>(ctx, (size_t)n * 6);
@@ -200,12 +142,7 @@ static int vm_cloud_rows(pcr_context *ctx, const char *call, const float *xyz, c
     int64_t nonfinite = 0;
     PCR_TRY(pcr_read_count(ctx, bad, &nonfinite));
     vm_origin(g, org);
-    bool inside = nonfinite == 0;
-    for (int d = 0; d < 3 && inside; d++) {
-        const double lo = floor((pb[d] - org[d]) / g.voxel), hi = floor((pb[3 + d] - org[d]) / g.voxel);
-        inside = lo >= 0.0 && hi < 2097152.0;
-    }
-    if (!inside) { ctx->err = std::string(call) + ": xyz lies outside the map's grid (cell indices must stay in [0, 2^21) on every axis)"; return PCR_EINVAL; }
+    if (nonfinite != 0 || !vg_inside_grid(pb, g.grid_min, g.voxel)) { ctx->err = std::string(call) + ": xyz lies outside the map's grid (cell indices must stay in [0, 2^21) on every axis)"; return PCR_EINVAL; }
     // one voxel pass for all nine channels: the keys of k_voxel_keys on the map's grid, the project's stable sort (members of a cell stay in input
     // order), head flags and their scan, and one lane per cell that sums its members.  Rows (cap n) in the arena; the count comes back once.
     uint32_t top = 0;
@@ -233,77 +170,10 @@ static int vm_cloud_rows(pcr_context *ctx, const char *call, const float *xyz, c
     return PCR_OK;
 }
 
-// A new block of `cells` rows: `fill` enqueues what writes the rows and the keys; then the count word and the cell hash.  Finished (the stream is
-// idle) when it returns PCR_OK; on an error nothing of it is left.
-struct VmBlock { char *block = nullptr; size_t bytes = 0; float4 *mean4 = nullptr, *cov8 = nullptr; uint64_t *keys = nullptr; int *n_dev = nullptr; GridView gv; };
-template <class Fill> static int vm_build_block(pcr_context *ctx, const char *call, int64_t cells, VmBlock *b, Fill &&fill) {
-    b->bytes = vg_block_bytes(cells);
-    if (hipMalloc((void **)&b->block, b->bytes) != hipSuccess) { b->block = nullptr; ctx->err = std::string("hipMalloc(") + call + ")"; return PCR_ENOMEM; }
-    auto body = [&]() -> int {
-        SideLane own(ctx, b->block, b->bytes, ctx->stream);      // the rows and the hash table come out of the block, on the call's own stream
-        b->mean4 = arena<float4>(ctx, (size_t)cells); b->cov8 = arena<float4>(ctx, 2 * (size_t)cells);
-        b->keys = arena<uint64_t>(ctx, (size_t)cells); b->n_dev = arena<int>(ctx, 1);
-        if (!b->mean4 || !b->cov8 || !b->keys || !b->n_dev) return PCR_ENOMEM;
-        PCR_TRY(fill(b->mean4, b->cov8, b->keys));
-        PCR_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)b->n_dev, (int)cells, 1, ctx->stream));
-        DevCloud mc;                                             // the cells as a voxel-lattice cloud: what the hash build reads (keys, count, capacity)
-        mc.keys = b->keys; mc.n = b->n_dev; mc.cap = (int)cells; mc.voxel_lattice = true;
-        const DevCloud *pmc = &mc; const int level = 0;
-        PCR_TRY(pcr_dev_build_grid_batch(ctx, &pmc, &level, 1, &b->gv));
-        if (!b->gv.tab) { ctx->err = std::string(call) + ": no cell hash"; return PCR_EHIP; }
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->launch_err != hipSuccess) return PCR_EHIP;      // (pcr_leave names the launch)
-        return PCR_OK;
-    };
-    const int rc = body();
-    if (rc != PCR_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(b->block); b->block = nullptr; }
-    return rc;
-}
-static void vm_adopt(pcr_voxel_map *m, const VmBlock &b, int64_t cells) {
-    m->cells = cells; m->block = b.block; m->bytes = b.bytes; m->keys = b.keys; m->n_dev = b.n_dev;
-    m->view.tab = b.gv.tab; m->view.dmask = b.gv.dmask; m->view.mean4 = b.mean4; m->view.cov8 = b.cov8;
-}
-static int vm_copy_rows(pcr_context *ctx, const VmRows &r, float4 *mean4, float4 *cov8, uint64_t *keys) {
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(mean4, r.mean4, sizeof(float4) * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(cov8, r.cov8, sizeof(float4) * 2 * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(keys, r.keys, sizeof(uint64_t) * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
-    return PCR_OK;
-}
-
-// map <- MERGE(map, b); b's rows live in the arena or in another map.  Scratch from the arena the caller has reserved.
-static int vm_merge_into(pcr_context *ctx, const char *call, pcr_voxel_map *map, const VmRows &b) {
-    const VmRows a = vm_rows_of(map);
-    const size_t total = (size_t)a.n + (size_t)b.n;
-    if (total > (size_t)(0x7fffffff / 8)) { ctx->err = std::string(call) + ": the merged map would hold 2^28 rows or more"; return PCR_EINVAL; }
-    int *where = arena<int>(ctx, total), *pos_b = arena<int>(ctx, (size_t)b.n), *word = arena<int>(ctx, 2);
-    uint8_t *only_b = arena<uint8_t>(ctx, (size_t)b.n);
-    if (!where || !pos_b || !word || !only_b) return PCR_ENOMEM;
-    int *total_b = word, *overflow = word + 1;
-    PCR_HIP_CHECK(ctx, hipMemsetAsync(word, 0, 2 * sizeof(int), ctx->stream));
-    PCR_LAUNCH(ctx, k_vmap_merge_mark, dim3(vm_blocks(total)), dim3(VM_BS), 0, ctx->stream, a, b, where, only_b, overflow);
-    PCR_TRY(pcr_dev_flag_scan(ctx, only_b, nullptr, b.n, pos_b, total_b));
-    int h[2] = {0, 0};
-    PCR_HIP_CHECK(ctx, hipMemcpyAsync(h, word, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (h[1]) { ctx->err = std::string(call) + ": the member count of a cell would pass 2^31 - 1"; return PCR_EINVAL; }
-    const int64_t cells = (int64_t)a.n + h[0];
-    if (h[0] < 0 || h[0] > b.n) { ctx->err = std::string(call) + ": the scan of the new cells is out of range"; return PCR_EHIP; }
-    VmBlock nb;
-    PCR_TRY(vm_build_block(ctx, call, cells, &nb, [&](float4 *mean4, float4 *cov8, uint64_t *keys) -> int {
-        PCR_LAUNCH(ctx, k_vmap_merge_write, dim3(vm_blocks(total)), dim3(VM_BS), 0, ctx->stream, a, b, (const int *)where, (const uint8_t *)only_b, (const int *)pos_b,
-                   (const int *)total_b, (int)cells, mean4, cov8, keys);
-        return PCR_OK;
-    }));
-    char *old = map->block;
-    vm_adopt(map, nb, cells);
-    (void)hipFree(old);                                       // waits for the device: no call is still reading the old block
-    return PCR_OK;
-}
-
-static int vm_check_grid_args(pcr_context *ctx, const char *call, double voxel_size, const double *grid_min3) {
-    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) { ctx->err = std::string(call) + ": voxel_size <= 0"; return PCR_EINVAL; }
-    if (!grid_min3) { ctx->err = std::string(call) + ": grid_min3 is null"; return PCR_EINVAL; }
-    for (int d = 0; d < 3; d++) if (!std::isfinite(grid_min3[d])) { ctx->err = std::string(call) + ": grid_min3 holds a non-finite value"; return PCR_EINVAL; }
+static int vm_copy_rows(pcr_context *ctx, const VmRows &r, const VmapRow::Out &o) {
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(o.mean4, r.mean4, sizeof(float4) * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(o.cov8, r.cov8, sizeof(float4) * 2 * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(o.keys, r.keys, sizeof(uint64_t) * (size_t)r.n, hipMemcpyDeviceToDevice, ctx->stream));
     return PCR_OK;
 }
 
@@ -313,17 +183,19 @@ extern "C" int pcr_voxel_map_create_on_grid(pcr_context *ctx, const float *xyz, 
     const char *call = "voxel_map_create_on_grid";
     if (!out) { ctx->err = "voxel_map_create_on_grid: out is null"; return PCR_EINVAL; }
     *out = nullptr;
-    PCR_TRY(vm_check_grid_args(ctx, call, voxel_size, grid_min3));
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) { ctx->err = std::string(call) + ": voxel_size <= 0"; return PCR_EINVAL; }
+    PCR_TRY(vg_check_grid_min(ctx, call, grid_min3));
     PCR_TRY(vm_check_cloud(ctx, call, xyz, cov6, normals, n, epsilon, T));
     PCR_TRY(pcr_arena_reserve(ctx, vm_scratch(n, 0)));
     VmGrid g; memcpy(g.grid_min, grid_min3, sizeof g.grid_min); g.voxel = voxel_size;
     VmRows rows;
     PCR_TRY(vm_cloud_rows(ctx, call, xyz, cov6, normals, n, epsilon, T, g, &rows));
-    VmBlock nb;
-    PCR_TRY(vm_build_block(ctx, call, rows.n, &nb, [&](float4 *mean4, float4 *cov8, uint64_t *keys) -> int { return vm_copy_rows(ctx, rows, mean4, cov8, keys); }));
+    MapBlock<VmapRow> nb;
+    PCR_TRY(map_build_block<VmapRow>(ctx, call, rows.n, &nb, [&](const VmapRow::Out &o) -> int { return vm_copy_rows(ctx, rows, o); },
+                                     [](const MapBlock<VmapRow> &) -> int { return PCR_OK; }));
     pcr_voxel_map *m = new pcr_voxel_map();
     m->device = ctx->device;
-    vm_adopt(m, nb, rows.n);
+    map_adopt<VmapRow>(m, nb, rows.n);
     memcpy(m->grid_min, g.grid_min, sizeof m->grid_min);
     vm_origin(g, m->view.org);
     m->view.voxel = voxel_size;
@@ -342,7 +214,7 @@ extern "C" int pcr_voxel_map_insert(pcr_context *ctx, pcr_voxel_map *map, const 
     VmGrid g; memcpy(g.grid_min, map->grid_min, sizeof g.grid_min); g.voxel = map->view.voxel;
     VmRows rows;
     PCR_TRY(vm_cloud_rows(ctx, call, xyz, cov6, normals, n, epsilon, T, g, &rows));
-    return vm_merge_into(ctx, call, map, rows);
+    return map_merge_into<VmapRow>(ctx, call, map, rows);      // the rows lie in the arena reserved above
     });
 }
 
@@ -357,7 +229,7 @@ extern "C" int pcr_voxel_map_merge(pcr_context *ctx, pcr_voxel_map *map, const p
         ctx->err = "voxel_map_merge: other is not on the map's grid (voxel size and origin must be equal bit for bit)"; return PCR_EINVAL;
     }
     PCR_TRY(pcr_arena_reserve(ctx, vm_scratch(0, map->cells + other->cells)));
-    return vm_merge_into(ctx, call, map, vm_rows_of(other));
+    return map_merge_into<VmapRow>(ctx, call, map, VmapRow::rows_of(other));
     });
 }
 
@@ -366,32 +238,7 @@ extern "C" int pcr_voxel_map_remove_far(pcr_context *ctx, pcr_voxel_map *map, co
     const char *call = "voxel_map_remove_far";
     if (removed) *removed = 0;
     PCR_TRY(vg_check_map(ctx, map, call));
-    if (!center3) { ctx->err = "voxel_map_remove_far: center3 is null"; return PCR_EINVAL; }
-    for (int d = 0; d < 3; d++) if (!std::isfinite(center3[d])) { ctx->err = "voxel_map_remove_far: center3 holds a non-finite value"; return PCR_EINVAL; }
-    if (!std::isfinite(max_distance) || !(max_distance > 0.0)) { ctx->err = "voxel_map_remove_far: max_distance must be finite and greater than 0"; return PCR_EINVAL; }
-    PCR_TRY(pcr_arena_reserve(ctx, vm_scratch(0, map->cells)));
-    const VmRows a = vm_rows_of(map);
-    uint8_t *keep = arena<uint8_t>(ctx, (size_t)a.n);
-    int *pos = arena<int>(ctx, (size_t)a.n), *total = arena<int>(ctx, 1);
-    if (!keep || !pos || !total) return PCR_ENOMEM;
-    const double r2 = max_distance * max_distance;
-    PCR_LAUNCH(ctx, k_vmap_far_flags, dim3(vm_blocks((size_t)a.n)), dim3(VM_BS), 0, ctx->stream, a.mean4, a.n, center3[0], center3[1], center3[2], r2, keep);
-    PCR_TRY(pcr_dev_flag_scan(ctx, keep, nullptr, a.n, pos, total));
-    int64_t kept = 0;
-    PCR_TRY(pcr_read_count(ctx, total, &kept));
-    if (kept < 0 || kept > a.n) { ctx->err = "voxel_map_remove_far: the scan of the kept rows is out of range"; return PCR_EHIP; }
-    if (kept == 0) { ctx->err = "voxel_map_remove_far: would leave the map empty"; return PCR_EINVAL; }
-    if (kept == a.n) return PCR_OK;                           // every row stays, with its bits and its place
-    VmBlock nb;
-    PCR_TRY(vm_build_block(ctx, call, kept, &nb, [&](float4 *mean4, float4 *cov8, uint64_t *keys) -> int {
-        PCR_LAUNCH(ctx, k_vmap_gather, dim3(vm_blocks((size_t)a.n)), dim3(VM_BS), 0, ctx->stream, a, (const uint8_t *)keep, (const int *)pos, (int)kept, mean4, cov8, keys);
-        return PCR_OK;
-    }));
-    char *old = map->block;
-    if (removed) *removed = (int64_t)a.n - kept;
-    vm_adopt(map, nb, kept);
-    (void)hipFree(old);                                       // waits for the device
-    return PCR_OK;
+    return map_remove_far<VmapRow>(ctx, call, map, center3, max_distance, removed, vm_scratch(0, map->cells));
     });
 }
 

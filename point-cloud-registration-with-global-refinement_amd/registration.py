@@ -371,7 +371,173 @@ def _check_voxel_size(fn: str, voxel_size):
     return v
 
 
-class VoxelCovarianceMap:
+class _GrowingVoxelMap:
+    """What ``VoxelCovarianceMap`` and ``NormalDistributionsMap`` are alike: a handle to a map on the device with one row per occupied cell of
+    a fixed grid, which ``insert``, ``merge`` and ``remove_far`` replace as a whole.  A subclass names its entry points (``_C``, the prefix of
+    ``<_C>_create`` ... ``<_C>_read``), the name its error texts carry (``_NAME``) and its columns in the argument order of ``<_C>_read``
+    (``_COLUMNS``: name -> (width or None, dtype)); it keeps its constructor, ``on_grid``, ``insert``, ``grid_min``, ``origin`` and what only
+    it can do."""
+
+    _handle = None
+    _C = _NAME = None
+    _COLUMNS = {}
+
+    @staticmethod
+    def centered_grid_min(point, voxel_size) -> np.ndarray:
+        """``floor(point / voxel_size) * voxel_size - 2^20 * voxel_size`` per axis (float64): the ``grid_min`` of a grid with ``point`` in the
+        middle of its 2^21 cells per axis, so the map can grow by 2^20 cells in every direction."""
+        v = _check_voxel_size("VoxelCovarianceMap.centered_grid_min", voxel_size)
+        p = np.asarray(point, np.float64).reshape(-1)
+        if p.shape != (3,) or not np.isfinite(p).all():
+            raise ValueError(f"VoxelCovarianceMap.centered_grid_min: point must be three finite numbers, got {point!r}")
+        return np.floor(p / v) * v - float(1 << 20) * v
+
+    @staticmethod
+    def _pose(fn: str, transformation):
+        """(array kept alive, pointer) of an optional 4x4 pose; ``None`` is the NULL pointer (the identity)"""
+        if transformation is None:
+            return None, None
+        T = np.asarray(transformation, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError(f"{fn}: transformation must have shape (4, 4), got {T.shape}")
+        return _T(T)
+
+    @classmethod
+    def _placement(cls, grid_min, transformation):
+        """(grid_min as three float64 or None, pose kept alive, pose pointer) of ``on_grid``: a pose needs a ``grid_min``"""
+        fn = cls._NAME
+        T, Tp = cls._pose(fn, transformation)
+        g = None
+        if grid_min is not None:
+            g = np.ascontiguousarray(np.asarray(grid_min, np.float64).reshape(-1))
+            if g.shape != (3,):
+                raise ValueError(f"{fn}: grid_min must hold three numbers, got {grid_min!r}")
+        if g is None and T is not None:
+            raise ValueError(f"{fn}: a transformation needs a grid_min (the placed target's minimum is not known before the call)")
+        return g, T, Tp
+
+    def _call(self, ctx, name):
+        return getattr(ctx.lib, f"{self._C}_{name}")
+
+    def _adopt(self, ctx, handle):
+        self._handle = handle
+        self._lib = ctx.lib
+        self._refresh()
+
+    def _refresh(self):
+        m = C.c_int64(0)
+        getattr(self._lib, self._C + "_size")(self._handle, C.byref(m))
+        self._cells = int(m.value)
+
+    def _open(self):
+        if self._handle is None:
+            raise RuntimeError(f"{self._NAME}: the map is closed")
+        return self._handle
+
+    def close(self):
+        """Destroy the map (waits for the device)."""
+        h, self._handle = self._handle, None
+        if h is not None and h.value:
+            getattr(self._lib, self._C + "_destroy")(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __len__(self):
+        self._open()
+        return self._cells
+
+    @property
+    def voxel_size(self) -> float:
+        self._open()
+        return self._voxel_size
+
+    def merge(self, other):
+        """Add the cells of ``other``, a map of the same class on the same grid -- and, for a ``NormalDistributionsMap``, with the same
+        ``min_points_per_voxel`` and ``eigenvalue_ratio`` -- (``pcr_voxel_map_merge`` / ``pcr_ndt_map_merge``); ``other`` is unchanged.  A cell
+        in both gets the sum of the counts and the count-weighted means: of the nine channels in a ``VoxelCovarianceMap``; of the mean, with
+        the covariance about that mean and a recomputed ``A_v``, in a ``NormalDistributionsMap``."""
+        fn = self._NAME + ".merge"
+        h = self._open()
+        if not isinstance(other, _GrowingVoxelMap) or other._C != self._C:
+            raise TypeError(f"{fn}: other must be a {self._NAME}, got {type(other).__name__}")
+        ho = other._open()
+        ctx = _lib.Context.current()
+        ctx.check(self._call(ctx, "merge")(ctx.handle, h, ho), fn)
+        self._refresh()
+
+    def remove_far(self, center, max_distance) -> int:
+        """Drop every cell whose mean is not closer to ``center`` than ``max_distance`` (``pcr_voxel_map_remove_far`` /
+        ``pcr_ndt_map_remove_far``; d^2 < r^2 keeps) and return the number of rows removed.  A call that would keep nothing raises the
+        library's error and leaves the map as it was."""
+        fn = self._NAME + ".remove_far"
+        h = self._open()
+        c = np.ascontiguousarray(np.asarray(center, np.float64).reshape(-1))
+        if c.shape != (3,):
+            raise ValueError(f"{fn}: center must hold three numbers, got {center!r}")
+        try:
+            r = float(max_distance)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: max_distance must be a number greater than 0, got {max_distance!r}") from None
+        if not np.isfinite(r) or not (r > 0.0):
+            raise ValueError(f"{fn}: max_distance must be a finite number greater than 0, got {max_distance!r}")
+        ctx = _lib.Context.current()
+        removed = C.c_int64(0)
+        ctx.check(self._call(ctx, "remove_far")(ctx.handle, h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r), C.byref(removed)), fn)
+        self._refresh()
+        return int(removed.value)
+
+    def _read(self, what: str):
+        """one column as a device tensor"""
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        cols, dtype = self._COLUMNS[what]
+        t = torch.empty((self._cells,) if cols is None else (self._cells, cols), dtype=getattr(torch, dtype), device="cuda")
+        args = [_ptr(t if k == what else None) for k in self._COLUMNS]
+        ctx.check(self._call(ctx, "read")(ctx.handle, h, *args), f"{self._NAME}.{what}")
+        return t
+
+    @property
+    def cells(self) -> np.ndarray:
+        """(cells, 3) int32: the cell index (ix, iy, iz) of every row"""
+        return self._read("cells").cpu().numpy()
+
+    @property
+    def counts(self) -> np.ndarray:
+        """(cells,) int32: the member count N_v"""
+        return self._read("counts").cpu().numpy()
+
+    @property
+    def points(self) -> np.ndarray:
+        """(cells, 3) float32: the mean point of every cell"""
+        return self._read("points").cpu().numpy()
+
+    @property
+    def covariances(self) -> np.ndarray:
+        """(cells, 6) float32, xx,xy,xz,yy,yz,zz: in a ``VoxelCovarianceMap`` the mean covariance of every cell, in a
+        ``NormalDistributionsMap`` C_v, the mean of the members' products about the cell mean"""
+        return self._read("covariances").cpu().numpy()
+
+    def to_point_cloud(self) -> PointCloud:
+        """The cells' means as a cloud that carries the cells' covariances."""
+        pc = PointCloud()
+        pc._xyz = self._read("points")
+        pc._cov = self._read("covariances")
+        return pc
+
+
+class VoxelCovarianceMap(_GrowingVoxelMap):
     """The target of voxelized GICP (Koide et al., ICRA 2021): per occupied cell of ``voxel_down_sample``'s grid the member count, the mean
     point and the mean covariance, behind a cell hash on the device.  Built once from ``target.covariances`` (or, without them, from its
     normals with ``epsilon`` as the GICP estimator forms them) and good for any number of registrations until ``close()``.  Rows are in
@@ -383,7 +549,8 @@ class VoxelCovarianceMap:
     drops the cells far from a point (the GRID / MERGE / INSERT / REMOVE_FAR rules of include/pcr_hip.h).  Each of them replaces the rows as a
     whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call may use the map while one runs."""
 
-    _handle = None
+    _C, _NAME = "pcr_voxel_map", "VoxelCovarianceMap"
+    _COLUMNS = {"cells": (3, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "covariances": (6, "float32")}
 
     def __init__(self, target: PointCloud, voxel_size: float, epsilon: float = 1e-3):
         self._create(target, voxel_size, epsilon, None, None)
@@ -399,16 +566,6 @@ class VoxelCovarianceMap:
         return m
 
     @staticmethod
-    def centered_grid_min(point, voxel_size) -> np.ndarray:
-        """``floor(point / voxel_size) * voxel_size - 2^20 * voxel_size`` per axis (float64): the ``grid_min`` of a grid with ``point`` in the
-        middle of its 2^21 cells per axis, so the map can grow by 2^20 cells in every direction."""
-        v = _check_voxel_size("VoxelCovarianceMap.centered_grid_min", voxel_size)
-        p = np.asarray(point, np.float64).reshape(-1)
-        if p.shape != (3,) or not np.isfinite(p).all():
-            raise ValueError(f"VoxelCovarianceMap.centered_grid_min: point must be three finite numbers, got {point!r}")
-        return np.floor(p / v) * v - float(1 << 20) * v
-
-    @staticmethod
     def _cloud_arrays(fn: str, cloud, what: str = "cloud"):
         """(covariances or None, normals or None) of a cloud that goes into a map: exactly one is given"""
         if not isinstance(cloud, PointCloud) or len(cloud) == 0:
@@ -419,16 +576,6 @@ class VoxelCovarianceMap:
             raise RuntimeError(f"{fn}: the {what} has neither covariances nor normals")
         return cov, nrm
 
-    @staticmethod
-    def _pose(fn: str, transformation):
-        """(array kept alive, pointer) of an optional 4x4 pose; ``None`` is the NULL pointer (the identity)"""
-        if transformation is None:
-            return None, None
-        T = np.asarray(transformation, dtype=np.float64)
-        if T.shape != (4, 4):
-            raise ValueError(f"{fn}: transformation must have shape (4, 4), got {T.shape}")
-        return _T(T)
-
     def _create(self, target, voxel_size, epsilon, grid_min, transformation):
         fn = "VoxelCovarianceMap"
         self._voxel_size = _check_voxel_size(fn, voxel_size)
@@ -436,14 +583,7 @@ class VoxelCovarianceMap:
         if not np.isfinite(self.epsilon):
             raise ValueError(f"VoxelCovarianceMap: epsilon must be finite, got {epsilon!r}")
         cov, nrm = self._cloud_arrays(fn, target, "target")
-        T, Tp = self._pose(fn, transformation)
-        g = None
-        if grid_min is not None:
-            g = np.ascontiguousarray(np.asarray(grid_min, np.float64).reshape(-1))
-            if g.shape != (3,):
-                raise ValueError(f"{fn}: grid_min must hold three numbers, got {grid_min!r}")
-        if g is None and T is not None:
-            raise ValueError(f"{fn}: a transformation needs a grid_min (the placed target's minimum is not known before the call)")
+        g, T, Tp = self._placement(grid_min, transformation)
         ctx = _lib.Context.current()
         h = C.c_void_p()
         if g is None:
@@ -453,24 +593,13 @@ class VoxelCovarianceMap:
             ctx.check(ctx.lib.pcr_voxel_map_create_on_grid(ctx.handle, _ptr(target.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(target)),
                                                            C.c_double(self._voxel_size), C.c_double(self.epsilon), g.ctypes.data_as(C.POINTER(C.c_double)),
                                                            Tp, C.byref(h)), fn)
-        self._handle = h
-        self._lib = ctx.lib
-        self._refresh()
-
-    def _refresh(self):
-        m = C.c_int64(0)
-        self._lib.pcr_voxel_map_size(self._handle, C.byref(m))
-        self._cells = int(m.value)
+        self._adopt(ctx, h)
 
     def _grid(self):
         h = self._open()
         g, o, v = (C.c_double * 3)(), (C.c_double * 3)(), C.c_double(0)
         self._lib.pcr_voxel_map_grid(h, g, o, C.byref(v))
         return np.array(g, np.float64), np.array(o, np.float64), float(v.value)
-
-    @property
-    def voxel_size(self) -> float:
-        return self._voxel_size
 
     @property
     def grid_min(self) -> np.ndarray:
@@ -493,106 +622,6 @@ class VoxelCovarianceMap:
         ctx = _lib.Context.current()
         ctx.check(ctx.lib.pcr_voxel_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), _ptr(cov), _ptr(nrm), C.c_int64(len(cloud)), C.c_double(self.epsilon), Tp), fn)
         self._refresh()
-
-    def merge(self, other: "VoxelCovarianceMap"):
-        """Add the cells of ``other``, a map on the same grid (``pcr_voxel_map_merge``); ``other`` is unchanged.  A cell in both gets the sum of
-        the counts and the count-weighted means of the nine channels."""
-        fn = "VoxelCovarianceMap.merge"
-        h = self._open()
-        if not isinstance(other, VoxelCovarianceMap):
-            raise TypeError(f"{fn}: other must be a VoxelCovarianceMap, got {type(other).__name__}")
-        ho = other._open()
-        ctx = _lib.Context.current()
-        ctx.check(ctx.lib.pcr_voxel_map_merge(ctx.handle, h, ho), fn)
-        self._refresh()
-
-    def remove_far(self, center, max_distance) -> int:
-        """Drop every cell whose mean is not closer to ``center`` than ``max_distance`` (``pcr_voxel_map_remove_far``; d^2 < r^2 keeps) and return
-        the number of rows removed.  A call that would keep nothing raises the library's error and leaves the map as it was."""
-        fn = "VoxelCovarianceMap.remove_far"
-        h = self._open()
-        c = np.ascontiguousarray(np.asarray(center, np.float64).reshape(-1))
-        if c.shape != (3,):
-            raise ValueError(f"{fn}: center must hold three numbers, got {center!r}")
-        try:
-            r = float(max_distance)
-        except (TypeError, ValueError):
-            raise ValueError(f"{fn}: max_distance must be a number greater than 0, got {max_distance!r}") from None
-        if not np.isfinite(r) or not (r > 0.0):
-            raise ValueError(f"{fn}: max_distance must be a finite number greater than 0, got {max_distance!r}")
-        ctx = _lib.Context.current()
-        removed = C.c_int64(0)
-        ctx.check(ctx.lib.pcr_voxel_map_remove_far(ctx.handle, h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r), C.byref(removed)), fn)
-        self._refresh()
-        return int(removed.value)
-
-    def close(self):
-        """Destroy the map (waits for the device)."""
-        h, self._handle = self._handle, None
-        if h is not None and h.value:
-            self._lib.pcr_voxel_map_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _open(self):
-        if self._handle is None:
-            raise RuntimeError("VoxelCovarianceMap: the map is closed")
-        return self._handle
-
-    def __len__(self):
-        self._open()
-        return self._cells
-
-    def _read(self, what: str):
-        h = self._open()
-        ctx = _lib.Context.current()
-        torch = _torch()
-        m = self._cells
-        out = {"cells": torch.empty((m, 3), dtype=torch.int32, device="cuda") if what == "cells" else None,
-               "counts": torch.empty((m,), dtype=torch.int32, device="cuda") if what == "counts" else None,
-               "points": torch.empty((m, 3), dtype=torch.float32, device="cuda") if what == "points" else None,
-               "covariances": torch.empty((m, 6), dtype=torch.float32, device="cuda") if what == "covariances" else None}
-        ctx.check(ctx.lib.pcr_voxel_map_read(ctx.handle, h, _ptr(out["cells"]), _ptr(out["counts"]), _ptr(out["points"]), _ptr(out["covariances"])),
-                  "VoxelCovarianceMap." + what)
-        return out[what]
-
-    @property
-    def cells(self) -> np.ndarray:
-        """(cells, 3) int32: the cell index (ix, iy, iz) of every row"""
-        return self._read("cells").cpu().numpy()
-
-    @property
-    def counts(self) -> np.ndarray:
-        """(cells,) int32: the member count N_v"""
-        return self._read("counts").cpu().numpy()
-
-    @property
-    def points(self) -> np.ndarray:
-        """(cells, 3) float32: the mean point of every cell"""
-        return self._read("points").cpu().numpy()
-
-    @property
-    def covariances(self) -> np.ndarray:
-        """(cells, 6) float32: the mean covariance of every cell, xx,xy,xz,yy,yz,zz"""
-        return self._read("covariances").cpu().numpy()
-
-    def to_point_cloud(self) -> PointCloud:
-        """The cells' means as a cloud that carries the cells' covariances."""
-        pc = PointCloud()
-        pc._xyz = self._read("points")
-        pc._cov = self._read("covariances")
-        return pc
 
     def correspondences(self, source: PointCloud, T=np.eye(4), neighborhood: int = 1, min_points_per_voxel: int = 1):
         """The rows (source index, map row) of the rule at the pose ``T``, ordered by source index and then by the neighbourhood's offset
@@ -657,6 +686,48 @@ def registration_voxelized_gicp(source: PointCloud, target_or_map, voxel_size=No
             own.close()
 
 
+def _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register):
+    """The recipe of ``scan_to_map_odometry`` and ``scan_to_map_odometry_ndt`` -> ``(poses, results, map)``: the argument checks
+    (``check_rule()`` for the caller's own, ``check_scan(k, scan)`` per scan), ``map = make_map(scans[0], grid_min, init)`` with
+    ``centered_grid_min`` of scan 0's centre placed at ``init`` for a ``grid_min`` of ``None``, then per further scan
+    ``register(scan, map, start)`` from the motion model's start, ``map.insert`` and, with a ``max_range``, ``map.remove_far``.  An error
+    closes the map."""
+    if motion_model not in ("constant_velocity", "static"):
+        raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
+    _check_voxel_size(fn, voxel_size)
+    check_rule()
+    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
+        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
+    scans = list(scans)
+    if not scans:
+        raise ValueError(f"{fn}: at least one scan is needed")
+    for k, s in enumerate(scans):
+        check_scan(k, s)
+    P0 = np.array(np.asarray(init, np.float64), np.float64)
+    if P0.shape != (4, 4):
+        raise ValueError(f"{fn}: init must have shape (4, 4), got {P0.shape}")
+    if grid_min is None:
+        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
+        grid_min = _GrowingVoxelMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
+    gmap = make_map(scans[0], grid_min, P0)
+    poses, results = [P0], [None]
+    try:
+        for k in range(1, len(scans)):
+            start = poses[-1]
+            if motion_model == "constant_velocity" and k >= 2:
+                start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
+            res = register(scans[k], gmap, start)
+            poses.append(np.array(res.transformation, np.float64))
+            results.append(res)
+            gmap.insert(scans[k], poses[-1])
+            if max_range is not None:
+                gmap.remove_far(poses[-1][:3, 3], max_range)
+    except BaseException:
+        gmap.close()
+        raise
+    return poses, results, gmap
+
+
 def scan_to_map_odometry(scans, voxel_size, init=np.eye(4), estimation_method=None, criteria=None, neighborhood: int = 1, min_points_per_voxel: int = 1,
                          motion_model: str = "constant_velocity", max_range=None, grid_min=None):
     """LiDAR odometry by scan-to-map voxelized GICP -> ``(poses, results, map)``.  Exactly these public calls, in this order (calling them by
@@ -672,43 +743,17 @@ def scan_to_map_odometry(scans, voxel_size, init=np.eye(4), estimation_method=No
     Every scan carries covariances or normals.  A scan that would leave the grid raises the library's error (the map is closed then).  The caller
     owns the returned map and closes it."""
     fn = "scan_to_map_odometry"
-    if motion_model not in ("constant_velocity", "static"):
-        raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
-    _check_voxel_size(fn, voxel_size)
-    _check_vgicp_rule(fn, neighborhood, min_points_per_voxel)
-    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
-        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
-    scans = list(scans)
-    if not scans:
-        raise ValueError(f"{fn}: at least one scan is needed")
-    for k, s in enumerate(scans):
-        VoxelCovarianceMap._cloud_arrays(fn, s, f"scan {k}")
     estimation = TransformationEstimationForGeneralizedICP() if estimation_method is None else estimation_method
-    if not isinstance(estimation, TransformationEstimationForGeneralizedICP):
-        raise RuntimeError(f"{fn}: {type(estimation).__name__} is not TransformationEstimationForGeneralizedICP")
-    P0 = np.array(np.asarray(init, np.float64), np.float64)
-    if P0.shape != (4, 4):
-        raise ValueError(f"{fn}: init must have shape (4, 4), got {P0.shape}")
-    if grid_min is None:
-        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
-        grid_min = VoxelCovarianceMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
-    vmap = VoxelCovarianceMap.on_grid(scans[0], voxel_size, estimation.epsilon, grid_min, P0)
-    poses, results = [P0], [None]
-    try:
-        for k in range(1, len(scans)):
-            start = poses[-1]
-            if motion_model == "constant_velocity" and k >= 2:
-                start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
-            res = registration_voxelized_gicp(scans[k], vmap, None, start, estimation_method, criteria, neighborhood, min_points_per_voxel)
-            poses.append(np.array(res.transformation, np.float64))
-            results.append(res)
-            vmap.insert(scans[k], poses[-1])
-            if max_range is not None:
-                vmap.remove_far(poses[-1][:3, 3], max_range)
-    except BaseException:
-        vmap.close()
-        raise
-    return poses, results, vmap
+
+    def check_rule():
+        _check_vgicp_rule(fn, neighborhood, min_points_per_voxel)
+        if not isinstance(estimation, TransformationEstimationForGeneralizedICP):
+            raise RuntimeError(f"{fn}: {type(estimation).__name__} is not TransformationEstimationForGeneralizedICP")
+
+    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule,
+                        lambda k, s: VoxelCovarianceMap._cloud_arrays(fn, s, f"scan {k}"),
+                        lambda s, g, P0: VoxelCovarianceMap.on_grid(s, voxel_size, estimation.epsilon, g, P0),
+                        lambda s, m, start: registration_voxelized_gicp(s, m, None, start, estimation_method, criteria, neighborhood, min_points_per_voxel))
 
 
 # ---- NDT on a normal-distributions voxel map (pcr_ndt_map_*, pcr_ndt_linearize, pcr_registration_ndt; the rule: include/pcr_hip.h)
@@ -736,7 +781,7 @@ class NdtLinearization:
         return f"NdtLinearization(score={self.score!r}, rows={self.rows}, points_with_rows={self.points_with_rows}, sum_d2={self.sum_d2!r})"
 
 
-class NormalDistributionsMap:
+class NormalDistributionsMap(_GrowingVoxelMap):
     """The target of NDT registration (Biber & Strasser 2003; Magnusson 2009; PCL's ``NormalDistributionsTransform``): per occupied cell of
     ``voxel_down_sample``'s grid the member count, the mean, the covariance ``C_v`` of the member positions about it and -- for a cell with at
     least ``min_points_per_voxel`` members that do not coincide -- the float64 information matrix ``A_v``, the inverse of the sample covariance
@@ -752,7 +797,9 @@ class NormalDistributionsMap:
     replaces the rows as a whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call may use the map while
     one runs.  ``len(map)`` and every property read the map as it is after the call."""
 
-    _handle = None
+    _C, _NAME = "pcr_ndt_map", "NormalDistributionsMap"
+    _COLUMNS = {"cells": (3, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "covariances": (6, "float32"), "information": (6, "float64"),
+                "valid": (None, "uint8")}
 
     def __init__(self, target: PointCloud, voxel_size: float, min_points_per_voxel: int = 6, eigenvalue_ratio: float = 0.01):
         self._create(target, voxel_size, min_points_per_voxel, eigenvalue_ratio, None, None)
@@ -768,11 +815,6 @@ class NormalDistributionsMap:
         m._create(target, voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, transformation)
         return m
 
-    @staticmethod
-    def centered_grid_min(point, voxel_size) -> np.ndarray:
-        """``VoxelCovarianceMap.centered_grid_min``: the ``grid_min`` of a grid with ``point`` in the middle of its 2^21 cells per axis."""
-        return VoxelCovarianceMap.centered_grid_min(point, voxel_size)
-
     def _create(self, target, voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, transformation):
         fn = "NormalDistributionsMap"
         self._voxel_size = _check_voxel_size(fn, voxel_size)
@@ -780,14 +822,7 @@ class NormalDistributionsMap:
         self.min_points_per_voxel, self.eigenvalue_ratio = int(min_points_per_voxel), float(eigenvalue_ratio)
         if not isinstance(target, PointCloud) or len(target) == 0:
             raise RuntimeError(f"{fn}: the target must be a PointCloud with at least one point")
-        T, Tp = VoxelCovarianceMap._pose(fn, transformation)
-        g = None
-        if grid_min is not None:
-            g = np.ascontiguousarray(np.asarray(grid_min, np.float64).reshape(-1))
-            if g.shape != (3,):
-                raise ValueError(f"{fn}: grid_min must hold three numbers, got {grid_min!r}")
-        if g is None and T is not None:
-            raise ValueError(f"{fn}: a transformation needs a grid_min (the placed target's minimum is not known before the call)")
+        g, T, Tp = self._placement(grid_min, transformation)
         ctx = _lib.Context.current()
         h = C.c_void_p()
         if g is None:
@@ -797,14 +832,7 @@ class NormalDistributionsMap:
             ctx.check(ctx.lib.pcr_ndt_map_create_on_grid(ctx.handle, _ptr(target.device_xyz()), C.c_int64(len(target)), C.c_double(self._voxel_size),
                                                          C.c_int(self.min_points_per_voxel), C.c_double(self.eigenvalue_ratio),
                                                          g.ctypes.data_as(C.POINTER(C.c_double)), Tp, C.byref(h)), fn)
-        self._handle = h
-        self._lib = ctx.lib
-        self._refresh()
-
-    def _refresh(self):
-        m = C.c_int64(0)
-        self._lib.pcr_ndt_map_size(self._handle, C.byref(m))
-        self._cells = int(m.value)
+        self._adopt(ctx, h)
 
     @property
     def grid_min(self) -> np.ndarray:
@@ -814,85 +842,6 @@ class NormalDistributionsMap:
         self._lib.pcr_ndt_map_rule(h, g, None, None)
         return np.array(g, np.float64)
 
-    def insert(self, cloud: PointCloud, transformation=None):
-        """Add ``cloud`` placed at ``transformation`` (``pcr_ndt_map_insert``; ``None`` is the identity): the map becomes MERGE(map, the map of
-        the placed cloud on this grid with this map's rule).  A point outside the grid raises the library's error and leaves the map as it
-        was."""
-        fn = "NormalDistributionsMap.insert"
-        h = self._open()
-        if not isinstance(cloud, PointCloud) or len(cloud) == 0:
-            raise RuntimeError(f"{fn}: the cloud must be a PointCloud with at least one point")
-        T, Tp = VoxelCovarianceMap._pose(fn, np.eye(4) if transformation is None else transformation)
-        ctx = _lib.Context.current()
-        ctx.check(ctx.lib.pcr_ndt_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), C.c_int64(len(cloud)), Tp), fn)
-        self._refresh()
-
-    def merge(self, other: "NormalDistributionsMap"):
-        """Add the cells of ``other``, a map on the same grid with the same ``min_points_per_voxel`` and ``eigenvalue_ratio``
-        (``pcr_ndt_map_merge``); ``other`` is unchanged.  A cell in both gets the sum of the counts, the count-weighted mean, the covariance
-        about that mean, and a recomputed ``A_v``."""
-        fn = "NormalDistributionsMap.merge"
-        h = self._open()
-        if not isinstance(other, NormalDistributionsMap):
-            raise TypeError(f"{fn}: other must be a NormalDistributionsMap, got {type(other).__name__}")
-        ho = other._open()
-        ctx = _lib.Context.current()
-        ctx.check(ctx.lib.pcr_ndt_map_merge(ctx.handle, h, ho), fn)
-        self._refresh()
-
-    def remove_far(self, center, max_distance) -> int:
-        """Drop every cell whose mean is not closer to ``center`` than ``max_distance`` (``pcr_ndt_map_remove_far``; d^2 < r^2 keeps) and return
-        the number of rows removed.  A call that would keep nothing raises the library's error and leaves the map as it was."""
-        fn = "NormalDistributionsMap.remove_far"
-        h = self._open()
-        c = np.ascontiguousarray(np.asarray(center, np.float64).reshape(-1))
-        if c.shape != (3,):
-            raise ValueError(f"{fn}: center must hold three numbers, got {center!r}")
-        try:
-            r = float(max_distance)
-        except (TypeError, ValueError):
-            raise ValueError(f"{fn}: max_distance must be a number greater than 0, got {max_distance!r}") from None
-        if not np.isfinite(r) or not (r > 0.0):
-            raise ValueError(f"{fn}: max_distance must be a finite number greater than 0, got {max_distance!r}")
-        ctx = _lib.Context.current()
-        removed = C.c_int64(0)
-        ctx.check(ctx.lib.pcr_ndt_map_remove_far(ctx.handle, h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r), C.byref(removed)), fn)
-        self._refresh()
-        return int(removed.value)
-
-    def close(self):
-        """Destroy the map (waits for the device)."""
-        h, self._handle = self._handle, None
-        if h is not None and h.value:
-            self._lib.pcr_ndt_map_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _open(self):
-        if self._handle is None:
-            raise RuntimeError("NormalDistributionsMap: the map is closed")
-        return self._handle
-
-    def __len__(self):
-        self._open()
-        return self._cells
-
-    @property
-    def voxel_size(self) -> float:
-        self._open()
-        return self._voxel_size
-
     @property
     def origin(self) -> np.ndarray:
         """(3,) float64: the target's minimum - ``voxel_size / 2``, the corner of cell (0, 0, 0)"""
@@ -901,38 +850,18 @@ class NormalDistributionsMap:
         self._lib.pcr_ndt_map_grid(h, o, None)
         return np.array(o, np.float64)
 
-    _COLUMNS = {"cells": (3, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "covariances": (6, "float32"), "information": (6, "float64"),
-                "valid": (None, "uint8")}
-
-    def _read(self, what: str):
+    def insert(self, cloud: PointCloud, transformation=None):
+        """Add ``cloud`` placed at ``transformation`` (``pcr_ndt_map_insert``; ``None`` is the identity): the map becomes MERGE(map, the map of
+        the placed cloud on this grid with this map's rule).  A point outside the grid raises the library's error and leaves the map as it
+        was."""
+        fn = "NormalDistributionsMap.insert"
         h = self._open()
+        if not isinstance(cloud, PointCloud) or len(cloud) == 0:
+            raise RuntimeError(f"{fn}: the cloud must be a PointCloud with at least one point")
+        T, Tp = self._pose(fn, np.eye(4) if transformation is None else transformation)
         ctx = _lib.Context.current()
-        torch = _torch()
-        cols, dtype = self._COLUMNS[what]
-        t = torch.empty((self._cells,) if cols is None else (self._cells, cols), dtype=getattr(torch, dtype), device="cuda")
-        args = [_ptr(t if k == what else None) for k in self._COLUMNS]
-        ctx.check(ctx.lib.pcr_ndt_map_read(ctx.handle, h, *args), "NormalDistributionsMap." + what)
-        return t
-
-    @property
-    def cells(self) -> np.ndarray:
-        """(cells, 3) int32: the cell index (ix, iy, iz) of every row"""
-        return self._read("cells").cpu().numpy()
-
-    @property
-    def counts(self) -> np.ndarray:
-        """(cells,) int32: the member count N_v"""
-        return self._read("counts").cpu().numpy()
-
-    @property
-    def points(self) -> np.ndarray:
-        """(cells, 3) float32: the mean of every cell"""
-        return self._read("points").cpu().numpy()
-
-    @property
-    def covariances(self) -> np.ndarray:
-        """(cells, 6) float32: C_v, the mean of the members' products about the cell mean, xx,xy,xz,yy,yz,zz"""
-        return self._read("covariances").cpu().numpy()
+        ctx.check(ctx.lib.pcr_ndt_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), C.c_int64(len(cloud)), Tp), fn)
+        self._refresh()
 
     @property
     def information(self) -> np.ndarray:
@@ -943,13 +872,6 @@ class NormalDistributionsMap:
     def valid(self) -> np.ndarray:
         """(cells,) bool: the cells that give rows"""
         return self._read("valid").cpu().numpy().astype(bool)
-
-    def to_point_cloud(self) -> PointCloud:
-        """The cells' means as a cloud that carries the cells' covariances ``C_v``."""
-        pc = PointCloud()
-        pc._xyz = self._read("points")
-        pc._cov = self._read("covariances")
-        return pc
 
     def correspondences(self, source: PointCloud, T=np.eye(4), neighborhood: int = 7):
         """The rows (source index, map row) of the rule at the pose ``T``, ordered by source index and then by the neighbourhood's offset
@@ -1034,41 +956,15 @@ def scan_to_map_odometry_ndt(scans, voxel_size, init=np.eye(4), criteria=None, n
 
     A scan that would leave the grid raises the library's error (the map is closed then).  The caller owns the returned map and closes it."""
     fn = "scan_to_map_odometry_ndt"
-    if motion_model not in ("constant_velocity", "static"):
-        raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
-    _check_voxel_size(fn, voxel_size)
-    _check_ndt_rule(fn, neighborhood, outlier_ratio, min_points_per_voxel, eigenvalue_ratio)
-    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
-        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
-    scans = list(scans)
-    if not scans:
-        raise ValueError(f"{fn}: at least one scan is needed")
-    for k, s in enumerate(scans):
+
+    def check_scan(k, s):
         if not isinstance(s, PointCloud) or len(s) == 0:
             raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
-    P0 = np.array(np.asarray(init, np.float64), np.float64)
-    if P0.shape != (4, 4):
-        raise ValueError(f"{fn}: init must have shape (4, 4), got {P0.shape}")
-    if grid_min is None:
-        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
-        grid_min = NormalDistributionsMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
-    nmap = NormalDistributionsMap.on_grid(scans[0], voxel_size, min_points_per_voxel, eigenvalue_ratio, grid_min, P0)
-    poses, results = [P0], [None]
-    try:
-        for k in range(1, len(scans)):
-            start = poses[-1]
-            if motion_model == "constant_velocity" and k >= 2:
-                start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
-            res = registration_ndt(scans[k], nmap, None, start, criteria, neighborhood, outlier_ratio, min_points_per_voxel)
-            poses.append(np.array(res.transformation, np.float64))
-            results.append(res)
-            nmap.insert(scans[k], poses[-1])
-            if max_range is not None:
-                nmap.remove_far(poses[-1][:3, 3], max_range)
-    except BaseException:
-        nmap.close()
-        raise
-    return poses, results, nmap
+
+    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min,
+                        lambda: _check_ndt_rule(fn, neighborhood, outlier_ratio, min_points_per_voxel, eigenvalue_ratio), check_scan,
+                        lambda s, g, P0: NormalDistributionsMap.on_grid(s, voxel_size, min_points_per_voxel, eigenvalue_ratio, g, P0),
+                        lambda s, m, start: registration_ndt(s, m, None, start, criteria, neighborhood, outlier_ratio, min_points_per_voxel))
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
