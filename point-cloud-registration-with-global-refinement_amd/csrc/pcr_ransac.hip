@@ -4,10 +4,9 @@
 //   k_rs_hypo    one lane per hypothesis: counter-based draw, edge-length check, float64 moments, icp_umeyama, distance / normal checks
 //                -> valid flag, 12 doubles, and (an integer atomic: the ORDER of the list does not reach any result) a slot in the list of
 //                valid hypotheses of the round
-//   k_rs_score   one lane per listed hypothesis, R|t in registers, a tile of gathered correspondence rows in LDS (every lane reads the same
-//                address: a broadcast), the rows split over blockIdx.y -> per-split (count, sum d^2) in row order
-//   k_rs_reduce  the splits summed in fixed order
-//   k_rs_select  ONE workgroup runs the sequential better-than and stop rule over the round, so that the answer does not depend on RS_ROUND
+// and the frame of pcr_hypo.h with RsPolicy scores them, sums the row splits in fixed order and runs the sequential better-than and stop rule
+// over the round in ONE workgroup, so that the answer does not depend on RS_ROUND.  This unit's own: k_rs_gather, k_rs_hypo<3..8>, rs_d2,
+// RsPolicy (better-than, the confidence rule), k_rs_inlier_flags, k_rs_dump (test hook), the parameter checks and the entry points.
 // The host reads one small record back per chunk of rounds.  Every loop is bounded by a count; no kernel waits on another workgroup.
 // Floating-point contraction per source expression only, as in pcr_gicp.hip: rs_d2 gives the same bits in every kernel it is inlined into.
 #pragma clang fp contract(on)
@@ -17,20 +16,15 @@
 #include <cstdlib>
 #include "pcr_internal.h"
 #include "pcr_umeyama.h"
+#include "pcr_hypo.h"
 
 #define RS_ROUND 16384             // hypotheses per round (internal: the results do not depend on it)
 #define RS_BS 256
 #define RS_TILE 512                // correspondence rows per LDS tile: 6 doubles each, 24 KB
-#define RS_SPLIT_ROWS 1024         // rows one lane of k_rs_score walks, about
+#define RS_SPLIT_ROWS 1024         // rows one lane of the score walks, about
 #define RS_MAX_SPLITS 64
-#define RS_CHUNK (RS_ROUND / RS_BS)   // hypotheses per thread of k_rs_select
-#define RS_ROUNDS_PER_READBACK 4
 
-struct RsState {                   // the sequential loop's state between rounds (device; the host reads it per chunk of rounds)
-    long long est_k, iterations_run, best_iter, n_valid;
-    double best_err2, bestT[12];
-    int best_count, stop, bad_index, pad;
-};
+struct RsState : HypoState<12> { int bad_index, pad; };      // best_err is a sum of d^2; bad_index: k_rs_gather met a row outside the clouds
 
 struct RsArgs {
     const float4 *ps, *pt, *ns, *nt;     // gathered rows of the correspondence list: source / target point, source / target normal (null: no normal check)
@@ -50,11 +44,33 @@ __device__ static inline double rs_d2(const double *T, double sx, double sy, dou
     return x * x + y * y + z * z;
 }
 
-__global__ void k_rs_init(RsState *st, long long max_iteration) {
-    st->est_k = max_iteration; st->iterations_run = 0; st->best_iter = -1; st->n_valid = 0; st->best_err2 = 0; st->best_count = 0;
-    st->stop = max_iteration <= 0 ? 1 : 0; st->bad_index = 0; st->pad = 0;
-    for (int k = 0; k < 12; k++) st->bestT[k] = (k % 5 == 0) ? 1.0 : 0.0;
-}
+// what the frame of pcr_hypo.h takes from this unit
+struct RsPolicy {
+    typedef RsState State; typedef float4 Row;
+    static constexpr int DIM = 12, ROWD = 6, TILE = RS_TILE, SPLIT_ROWS = RS_SPLIT_ROWS, MAX_SPLITS = RS_MAX_SPLITS, ROUND = RS_ROUND, SEL_BS = RS_BS, UNROLL = 4, SUM_UNROLL = 1;
+    static constexpr bool LISTED = true, STOPS = false;
+    __host__ __device__ static constexpr int stride(int) { return RS_ROUND; }
+    __device__ static inline double residual(const double *T, const double *p) { return rs_d2(T, p[0], p[1], p[2], p[3], p[4], p[5]); }
+    __device__ static inline void init_model(RsState *st) {
+        st->bad_index = 0; st->pad = 0;
+        for (int k = 0; k < 12; k++) st->best[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    }
+    // better-than rule: more inliers, or as many with a strictly smaller RMSE; (bc == 0: the empty start, beaten by any inlier at all)
+    __device__ static inline bool better(int c, double e, int bc, double be) {
+        if (c <= 0) return false;
+        if (c != bc) return c > bc;
+        return sqrt(e / (double)c) < sqrt(be / (double)bc);
+    }
+    __device__ static inline void est_k(RsState &s, int c, int C, int n, double confidence, double log_fail) {
+        const double rho = (double)c / (double)C;
+        double p = 1.0;
+        for (int k = 0; k < n; k++) p *= rho;
+        // k' = log(1 - confidence) / log(1 - rho^n), the denominator as log1p(-p): 1 - p rounds to 1 for p below 1e-16 (a handful of inliers
+        // at n >= 5), where k' is astronomically large, not -inf.  Only a finite k' >= 0 below est_k shortens the run.
+        const double kp = log_fail / log1p(-p);
+        if (p > 0.0 && isfinite(kp) && kp >= 0.0 && kp < (double)s.est_k) s.est_k = (long long)ceil(kp);
+    }
+};
 
 __global__ void __launch_bounds__(RS_BS) k_rs_gather(const float *__restrict__ src, int n_src, const float *__restrict__ tgt, int n_tgt, const float *__restrict__ src_n,
                                                      const float *__restrict__ tgt_n, const int32_t *__restrict__ corres, int C, float4 *__restrict__ ps,
@@ -140,115 +156,6 @@ template <int N> __global__ void __launch_bounds__(RS_BS) k_rs_hypo(RsArgs a) {
     if (ok) a.list[atomicAdd(a.n_list, 1)] = h;
 }
 
-__global__ void __launch_bounds__(RS_BS) k_rs_score(const float4 *__restrict__ ps, const float4 *__restrict__ pt, int C, int rows_per_split, double d2max,
-                                                    const double *__restrict__ T, const int *__restrict__ list, const int *__restrict__ n_list,
-                                                    int *__restrict__ pcnt, double *__restrict__ perr) {
-    const int nl = *n_list;
-    if ((int)(blockIdx.x * RS_BS) >= nl) return;
-    __shared__ double sh[RS_TILE * 6];
-    const int j = blockIdx.x * RS_BS + threadIdx.x;
-    const bool live = j < nl;
-    const int h = list[live ? j : nl - 1];
-    double Tm[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) Tm[k] = T[(size_t)h * 12 + k];
-    const int r0 = blockIdx.y * rows_per_split, r1 = min(C, r0 + rows_per_split);
-    int cnt = 0; double e = 0.0;
-    for (int base = r0; base < r1; base += RS_TILE) {
-        const int m = min(RS_TILE, r1 - base);
-        __syncthreads();
-        for (int q = threadIdx.x; q < m; q += RS_BS) {
-            const float4 s = ps[base + q], t = pt[base + q];
-            sh[q * 6 + 0] = s.x; sh[q * 6 + 1] = s.y; sh[q * 6 + 2] = s.z; sh[q * 6 + 3] = t.x; sh[q * 6 + 4] = t.y; sh[q * 6 + 5] = t.z;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int q = 0; q < m; q++) {
-            const double *p = sh + q * 6;
-            const double d2 = rs_d2(Tm, p[0], p[1], p[2], p[3], p[4], p[5]);
-            const bool in = d2 < d2max;
-            cnt += in ? 1 : 0; e += in ? d2 : 0.0;
-        }
-    }
-    if (live) { pcnt[(size_t)blockIdx.y * RS_ROUND + j] = cnt; perr[(size_t)blockIdx.y * RS_ROUND + j] = e; }
-}
-
-__global__ void __launch_bounds__(RS_BS) k_rs_reduce(const int *__restrict__ list, const int *__restrict__ n_list, const int *__restrict__ pcnt,
-                                                     const double *__restrict__ perr, int splits, int *__restrict__ cnt, double *__restrict__ err2) {
-    const int j = blockIdx.x * RS_BS + threadIdx.x;
-    if (j >= *n_list) return;
-    int c = 0; double e = 0.0;
-    for (int y = 0; y < splits; y++) { c += pcnt[(size_t)y * RS_ROUND + j]; e += perr[(size_t)y * RS_ROUND + j]; }      // ascending row ranges, fixed order
-    cnt[list[j]] = c; err2[list[j]] = e;
-}
-
-// better-than rule: more inliers, or as many with a strictly smaller RMSE; (bc == 0: the empty start, beaten by any inlier at all)
-__device__ static inline bool rs_better(int c, double e, int bc, double be) {
-    if (c <= 0) return false;
-    if (c != bc) return c > bc;
-    return sqrt(e / (double)c) < sqrt(be / (double)bc);
-}
-
-struct RsSelectArgs {
-    RsState *st; const int *cnt; const double *err2; const double *T;
-    long long first; int count, C, n; double confidence;
-};
-// The sequential loop over the round in one workgroup.  Each thread folds RS_CHUNK consecutive hypotheses into (first strict best, valid count);
-// thread 0 then walks the chunks in order.  est_k is a function of the best COUNT so far alone (k' falls as the count grows, an equal count
-// leaves it where it is), so a chunk that ends before est_k and holds no count above the running best can neither stop the loop nor move
-// est_k: only its best enters.  Every other chunk is walked hypothesis by hypothesis.
-__global__ void __launch_bounds__(RS_BS) k_rs_select(RsSelectArgs a) {
-    if (a.st->stop) return;
-    __shared__ int l_idx[RS_BS], l_cnt[RS_BS], l_nv[RS_BS];
-    __shared__ double l_err[RS_BS];
-    {
-        const int b = threadIdx.x * RS_CHUNK, m = min(RS_CHUNK, a.count - b);
-        int bi = -1, bc = 0, nv = 0; double be = 0.0;
-        for (int q = 0; q < m; q++) {
-            const int c = a.cnt[b + q];
-            nv += c >= 0 ? 1 : 0;
-            if (c > 0) { const double e = a.err2[b + q]; if (rs_better(c, e, bc, be)) { bi = b + q; bc = c; be = e; } }
-        }
-        l_idx[threadIdx.x] = bi; l_cnt[threadIdx.x] = bc; l_nv[threadIdx.x] = nv; l_err[threadIdx.x] = be;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    RsState s = *a.st;
-    const double log_fail = log(1.0 - a.confidence);
-    int stop = 0; long long run = a.first + a.count;
-    for (int ch = 0; ch < RS_BS && !stop; ch++) {
-        const int b = ch * RS_CHUNK, m = min(RS_CHUNK, a.count - b);
-        if (m <= 0) break;
-        if (a.first + b + m <= s.est_k && (l_idx[ch] < 0 || l_cnt[ch] <= s.best_count)) {
-            if (l_idx[ch] >= 0 && rs_better(l_cnt[ch], l_err[ch], s.best_count, s.best_err2)) { s.best_count = l_cnt[ch]; s.best_err2 = l_err[ch]; s.best_iter = a.first + l_idx[ch]; }
-            s.n_valid += l_nv[ch];
-            continue;
-        }
-        for (int q = 0; q < m; q++) {
-            const long long i = a.first + b + q;
-            if (i >= s.est_k) { stop = 1; run = i; break; }
-            const int c = a.cnt[b + q];
-            if (c >= 0) s.n_valid++;
-            if (c <= 0) continue;
-            const double e = a.err2[b + q];
-            if (!rs_better(c, e, s.best_count, s.best_err2)) continue;
-            s.best_count = c; s.best_err2 = e; s.best_iter = i;
-            const double rho = (double)c / (double)a.C;
-            double p = 1.0;
-            for (int k = 0; k < a.n; k++) p *= rho;
-            // k' = log(1 - confidence) / log(1 - rho^n), the denominator as log1p(-p): 1 - p rounds to 1 for p below 1e-16 (a handful of inliers
-            // at n >= 5), where k' is astronomically large, not -inf.  Only a finite k' >= 0 below est_k shortens the run.
-            const double kp = log_fail / log1p(-p);
-            if (p > 0.0 && isfinite(kp) && kp >= 0.0 && kp < (double)s.est_k) s.est_k = (long long)ceil(kp);
-        }
-    }
-    if (!stop && run >= s.est_k) stop = 1;
-    s.iterations_run = run; s.stop = stop;
-    if (s.best_iter >= a.first)
-        for (int k = 0; k < 12; k++) s.bestT[k] = a.T[(size_t)(s.best_iter - a.first) * 12 + k];
-    *a.st = s;
-}
-
 // the inlier rows of the winner, by the expression that counted them
 __global__ void __launch_bounds__(RS_BS) k_rs_inlier_flags(const float4 *__restrict__ ps, const float4 *__restrict__ pt, int C, const RsState *__restrict__ st, double d2max,
                                                            uint8_t *__restrict__ flags) {
@@ -256,14 +163,9 @@ __global__ void __launch_bounds__(RS_BS) k_rs_inlier_flags(const float4 *__restr
     if (i >= C) return;
     double Tm[12];
 #pragma unroll
-    for (int k = 0; k < 12; k++) Tm[k] = st->bestT[k];
+    for (int k = 0; k < 12; k++) Tm[k] = st->best[k];
     const float4 s = ps[i], t = pt[i];
     flags[i] = rs_d2(Tm, s.x, s.y, s.z, t.x, t.y, t.z) < d2max ? 1 : 0;
-}
-__global__ void __launch_bounds__(RS_BS) k_rs_emit(const int32_t *__restrict__ corres, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int C, int32_t *__restrict__ out) {
-    const int i = blockIdx.x * RS_BS + threadIdx.x;
-    if (i >= C || !flags[i]) return;
-    out[2 * (size_t)pos[i]] = corres[2 * (size_t)i]; out[2 * (size_t)pos[i] + 1] = corres[2 * (size_t)i + 1];
 }
 // test hook: what the round left for its hypotheses, copied to the caller's arrays
 __global__ void __launch_bounds__(RS_BS) k_rs_dump(const uint8_t *__restrict__ valid, const double *__restrict__ T, const int *__restrict__ cnt, const double *__restrict__ err2, int count,
@@ -277,8 +179,7 @@ __global__ void __launch_bounds__(RS_BS) k_rs_dump(const uint8_t *__restrict__ v
 
 // ------------------------------------------------------------------------------------------------------------------ host
 struct RsRun {                     // the device image of one call
-    RsArgs a; RsState *st; int splits, rows_per_split; double d2max;
-    int *pcnt; double *perr;
+    RsArgs a; RsState *st; HypoScore<RsPolicy> s;
 };
 
 static size_t rs_scratch_bytes(int64_t C) {
@@ -305,18 +206,14 @@ static int rs_setup(pcr_context *ctx, RsRun &R, const float *src_xyz, const floa
     R.st = arena<RsState>(ctx, 1);
     a.valid = arena<uint8_t>(ctx, RS_ROUND); a.T = arena<double>(ctx, (size_t)RS_ROUND * 12); a.cnt = arena<int>(ctx, RS_ROUND); a.err2 = arena<double>(ctx, RS_ROUND);
     a.list = arena<int>(ctx, RS_ROUND); a.n_list = arena<int>(ctx, 1);
-    R.splits = (C + RS_SPLIT_ROWS - 1) / RS_SPLIT_ROWS;
-    if (R.splits > RS_MAX_SPLITS) R.splits = RS_MAX_SPLITS;
-    if (R.splits < 1) R.splits = 1;
-    R.rows_per_split = (C + R.splits - 1) / R.splits;
-    R.pcnt = arena<int>(ctx, (size_t)R.splits * RS_ROUND); R.perr = arena<double>(ctx, (size_t)R.splits * RS_ROUND);
-    if (!ps || !pt || (normal_check && (!ns || !nt)) || !R.st || !a.valid || !a.T || !a.cnt || !a.err2 || !a.list || !a.n_list || !R.pcnt || !R.perr) return PCR_ENOMEM;
+    if (!ps || !pt || (normal_check && (!ns || !nt)) || !R.st || !a.valid || !a.T || !a.cnt || !a.err2 || !a.list || !a.n_list) return PCR_ENOMEM;
+    PCR_TRY(hypo_score_alloc(ctx, R.s, C, RS_ROUND));
     a.ps = ps; a.pt = pt; a.ns = ns; a.nt = nt; a.C = C; a.with_scaling = p->with_scaling; a.seed = p->seed;
     a.edge_thr = p->edge_length_threshold >= 0.0 ? p->edge_length_threshold : -1.0;
     a.dist_thr2 = p->distance_threshold >= 0.0 ? p->distance_threshold * p->distance_threshold : -1.0;
     a.cos_thr = normal_check ? cos(p->normal_angle_threshold) : -2.0;
-    R.d2max = max_dist * max_dist;
-    PCR_LAUNCH(ctx, k_rs_init, dim3(1), dim3(1), 0, ctx->stream, R.st, (long long)p->max_iteration);
+    R.s.ra = ps; R.s.rb = pt; R.s.rows = C; R.s.thr = max_dist * max_dist; R.s.model = a.T; R.s.list = a.list; R.s.n_list = a.n_list; R.s.cnt = a.cnt; R.s.err = a.err2;
+    PCR_LAUNCH(ctx, k_hypo_init<RsPolicy>, dim3(1), dim3(1), 0, ctx->stream, R.st, (long long)p->max_iteration);
     PCR_LAUNCH(ctx, k_rs_gather, dim3((C + RS_BS - 1) / RS_BS), dim3(RS_BS), 0, ctx->stream, src_xyz, (int)n_src, tgt_xyz, (int)n_tgt, normal_check ? src_nrm : nullptr,
                normal_check ? tgt_nrm : nullptr, corres, C, ps, pt, ns, nt, R.st);
     return PCR_OK;
@@ -327,18 +224,11 @@ static int rs_round(pcr_context *ctx, RsRun &R, int n, long long first, int coun
     RsArgs a = R.a;
     a.first = first; a.count = count; a.st = early_exit ? R.st : nullptr;
     PCR_HIP_CHECK(ctx, hipMemsetAsync(a.n_list, 0, sizeof(int), ctx->stream));
-    const dim3 g((count + RS_BS - 1) / RS_BS), b(RS_BS);
-    switch (n) {
-        case 3: PCR_LAUNCH(ctx, k_rs_hypo<3>, g, b, 0, ctx->stream, a); break;
-        case 4: PCR_LAUNCH(ctx, k_rs_hypo<4>, g, b, 0, ctx->stream, a); break;
-        case 5: PCR_LAUNCH(ctx, k_rs_hypo<5>, g, b, 0, ctx->stream, a); break;
-        case 6: PCR_LAUNCH(ctx, k_rs_hypo<6>, g, b, 0, ctx->stream, a); break;
-        case 7: PCR_LAUNCH(ctx, k_rs_hypo<7>, g, b, 0, ctx->stream, a); break;
-        case 8: PCR_LAUNCH(ctx, k_rs_hypo<8>, g, b, 0, ctx->stream, a); break;
-        default: return PCR_EINVAL;
-    }
-    PCR_LAUNCH(ctx, k_rs_score, dim3(g.x, R.splits), b, 0, ctx->stream, a.ps, a.pt, a.C, R.rows_per_split, R.d2max, a.T, a.list, a.n_list, R.pcnt, R.perr);
-    PCR_LAUNCH(ctx, k_rs_reduce, g, b, 0, ctx->stream, a.list, a.n_list, R.pcnt, R.perr, R.splits, a.cnt, a.err2);
+    PCR_TRY(hypo_dispatch_n(n, [&](auto N) -> int {
+        PCR_LAUNCH(ctx, k_rs_hypo<decltype(N)::value>, dim3((count + RS_BS - 1) / RS_BS), dim3(RS_BS), 0, ctx->stream, a);
+        return PCR_OK;
+    }));
+    hypo_score(ctx, R.s, count, nullptr);
     return PCR_OK;
 }
 
@@ -357,32 +247,19 @@ static int rs_run(pcr_context *ctx, const float *src_xyz, const float *src_nrm, 
     PCR_TRY(rs_setup(ctx, R, src_xyz, src_nrm, n_src, tgt_xyz, tgt_nrm, n_tgt, corres, (int)C, max_dist, p));
     RsState h; memset(&h, 0, sizeof h);
     h.best_iter = -1;
-    long long first = 0; int rounds = 1;
-    while (first < p->max_iteration) {
-        for (int r = 0; r < rounds && first < p->max_iteration; r++) {
-            const int count = (int)std::min<long long>(RS_ROUND, p->max_iteration - first);
-            PCR_TRY(rs_round(ctx, R, p->ransac_n, first, count, true));
-            RsSelectArgs sa; sa.st = R.st; sa.cnt = R.a.cnt; sa.err2 = R.a.err2; sa.T = R.a.T; sa.first = first; sa.count = count; sa.C = (int)C; sa.n = p->ransac_n; sa.confidence = p->confidence;
-            PCR_LAUNCH(ctx, k_rs_select, dim3(1), dim3(RS_BS), 0, ctx->stream, sa);
-            first += count;
-        }
-        PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h, R.st, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (h.bad_index) { ctx->err = "correspondence index out of range"; return PCR_EINVAL; }
-        if (h.stop) break;
-        rounds = RS_ROUNDS_PER_READBACK;
-    }
-    if (p->max_iteration == 0) {                          // nothing ran; the list is still checked
-        PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h, R.st, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (h.bad_index) { ctx->err = "correspondence index out of range"; return PCR_EINVAL; }
-    }
+    HypoSelectArgs<RsPolicy> sa;
+    sa.st = R.st; sa.cnt = R.a.cnt; sa.err = R.a.err2; sa.model = R.a.T; sa.rows = (int)C; sa.n = p->ransac_n; sa.confidence = p->confidence;
+    const auto check = [&](const RsState &s) -> int {      // (max_iteration 0: nothing ran; the list is still checked)
+        if (s.bad_index) { ctx->err = "correspondence index out of range"; return PCR_EINVAL; }
+        return PCR_OK;
+    };
+    PCR_TRY(hypo_run(ctx, sa, p->max_iteration, h, [&](long long first, int count) { return rs_round(ctx, R, p->ransac_n, first, count, true); }, check));
     if (info) { info->iterations_run = h.iterations_run; info->best_iteration = h.best_iter; info->n_valid = h.n_valid; }
     result->iterations = (int32_t)h.iterations_run;
     if (h.best_iter < 0) return PCR_OK;
-    for (int k = 0; k < 12; k++) result->transformation[k] = h.bestT[k];
+    for (int k = 0; k < 12; k++) result->transformation[k] = h.best[k];
     result->fitness = (double)h.best_count / (double)C;
-    result->inlier_rmse = sqrt(h.best_err2 / (double)h.best_count);
+    result->inlier_rmse = sqrt(h.best_err / (double)h.best_count);
     result->n_correspondences = h.best_count;
     result->converged = 1;
     if (correspondences) {
@@ -390,9 +267,9 @@ static int rs_run(pcr_context *ctx, const float *src_xyz, const float *src_nrm, 
         uint8_t *flags = arena<uint8_t>(ctx, C); int *pos = arena<int>(ctx, C), *total = arena<int>(ctx, 1);
         if (!flags || !pos || !total) return PCR_ENOMEM;
         const dim3 g((unsigned)((C + RS_BS - 1) / RS_BS)), b(RS_BS);
-        PCR_LAUNCH(ctx, k_rs_inlier_flags, g, b, 0, ctx->stream, R.a.ps, R.a.pt, (int)C, R.st, R.d2max, flags);
+        PCR_LAUNCH(ctx, k_rs_inlier_flags, g, b, 0, ctx->stream, R.a.ps, R.a.pt, (int)C, R.st, R.s.thr, flags);
         PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)C, pos, total));
-        PCR_LAUNCH(ctx, k_rs_emit, g, b, 0, ctx->stream, corres, flags, pos, (int)C, correspondences);
+        PCR_LAUNCH(ctx, k_hypo_emit<>, dim3(hypo_blocks(C)), dim3(HYPO_BS), 0, ctx->stream, corres, flags, pos, (int)C, correspondences);
         int64_t n_in = 0;
         PCR_TRY(pcr_read_count(ctx, total, &n_in));
         if (n_in != h.best_count) { ctx->err = "RANSAC: the inlier pass disagrees with the score of the winner"; return PCR_ENUMERIC; }
@@ -449,12 +326,10 @@ extern "C" int pcr_debug_ransac_hypotheses(pcr_context *ctx, const float *src_xy
         PCR_TRY(pcr_arena_reserve(ctx, rs_scratch_bytes(n_corres)));
         RsRun R;
         PCR_TRY(rs_setup(ctx, R, src_xyz, src_normals, n_src, tgt_xyz, tgt_normals, n_tgt, corres, (int)n_corres, max_distance, params));
-        for (int64_t done = 0; done < count; done += RS_ROUND) {
-            const int c = (int)std::min<int64_t>(RS_ROUND, count - done);
-            PCR_TRY(rs_round(ctx, R, params->ransac_n, first + done, c, false));
+        PCR_TRY(hypo_debug_rounds(RS_ROUND, first, count, [&](long long f, int c) { return rs_round(ctx, R, params->ransac_n, f, c, false); }, [&](int64_t done, int c) {
             PCR_LAUNCH(ctx, k_rs_dump, dim3((c + RS_BS - 1) / RS_BS), dim3(RS_BS), 0, ctx->stream, R.a.valid, R.a.T, R.a.cnt, R.a.err2, c, valid_out + done, T_out + done * 16,
                        inliers_out + done, err2_out + done);
-        }
+        }));
         RsState h;
         PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h, R.st, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
         PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

@@ -13,8 +13,8 @@
 //   k_sc_seed     one workgroup per seed m, row m in LDS: SC2_mj for every set bit j, the k1 largest packed (value, ~row) keys kept sorted across the
 //                 lanes of each wavefront and merged by the first; then ONE wavefront: lane a holds the mask of K1 members compatible with member a,
 //                 L_ma, the k2 cut with the half-of-maximum rule, and the Umeyama fit over K2
-//   k_sc_score / k_sc_score_sum   the hypotheses scored as pcr_ransac.hip scores a round (one lane per hypothesis, rows broadcast from LDS, splits
-//                 summed in order)
+//   ScPolicy      the seeds' hypotheses scored by the frame of pcr_hypo.h, as pcr_ransac.hip scores a round but over a dense array of seeds and
+//                 with sc_d2, whose products and sums round one by one like the restatement's
 //   k_sc_eval / k_sc_refit        refinement: inlier flags, count, err2 and the moments of the inlier rows under a pose in one pass, then the fit
 // No floating-point atomics; no kernel waits on another workgroup; every loop is bounded by a count.
 #pragma clang fp contract(off)      // x*x + y*y + z*z rounds every product and every sum once, as the restatement does
@@ -24,12 +24,13 @@
 #include <vector>
 #include "pcr_internal.h"
 #include "pcr_umeyama.h"
+#include "pcr_hypo.h"
 
 #define SC_BS 256
 #define SC_WAVES (SC_BS / 64)
 #define SC_MAX_N 65536
 #define SC_MAX_W (SC_MAX_N / 64)
-#define SC_TILE 512                 // rows per LDS tile of k_sc_score: 6 doubles each
+#define SC_TILE 512                 // rows per LDS tile of the score: 6 doubles each
 #define SC_SPLIT_ROWS 1024
 #define SC_MAX_SPLITS 64
 #define SC_NV 18                    // sums of k_sc_eval: count, err2, 16 moments
@@ -239,44 +240,13 @@ __global__ void __launch_bounds__(SC_BS) k_sc_seed(ScSeedArgs a) {
     }
 }
 
-// one lane per seed, the rows split over blockIdx.y: per-split (count, sum d^2) in row order.  The form of k_rs_score (pcr_ransac.hip), restated here
-// because that kernel walks a listed subset of a round with the contracted rs_d2; this one scores a dense array of seeds with sc_d2, whose products
-// and sums round one by one like the restatement's
-__global__ void __launch_bounds__(SC_BS) k_sc_score(const float4 *__restrict__ ps, const float4 *__restrict__ pt, int N, int rows_per_split, double d2max, const double *__restrict__ T,
-                                                    int S, int *__restrict__ pcnt, double *__restrict__ perr) {
-    __shared__ double sh[SC_TILE * 6];
-    const int j = blockIdx.x * SC_BS + threadIdx.x;
-    const bool live = j < S;
-    double Tm[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) Tm[k] = T[(size_t)(live ? j : S - 1) * 12 + k];
-    const int r0 = blockIdx.y * rows_per_split, r1 = min(N, r0 + rows_per_split);
-    int cnt = 0; double e = 0.0;
-    for (int base = r0; base < r1; base += SC_TILE) {
-        const int m = min(SC_TILE, r1 - base);
-        __syncthreads();
-        for (int q = threadIdx.x; q < m; q += SC_BS) {
-            const float4 s = ps[base + q], t = pt[base + q];
-            sh[q * 6 + 0] = s.x; sh[q * 6 + 1] = s.y; sh[q * 6 + 2] = s.z; sh[q * 6 + 3] = t.x; sh[q * 6 + 4] = t.y; sh[q * 6 + 5] = t.z;
-        }
-        __syncthreads();
-        for (int q = 0; q < m; q++) {
-            const double *p = sh + q * 6;
-            const double d2 = sc_d2(Tm, p[0], p[1], p[2], p[3], p[4], p[5]);
-            const bool in = d2 < d2max;
-            cnt += in ? 1 : 0; e += in ? d2 : 0.0;
-        }
-    }
-    if (live) { pcnt[(size_t)blockIdx.y * S + j] = cnt; perr[(size_t)blockIdx.y * S + j] = e; }
-}
-__global__ void __launch_bounds__(SC_BS) k_sc_score_sum(const uint8_t *__restrict__ valid, const int *__restrict__ pcnt, const double *__restrict__ perr, int splits, int S,
-                                                        int32_t *__restrict__ cnt, double *__restrict__ err2) {
-    const int j = blockIdx.x * SC_BS + threadIdx.x;
-    if (j >= S) return;
-    int c = 0; double e = 0.0;
-    for (int y = 0; y < splits; y++) { c += pcnt[(size_t)y * S + j]; e += perr[(size_t)y * S + j]; }
-    cnt[j] = valid[j] ? c : -1; err2[j] = valid[j] ? e : 0.0;
-}
+struct ScPolicy {                  // no sequential loop here: the host picks the best seed from one read-back.  UNROLL 2: what the compiler chose unasked
+    typedef float4 Row;
+    static constexpr int DIM = 12, ROWD = 6, TILE = SC_TILE, SPLIT_ROWS = SC_SPLIT_ROWS, MAX_SPLITS = SC_MAX_SPLITS, UNROLL = 2, SUM_UNROLL = 1;
+    static constexpr bool LISTED = false, STOPS = false;
+    __host__ __device__ static constexpr int stride(int S) { return S; }
+    __device__ static inline double residual(const double *T, const double *p) { return sc_d2(T, p[0], p[1], p[2], p[3], p[4], p[5]); }
+};
 
 // refinement pass under the pose T12: inlier flags, and per workgroup (count, err2, the 16 moments of the inlier rows about o = (target, source) origin)
 __global__ void __launch_bounds__(SC_BS) k_sc_eval(const float4 *__restrict__ ps, const float4 *__restrict__ pt, int N, const double *__restrict__ T12, double d2max,
@@ -335,11 +305,6 @@ __global__ void k_sc_refit(const double *__restrict__ partials, int nb, const do
     out[0] = S[0]; out[1] = S[1];
     for (int k = 0; k < 12; k++) out[2 + k] = U[k];
     out[14] = ok ? 1.0 : 0.0;
-}
-__global__ void __launch_bounds__(SC_BS) k_sc_emit(const int32_t *__restrict__ corres, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int N, int32_t *__restrict__ out) {
-    const int i = blockIdx.x * SC_BS + threadIdx.x;
-    if (i >= N || !flags[i]) return;
-    out[2 * (size_t)pos[i]] = corres[2 * (size_t)i]; out[2 * (size_t)pos[i] + 1] = corres[2 * (size_t)i + 1];
 }
 __global__ void __launch_bounds__(SC_BS) k_sc_dump(const int *__restrict__ seeds, const double *__restrict__ T, int S, int32_t *__restrict__ seed_rows, double *__restrict__ T_out) {
     const int s = blockIdx.x * SC_BS + threadIdx.x;
@@ -431,16 +396,14 @@ static int sc_seeds(pcr_context *ctx, ScRun &R, const pcr_sc2_option *o) {
     if (S == 0) return PCR_OK;
     R.k1_rows = arena<int32_t>(ctx, (size_t)S * 64); R.k2_rows = arena<int32_t>(ctx, (size_t)S * 64);
     R.T = arena<double>(ctx, (size_t)S * 12); R.valid = arena<uint8_t>(ctx, S); R.cnt = arena<int32_t>(ctx, S); R.err2 = arena<double>(ctx, S);
-    int splits = std::max(1, std::min(SC_MAX_SPLITS, (N + SC_SPLIT_ROWS - 1) / SC_SPLIT_ROWS));
-    const int rows_per_split = (N + splits - 1) / splits;
-    int *pcnt = arena<int>(ctx, (size_t)splits * S); double *perr = arena<double>(ctx, (size_t)splits * S);
-    if (!R.k1_rows || !R.k2_rows || !R.T || !R.valid || !R.cnt || !R.err2 || !pcnt || !perr) return PCR_ENOMEM;
+    HypoScore<ScPolicy> sc = {};
+    PCR_TRY(hypo_score_alloc(ctx, sc, N, S));
+    if (!R.k1_rows || !R.k2_rows || !R.T || !R.valid || !R.cnt || !R.err2) return PCR_ENOMEM;
     ScSeedArgs a;
     a.bits = R.bits; a.ps = R.ps; a.pt = R.pt; a.N = N; a.W = R.W; a.k1 = o->k1; a.k2 = o->k2; a.seeds = R.seeds; a.k1_rows = R.k1_rows; a.k2_rows = R.k2_rows; a.T = R.T; a.valid = R.valid;
     PCR_LAUNCH(ctx, k_sc_seed, dim3(S), dim3(SC_BS), 0, ctx->stream, a);
-    const double d2max = o->inlier_threshold * o->inlier_threshold;
-    PCR_LAUNCH(ctx, k_sc_score, dim3(sc_grid(S), splits), dim3(SC_BS), 0, ctx->stream, R.ps, R.pt, N, rows_per_split, d2max, R.T, S, pcnt, perr);
-    PCR_LAUNCH(ctx, k_sc_score_sum, dim3(sc_grid(S)), dim3(SC_BS), 0, ctx->stream, R.valid, pcnt, perr, splits, S, R.cnt, R.err2);
+    sc.ra = R.ps; sc.rb = R.pt; sc.rows = N; sc.thr = o->inlier_threshold * o->inlier_threshold; sc.model = R.T; sc.valid = R.valid; sc.cnt = R.cnt; sc.err = R.err2;
+    hypo_score(ctx, sc, S, nullptr);
     return PCR_OK;
 }
 
@@ -541,7 +504,7 @@ extern "C" int pcr_registration_sc2_correspondence(pcr_context *ctx, const float
         result->converged = 1;
         if (correspondences) {
             PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)N, pos, total));
-            PCR_LAUNCH(ctx, k_sc_emit, dim3(nb), dim3(SC_BS), 0, ctx->stream, corres, flags, pos, (int)N, correspondences);
+            PCR_LAUNCH(ctx, k_hypo_emit<>, dim3(hypo_blocks(N)), dim3(HYPO_BS), 0, ctx->stream, corres, flags, pos, (int)N, correspondences);
             int64_t n_in = 0;
             PCR_TRY(pcr_read_count(ctx, total, &n_in));
             if (n_in != count) { ctx->err = "sc2: the inlier pass disagrees with the count of the pose"; return PCR_ENUMERIC; }

@@ -1,14 +1,11 @@
 // pcr_segment.hip -- plane segmentation on gfx950: PointCloud.segment_plane of Open3D as ONE sequential RANSAC loop over hypotheses
-// i = 0, 1, ... (include/pcr_hip.h states the rules SAMPLE, FIT, SCORE, BETTER, STOP and RESULT).  The frame is that of pcr_ransac.hip with a
-// 4-number model; the device evaluates the loop in rounds of PS_ROUND:
+// i = 0, 1, ... (include/pcr_hip.h states the rules SAMPLE, FIT, SCORE, BETTER, STOP and RESULT), evaluated in rounds of PS_ROUND by the frame of
+// pcr_hypo.h with a 4-number model (PsPolicy): score, split sum, and the sequential better-than and stop rule in ONE workgroup, so that the
+// answer depends neither on PS_ROUND nor on how many rounds are enqueued before the host looks at the state.  This unit's own:
 //   k_ps_hypo    one lane per hypothesis: counter-based draw and the fit of pcr_plane.h -> valid flag and 4 doubles.  Nearly every sample is
 //                valid (a repeated row or three collinear points are not), so there is no list of valid hypotheses: an invalid one is scored
-//                like the others and its count is replaced by -1 in k_ps_reduce
-//   k_ps_score   one lane per hypothesis, the plane in registers, a tile of points in LDS (every lane reads the same address: a broadcast),
-//                the rows split over blockIdx.y -> per-split (count, sum of distances) in row order
-//   k_ps_reduce  the splits summed in ascending order
-//   k_ps_select  ONE workgroup runs the sequential better-than and stop rule over the round, so that the answer depends neither on PS_ROUND
-//                nor on how many rounds are enqueued before the host looks at the state
+//                like the others and its count is replaced by -1 in the split sum
+//   PsPolicy     the residual pcr_plane_dist, better-than, the probability rule
 // and a final pass: inlier flags of the winner by the expression that counted them, their ascending indices, and the fixed-order float64
 // centroid and centred second moments of the inliers, which the host hands to the moment fit of pcr_plane.h (Open3D's last step).
 // Every loop is bounded by a count; no kernel waits on another workgroup; no float atomics.  Contraction is off: pcr_plane.h's expressions
@@ -20,23 +17,18 @@
 #include "pcr_device.h"
 #include "pcr_umeyama.h"
 #include "pcr_plane.h"
+#include "pcr_hypo.h"
 
 #define PS_ROUND 1024              // hypotheses per round (internal: the results do not depend on it)
 #define PS_BS 256
 #define PS_TILE 512                // points per LDS tile: 3 doubles each, 12 KB
-#define PS_SPLIT_ROWS 1024         // rows one lane of k_ps_score walks, about
+#define PS_SPLIT_ROWS 1024         // rows one lane of the score walks, about
 #define PS_MAX_SPLITS 256          // from PS_MAX_SPLITS * PS_SPLIT_ROWS points on a lane walks more rows instead
-#define PS_SEL_BS 64               // threads of k_ps_select: thread 0 walks one chunk record per thread, so few and long chunks
-#define PS_CHUNK (PS_ROUND / PS_SEL_BS)   // hypotheses per thread of k_ps_select
-#define PS_ROUNDS_PER_READBACK 4
+#define PS_SEL_BS 64               // threads of the select: thread 0 walks one chunk record per thread, so few and long chunks
 #define PS_MOM_MAX_BLOCKS 256
 #define PS_MAX_POINTS 0x7fffffffLL    // the clouds of this library are counted in int
 
-struct PsState {                   // the sequential loop's state between rounds (device; the host reads it per chunk of rounds)
-    long long est_k, iterations_run, best_iter, n_valid;
-    double best_err, best_plane[4];
-    int best_count, stop;
-};
+typedef HypoState<4> PsState;      // best_err is a sum of distances
 
 struct PsArgs {
     const float *xyz; int n;
@@ -46,11 +38,31 @@ struct PsArgs {
     uint8_t *valid; double *plane;        // per hypothesis of the round
 };
 
-__global__ void k_ps_init(PsState *st, long long num_iterations) {
-    st->est_k = num_iterations; st->iterations_run = 0; st->best_iter = -1; st->n_valid = 0; st->best_err = 0; st->best_count = 0;
-    st->stop = num_iterations <= 0 ? 1 : 0;
-    for (int k = 0; k < 4; k++) st->best_plane[k] = 0.0;
-}
+// what the frame of pcr_hypo.h takes from this unit
+struct PsPolicy {
+    typedef PsState State; typedef float Row;
+    static constexpr int DIM = 4, ROWD = 3, TILE = PS_TILE, SPLIT_ROWS = PS_SPLIT_ROWS, MAX_SPLITS = PS_MAX_SPLITS, ROUND = PS_ROUND, SEL_BS = PS_SEL_BS, UNROLL = 4, SUM_UNROLL = 8;
+    static constexpr bool LISTED = false, STOPS = true;
+    __host__ __device__ static constexpr int stride(int) { return PS_ROUND; }
+    __device__ static inline double residual(const double *pl, const double *p) { return pcr_plane_dist(pl, p[0], p[1], p[2]); }
+    __device__ static inline void init_model(PsState *st) { for (int k = 0; k < 4; k++) st->best[k] = 0.0; }
+    // better-than rule: more inliers, or as many with a strictly smaller rmse = err / sqrt(count); (bc == 0: the empty start, beaten by any inlier at all)
+    __device__ static inline bool better(int c, double e, int bc, double be) {
+        if (c <= 0) return false;
+        if (c != bc) return c > bc;
+        return e / sqrt((double)c) < be / sqrt((double)bc);
+    }
+    __device__ static inline void est_k(PsState &s, int c, int n, int ransac_n, double probability, double log_fail) {
+        if (!(probability < 1.0)) return;                     // probability == 1 never stops early
+        const double rho = (double)c / (double)n;
+        double p = 1.0;
+        for (int k = 0; k < ransac_n; k++) p *= rho;
+        // k' = log(1 - probability) / log(1 - rho^n), the denominator as log1p(-p): 1 - p rounds to 1 for p below 1e-16, where k' is
+        // astronomically large, not -inf; every point an inlier: k' = 0.  Only a finite k' >= 0 below est_k shortens the run.
+        const double kp = c == n ? 0.0 : log_fail / log1p(-p);
+        if (isfinite(kp) && kp >= 0.0 && kp < (double)s.est_k) s.est_k = (long long)ceil(kp);
+    }
+};
 
 template <int N> __global__ void __launch_bounds__(PS_BS) k_ps_hypo(PsArgs a) {
     const int h = blockIdx.x * PS_BS + threadIdx.x;
@@ -77,122 +89,13 @@ template <int N> __global__ void __launch_bounds__(PS_BS) k_ps_hypo(PsArgs a) {
     for (int k = 0; k < 4; k++) a.plane[(size_t)h * 4 + k] = pl[k];
 }
 
-__global__ void __launch_bounds__(PS_BS) k_ps_score(const float *__restrict__ xyz, int n, int rows_per_split, double thr, const double *__restrict__ plane, int count,
-                                                    const PsState *__restrict__ st, int *__restrict__ pcnt, double *__restrict__ perr) {
-    if (st && st->stop) return;
-    __shared__ double sh[PS_TILE * 3];
-    const int j = blockIdx.x * PS_BS + threadIdx.x;
-    const bool live = j < count;
-    double pl[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) pl[k] = plane[(size_t)(live ? j : count - 1) * 4 + k];
-    const long long r0l = (long long)blockIdx.y * rows_per_split;               // (a late split of a short cloud may start past the end: no rows)
-    const int r0 = (int)min(r0l, (long long)n), r1 = (int)min(r0l + rows_per_split, (long long)n);
-    const bool wave_live = (int)(blockIdx.x * PS_BS + (threadIdx.x & ~(PCR_WAVE - 1))) < count;      // a wavefront past the round's end only helps to load
-    int cnt = 0; double e = 0.0;
-    for (int base = r0; base < r1; base += PS_TILE) {
-        const int m = min(PS_TILE, r1 - base);
-        __syncthreads();
-        for (int q = threadIdx.x; q < 3 * m; q += PS_BS) sh[q] = (double)xyz[(size_t)base * 3 + q];
-        __syncthreads();
-        if (!wave_live) continue;
-#pragma unroll 4
-        for (int q = 0; q < m; q++) {
-            const double d = pcr_plane_dist(pl, sh[q * 3], sh[q * 3 + 1], sh[q * 3 + 2]);
-            const bool in = d < thr;
-            cnt += in ? 1 : 0; e += in ? d : 0.0;
-        }
-    }
-    if (live) { pcnt[(size_t)blockIdx.y * PS_ROUND + j] = cnt; perr[(size_t)blockIdx.y * PS_ROUND + j] = e; }
-}
-
-__global__ void __launch_bounds__(PS_BS) k_ps_reduce(const uint8_t *__restrict__ valid, const int *__restrict__ pcnt, const double *__restrict__ perr, int splits, int count,
-                                                     const PsState *__restrict__ st, int *__restrict__ cnt, double *__restrict__ err) {
-    const int j = blockIdx.x * PS_BS + threadIdx.x;
-    if (j >= count) return;
-    if (st && st->stop) return;
-    int c = 0; double e = 0.0;
-#pragma unroll 8
-    for (int y = 0; y < splits; y++) { c += pcnt[(size_t)y * PS_ROUND + j]; e += perr[(size_t)y * PS_ROUND + j]; }      // ascending row ranges, fixed order
-    const bool ok = valid[j] != 0;
-    cnt[j] = ok ? c : -1; err[j] = ok ? e : 0.0;
-}
-
-// better-than rule: more inliers, or as many with a strictly smaller rmse = err / sqrt(count); (bc == 0: the empty start, beaten by any inlier at all)
-__device__ static inline bool ps_better(int c, double e, int bc, double be) {
-    if (c <= 0) return false;
-    if (c != bc) return c > bc;
-    return e / sqrt((double)c) < be / sqrt((double)bc);
-}
-
-struct PsSelectArgs {
-    PsState *st; const int *cnt; const double *err; const double *plane;
-    long long first; int count, n, ransac_n; double probability;
-};
-// The sequential loop over the round in one workgroup (the select rule of pcr_ransac.hip).  Each thread folds PS_CHUNK consecutive hypotheses
-// into (first strict best, valid count); thread 0 then walks the PS_SEL_BS chunks in order.  est_k is a function of the best COUNT so far alone (k' falls
-// as the count grows, an equal count leaves it where it is), so a chunk that ends before est_k and holds no count above the running best can
-// neither stop the loop nor move est_k: only its best enters.  Every other chunk is walked hypothesis by hypothesis.
-__global__ void __launch_bounds__(PS_SEL_BS) k_ps_select(PsSelectArgs a) {
-    if (a.st->stop) return;
-    __shared__ int l_idx[PS_SEL_BS], l_cnt[PS_SEL_BS], l_nv[PS_SEL_BS];
-    __shared__ double l_err[PS_SEL_BS];
-    {
-        const int b = threadIdx.x * PS_CHUNK, m = min(PS_CHUNK, a.count - b);
-        int bi = -1, bc = 0, nv = 0; double be = 0.0;
-        for (int q = 0; q < m; q++) {
-            const int c = a.cnt[b + q];
-            nv += c >= 0 ? 1 : 0;
-            if (c > 0) { const double e = a.err[b + q]; if (ps_better(c, e, bc, be)) { bi = b + q; bc = c; be = e; } }
-        }
-        l_idx[threadIdx.x] = bi; l_cnt[threadIdx.x] = bc; l_nv[threadIdx.x] = nv; l_err[threadIdx.x] = be;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    PsState s = *a.st;
-    const double log_fail = log(1.0 - a.probability);
-    int stop = 0; long long run = a.first + a.count;
-    for (int ch = 0; ch < PS_SEL_BS && !stop; ch++) {
-        const int b = ch * PS_CHUNK, m = min(PS_CHUNK, a.count - b);
-        if (m <= 0) break;
-        if (a.first + b + m <= s.est_k && (l_idx[ch] < 0 || l_cnt[ch] <= s.best_count)) {
-            if (l_idx[ch] >= 0 && ps_better(l_cnt[ch], l_err[ch], s.best_count, s.best_err)) { s.best_count = l_cnt[ch]; s.best_err = l_err[ch]; s.best_iter = a.first + l_idx[ch]; }
-            s.n_valid += l_nv[ch];
-            continue;
-        }
-        for (int q = 0; q < m; q++) {
-            const long long i = a.first + b + q;
-            if (i >= s.est_k) { stop = 1; run = i; break; }
-            const int c = a.cnt[b + q];
-            if (c >= 0) s.n_valid++;
-            if (c <= 0) continue;
-            const double e = a.err[b + q];
-            if (!ps_better(c, e, s.best_count, s.best_err)) continue;
-            s.best_count = c; s.best_err = e; s.best_iter = i;
-            if (!(a.probability < 1.0)) continue;                 // probability == 1 never stops early
-            const double rho = (double)c / (double)a.n;
-            double p = 1.0;
-            for (int k = 0; k < a.ransac_n; k++) p *= rho;
-            // k' = log(1 - probability) / log(1 - rho^n), the denominator as log1p(-p): 1 - p rounds to 1 for p below 1e-16, where k' is
-            // astronomically large, not -inf; every point an inlier: k' = 0.  Only a finite k' >= 0 below est_k shortens the run.
-            const double kp = c == a.n ? 0.0 : log_fail / log1p(-p);
-            if (isfinite(kp) && kp >= 0.0 && kp < (double)s.est_k) s.est_k = (long long)ceil(kp);
-        }
-    }
-    if (!stop && run >= s.est_k) stop = 1;
-    s.iterations_run = run; s.stop = stop;
-    if (s.best_iter >= a.first)
-        for (int k = 0; k < 4; k++) s.best_plane[k] = a.plane[(size_t)(s.best_iter - a.first) * 4 + k];
-    *a.st = s;
-}
-
 // the inlier rows of the winner, by the expression that counted them
 __global__ void __launch_bounds__(PS_BS) k_ps_inlier_flags(const float *__restrict__ xyz, int n, const PsState *__restrict__ st, double thr, uint8_t *__restrict__ flags) {
     const int i = blockIdx.x * PS_BS + threadIdx.x;
     if (i >= n) return;
     double pl[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) pl[k] = st->best_plane[k];
+    for (int k = 0; k < 4; k++) pl[k] = st->best[k];
     flags[i] = pcr_plane_dist(pl, (double)xyz[(size_t)i * 3], (double)xyz[(size_t)i * 3 + 1], (double)xyz[(size_t)i * 3 + 2]) < thr ? 1 : 0;
 }
 
@@ -240,8 +143,7 @@ __global__ void __launch_bounds__(PS_BS) k_ps_dump(const uint8_t *__restrict__ v
 
 // ------------------------------------------------------------------------------------------------------------------ host
 struct PsRun {                     // the device image of one call
-    PsArgs a; PsState *st; int splits, rows_per_split; double thr;
-    int *cnt; double *err; int *pcnt; double *perr;
+    PsArgs a; PsState *st; HypoScore<PsPolicy> s;
 };
 
 static size_t ps_scratch_bytes(int64_t n) {
@@ -266,15 +168,12 @@ static int ps_setup(pcr_context *ctx, PsRun &R, const float *xyz, int n, double 
     PsArgs &a = R.a;
     R.st = arena<PsState>(ctx, 1);
     a.valid = arena<uint8_t>(ctx, PS_ROUND); a.plane = arena<double>(ctx, (size_t)PS_ROUND * 4);
-    R.cnt = arena<int>(ctx, PS_ROUND); R.err = arena<double>(ctx, PS_ROUND);
-    R.splits = (n + PS_SPLIT_ROWS - 1) / PS_SPLIT_ROWS;
-    if (R.splits > PS_MAX_SPLITS) R.splits = PS_MAX_SPLITS;
-    if (R.splits < 1) R.splits = 1;
-    R.rows_per_split = (int)(((int64_t)n + R.splits - 1) / R.splits);
-    R.pcnt = arena<int>(ctx, (size_t)R.splits * PS_ROUND); R.perr = arena<double>(ctx, (size_t)R.splits * PS_ROUND);
-    if (!R.st || !a.valid || !a.plane || !R.cnt || !R.err || !R.pcnt || !R.perr) return PCR_ENOMEM;
-    a.xyz = xyz; a.n = n; a.seed = p->seed; R.thr = thr;
-    PCR_LAUNCH(ctx, k_ps_init, dim3(1), dim3(1), 0, ctx->stream, R.st, (long long)p->num_iterations);
+    R.s.cnt = arena<int>(ctx, PS_ROUND); R.s.err = arena<double>(ctx, PS_ROUND);
+    if (!R.st || !a.valid || !a.plane || !R.s.cnt || !R.s.err) return PCR_ENOMEM;
+    PCR_TRY(hypo_score_alloc(ctx, R.s, n, PS_ROUND));
+    a.xyz = xyz; a.n = n; a.seed = p->seed;
+    R.s.ra = xyz; R.s.rows = n; R.s.thr = thr; R.s.model = a.plane; R.s.valid = a.valid;
+    PCR_LAUNCH(ctx, k_hypo_init<PsPolicy>, dim3(1), dim3(1), 0, ctx->stream, R.st, (long long)p->num_iterations);
     return PCR_OK;
 }
 
@@ -282,18 +181,11 @@ static int ps_setup(pcr_context *ctx, PsRun &R, const float *xyz, int n, double 
 static int ps_round(pcr_context *ctx, PsRun &R, int ransac_n, long long first, int count, bool early_exit) {
     PsArgs a = R.a;
     a.first = first; a.count = count; a.st = early_exit ? R.st : nullptr;
-    const dim3 g((count + PS_BS - 1) / PS_BS), b(PS_BS);
-    switch (ransac_n) {
-        case 3: PCR_LAUNCH(ctx, k_ps_hypo<3>, g, b, 0, ctx->stream, a); break;
-        case 4: PCR_LAUNCH(ctx, k_ps_hypo<4>, g, b, 0, ctx->stream, a); break;
-        case 5: PCR_LAUNCH(ctx, k_ps_hypo<5>, g, b, 0, ctx->stream, a); break;
-        case 6: PCR_LAUNCH(ctx, k_ps_hypo<6>, g, b, 0, ctx->stream, a); break;
-        case 7: PCR_LAUNCH(ctx, k_ps_hypo<7>, g, b, 0, ctx->stream, a); break;
-        case 8: PCR_LAUNCH(ctx, k_ps_hypo<8>, g, b, 0, ctx->stream, a); break;
-        default: return PCR_EINVAL;
-    }
-    PCR_LAUNCH(ctx, k_ps_score, dim3(g.x, R.splits), b, 0, ctx->stream, a.xyz, a.n, R.rows_per_split, R.thr, (const double *)a.plane, count, a.st, R.pcnt, R.perr);
-    PCR_LAUNCH(ctx, k_ps_reduce, g, b, 0, ctx->stream, (const uint8_t *)a.valid, (const int *)R.pcnt, (const double *)R.perr, R.splits, count, a.st, R.cnt, R.err);
+    PCR_TRY(hypo_dispatch_n(ransac_n, [&](auto N) -> int {
+        PCR_LAUNCH(ctx, k_ps_hypo<decltype(N)::value>, dim3((count + PS_BS - 1) / PS_BS), dim3(PS_BS), 0, ctx->stream, a);
+        return PCR_OK;
+    }));
+    hypo_score(ctx, R.s, count, a.st ? &a.st->stop : nullptr);
     return PCR_OK;
 }
 
@@ -312,21 +204,10 @@ extern "C" int pcr_segment_plane(pcr_context *ctx, const float *xyz, int64_t n, 
         PCR_TRY(ps_setup(ctx, R, xyz, (int)n, distance_threshold, params));
         PsState h; memset(&h, 0, sizeof h);
         h.best_iter = -1;
-        long long first = 0; int rounds = 1;
-        while (first < params->num_iterations) {
-            for (int r = 0; r < rounds && first < params->num_iterations; r++) {
-                const int count = (int)std::min<long long>(PS_ROUND, params->num_iterations - first);
-                PCR_TRY(ps_round(ctx, R, params->ransac_n, first, count, true));
-                PsSelectArgs sa; sa.st = R.st; sa.cnt = R.cnt; sa.err = R.err; sa.plane = R.a.plane; sa.first = first; sa.count = count; sa.n = (int)n;
-                sa.ransac_n = params->ransac_n; sa.probability = params->probability;
-                PCR_LAUNCH(ctx, k_ps_select, dim3(1), dim3(PS_SEL_BS), 0, ctx->stream, sa);
-                first += count;
-            }
-            PCR_HIP_CHECK(ctx, hipMemcpyAsync(&h, R.st, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-            PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            if (h.stop) break;
-            rounds = PS_ROUNDS_PER_READBACK;
-        }
+        HypoSelectArgs<PsPolicy> sa;
+        sa.st = R.st; sa.cnt = R.s.cnt; sa.err = R.s.err; sa.model = R.a.plane; sa.rows = (int)n; sa.n = params->ransac_n; sa.confidence = params->probability;
+        PCR_TRY(hypo_run(ctx, sa, params->num_iterations, h, [&](long long first, int count) { return ps_round(ctx, R, params->ransac_n, first, count, true); },
+                         [](const PsState &) { return PCR_OK; }));
         if (info) { info->iterations_run = h.iterations_run; info->best_iteration = h.best_iter; info->n_valid = h.n_valid; }
         if (h.best_iter < 0) return PCR_OK;                      // no valid hypothesis with an inlier: the zero plane, no inliers
         if (info) {
@@ -368,12 +249,9 @@ extern "C" int pcr_debug_plane_hypotheses(pcr_context *ctx, const float *xyz, in
         PCR_TRY(pcr_arena_reserve(ctx, ps_scratch_bytes(n)));
         PsRun R;
         PCR_TRY(ps_setup(ctx, R, xyz, (int)n, distance_threshold, params));
-        for (int64_t done = 0; done < count; done += PS_ROUND) {
-            const int c = (int)std::min<int64_t>(PS_ROUND, count - done);
-            PCR_TRY(ps_round(ctx, R, params->ransac_n, first + done, c, false));
-            PCR_LAUNCH(ctx, k_ps_dump, dim3((c + PS_BS - 1) / PS_BS), dim3(PS_BS), 0, ctx->stream, (const uint8_t *)R.a.valid, (const double *)R.a.plane, (const int *)R.cnt,
-                       (const double *)R.err, c, valid_out + done, plane_out + done * 4, inliers_out + done, err_out + done);
-        }
-        return PCR_OK;
+        return hypo_debug_rounds(PS_ROUND, first, count, [&](long long f, int c) { return ps_round(ctx, R, params->ransac_n, f, c, false); }, [&](int64_t done, int c) {
+            PCR_LAUNCH(ctx, k_ps_dump, dim3((c + PS_BS - 1) / PS_BS), dim3(PS_BS), 0, ctx->stream, (const uint8_t *)R.a.valid, (const double *)R.a.plane, (const int *)R.s.cnt,
+                       (const double *)R.s.err, c, valid_out + done, plane_out + done * 4, inliers_out + done, err_out + done);
+        });
     });
 }

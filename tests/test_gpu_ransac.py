@@ -258,6 +258,49 @@ def test_normal_checker_prunes_by_the_rotated_normals(P, inputs):
     assert 0 < v1.sum() < v0.sum()
 
 
+RS_TILE, RS_SPLIT_ROWS, RS_MAX_SPLITS = 512, 1024, 64      # csrc/pcr_ransac.hip
+BOUNDARY_SEED = 20240607
+
+
+def lattice_list(rows):
+    """A list for the boundary test: source points on a lattice of multiples of 1/8 m; the target of an inlier row is its source point plus
+    one translation of multiples of 1/8, every other row is moved at least 4 m further along each axis (by an amount that changes from row to
+    row, so that the outliers agree on no second pose).  Every coordinate is exact in float32.  The list pairs source row i with target row
+    rows - 1 - i."""
+    i = np.arange(rows)
+    src = np.stack([i % 37, (i // 37) % 41, i // (37 * 41)], axis=1) / 8.0
+    inlier = (i * 7) % 10 < 6
+    off = np.stack([32 + i % 7, -(32 + i % 11), 32 + i % 13], axis=1) / 8.0
+    tgt = src + np.array([3, -5, 7]) / 8.0 + np.where(inlier[:, None], 0.0, off)
+    corres = np.stack([i, rows - 1 - i], axis=1).astype(np.int32)
+    return src.astype(np.float32), tgt[::-1].astype(np.float32).copy(), corres
+
+
+@pytest.mark.parametrize("rows", [RS_TILE - 1, RS_TILE, RS_TILE + 1, RS_SPLIT_ROWS - 1, RS_SPLIT_ROWS, RS_SPLIT_ROWS + 1, 2 * RS_SPLIT_ROWS + 1,
+                                  RS_MAX_SPLITS * RS_SPLIT_ROWS + 1])
+def test_tile_and_split_boundaries(P, rows):
+    """The score at list lengths around a tile, around a split, and one row past RS_MAX_SPLITS * RS_SPLIT_ROWS, from where a lane walks more
+    than RS_SPLIT_ROWS rows in several tiles: the count of every valid one of the first 64 hypotheses is numpy's float64 count of
+    |T s - t|^2 < d^2 under the device's own T.  No compared row lies within 1e-9 relative of the threshold (asserted; it holds for the
+    restatement's fits of these samples too)."""
+    d, n, count = 0.1, 3, 64
+    src, tgt, corres = lattice_list(rows)
+    inp = dict(src=P.PointCloud(src), tgt=P.PointCloud(tgt))
+    valid, T, inl, _ = dump(P, inp, corres, d, ransac_params(P, n, False, None, None, None, BOUNDARY_SEED), 0, count)
+    ps, pt = src.astype(np.float64)[corres[:, 0]], tgt.astype(np.float64)[corres[:, 1]]
+    assert valid.any()
+    best = 0
+    for h in np.flatnonzero(valid):
+        diff = ps @ T[h][:3, :3].T + T[h][:3, 3] - pt
+        d2 = (diff * diff).sum(axis=1)
+        assert not (np.abs(np.sqrt(d2) - d) <= 1e-9 * d).any(), h
+        ref = int((d2 < d * d).sum())
+        assert inl[h] == ref, (rows, h, inl[h], ref)
+        best = max(best, ref)
+    print(f"rows {rows}: {int(valid.sum())} valid of {count}, largest count {best}")
+    assert best > 3
+
+
 # ---------------------------------------------------------------------------------------------------------------- 2. loop
 def _check_loop(P, inputs, n, d, checkers, confidence, seed, max_it=20000):
     """Product call against the restated sequential rule run over the device's own per-hypothesis dump (max_it spans more than one round)."""
