@@ -1093,6 +1093,103 @@ int pcr_multiway_linearize(pcr_context *ctx, const pcr_multiway *problem, const 
                            double max_correspondence_distance, const pcr_estimation *estimation, double *JTJ, double *JTr, double *stats,
                            int64_t *rows, int32_t *match);
 
+/* ============================================================================================ scan-to-map ICP on a voxel point map
+ * The third map of the family keeps raw POINTS, not statistics: a voxel hash with at most M points per cell, the local map of KISS-ICP (Vizzo
+ * et al., RA-L 2023).  Point-to-point and point-to-plane ICP run on it with a cost that follows the scan, not the map: a source point probes 1, 7
+ * or 27 cells of the cell hash and scans their members.  Open3D has no such call; this statement is the specification, and
+ * tests/point_map_reference.py restates it in numpy.
+ *
+ * MAP.  Input: n >= 1 float32 points; optionally one float32 normal per point (all rows or none; a map has normals or has none);
+ *   voxel_size; max_points_per_voxel M in 1 .. 64; a grid by the GRID rule of the voxel covariance map: grid_min g (float64 x3),
+ *   origin = g - voxel_size / 2, index = floor((p - origin) / voxel_size) in float64 on the float32 value, 21 bits per axis.  pcr_point_map_create
+ *   takes g = the cloud's minimum.  The members of a cell are the input points that fall into it, in input order; the first min(count, M) are
+ *   kept and the others are dropped.  The map's ROWS are the kept points, ordered by (Morton key of the cell as in the voxel covariance map,
+ *   input order); a row is the float32 point, with its normal in a map that has normals, bit for bit.  The CELL TABLE lists the occupied cells in
+ *   Morton order with their first row and member count (1 .. M); the cell hash holds cell -> (first row, count).  A map never has zero rows.
+ * ON A GRID, AT A POSE T (float64 4x4, row-major).  Member point p' = float32(q), q the float64 ROWS expression of the voxel maps,
+ *   q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3, every operation rounded once.  Member normal n' = float32(R n) with R the upper 3x3 of T, entry by
+ *   entry (a0 b0 + a1 b1) + a2 b2 in float64, uncontracted and NOT normalised.  T == NULL: the members are the inputs bit for bit (no expression
+ *   is applied, so -0 stays -0).  A member whose cell index lies outside [0, 2^21) on any axis -- below the origin counts too -- or that is not
+ *   finite is PCR_EINVAL (xyz lies outside the map's grid) and nothing changes.
+ * MERGE(A, B).  Same grid bit for bit (voxel size and origin), same M, both with normals or both without: anything else is PCR_EINVAL.  A cell in
+ *   one map keeps its rows bit for bit.  A cell in both gets A's members and then B's, cut at M.  MERGE IS NOT COMMUTATIVE: in a shared cell
+ *   whose members add up past M, MERGE(A, B) keeps A's and drops B's tail, MERGE(B, A) the other way round.  It is associative.
+ * INSERT(map, cloud, T) = MERGE(map, the map of the cloud at T on the map's grid with the map's M).  Consequence: inserting clouds one after
+ *   another equals appending every point, in arrival order, to its cell's list while that list has fewer than M entries -- KISS-ICP's rule.
+ * REMOVE_FAR(map, center c (float64 x3), max_distance r).  Per ROW: a row is kept iff d^2 < r^2 (strict), d^2 in float64 from the float32 point by
+ *   differences, squares and sums in the order x, y, z, each rounded once, r^2 = r r (the arithmetic of the voxel covariance map's REMOVE_FAR).
+ *   Kept rows keep their bits and their relative order; a cell left without rows disappears, a thinned one has room again.  A call that would
+ *   leave no rows is PCR_EINVAL (would leave the map empty) and changes nothing.
+ * ROW OF A SOURCE POINT AT T.  q as above, in float64 (it is NOT rounded to float32).  cell = floor((q - origin) / voxel_size).  Candidate cells:
+ *   cell + offset for the neighbourhood 1, 7 or 27, the offsets of the voxelized GICP section (their order plays no part here).  Over all members of
+ *   all candidate cells d^2 = ((q_x - p_x)^2 + (q_y - p_y)^2) + (q_z - p_z)^2 in float64 on the widened float32 member, every operation rounded
+ *   once.  The match is the row with the smallest (d^2, row index); it is a correspondence iff d^2 < max_correspondence_distance^2 (strict, the
+ *   square taken in float64).  At most one row (i, map row) per source point, ordered by i.
+ *   EXACTNESS.  With neighbourhood 27 and max_correspondence_distance <= voxel_size the match is the nearest of ALL map rows within that
+ *   distance, with the same tie rule: a row with |q - p| < voxel_size differs from q by less than a voxel on every axis, so its cell index
+ *   differs from q's by at most one per axis, and it is a member of a candidate cell.  A larger distance is allowed and is simply the rule;
+ *   neighbourhoods 1 and 7 are approximations by design.
+ * UPDATE.  s = q, t and n the matched row widened to float64, w the kernel's weight as the multiway section states it (L2: 1, L1:
+ *   1 / max(|r|, 1e-300), GM: k / (k + r^2)^2).
+ *     PCR_EST_POINT_TO_PLANE   one row: r = ((s - t)_x n_x + (s - t)_y n_y) + (s - t)_z n_z, J = [s x n, n], weighted by w(r).  Needs a map
+ *                              with normals (PCR_EINVAL names normals).
+ *     PCR_EST_POINT_TO_POINT   three rows: r = s - t, J = [-skew(s) | I], all three weighted by w(|s - t|), |s - t| = sqrt(d^2).  This is
+ *                              the Gauss-Newton form, which is what KISS-ICP runs, so the kernels apply.  It is NOT the Umeyama fit of
+ *                              pcr_registration_icp: the two agree only in the limit of small updates.  with_scaling != 0 is PCR_EINVAL.
+ *   The 6x6 system is solved and turned into a pose exactly as the point-to-plane update of pcr_registration_icp (LDLT, Rz Ry Rx,
+ *   left-multiplied).  No rows: the identity.
+ * LOOP.  RegistrationICP's, as in pcr_registration_icp: rows at init, then update / left-multiply / rows, until |d fitness| < relative_fitness
+ *   and |d RMSE| < relative_rmse, or max_iteration.  fitness = rows / n_src, inlier_rmse = sqrt(sum d^2 / rows).
+ * SUMS.  Float64, no floating-point atomics.  The source points are taken in caller order in tiles of 512; a tile's sum is a fixed tree over its
+ *   points (three rows of a point in the order x, y, z) and the tiles are added in ascending order: the same bits on every run.
+ * All cloud and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed; any context on the same
+ * device may use it.  _insert, _merge and _remove_far change it, all or nothing and finished when they return: the new block with its cell hash is
+ * built, swapped in, and the old one freed (which waits for the device); on any error the map is exactly as before.  While such a call runs no
+ * other call may use the map, and map rows in an earlier correspondence set are stale afterwards (row indices change).
+ * Every refusal is PCR_EINVAL with a message naming the argument: a non-finite value in xyz / normals / grid_min3 / T / center3 / src_xyz,
+ * voxel_size <= 0, max_points_per_voxel outside 1 .. 64, a neighborhood that is not 1, 7 or 27, a max_correspondence_distance or max_distance
+ * that is not finite or <= 0, a NULL map, a map on another device than the context, mismatched maps, normals given to a map without (or the
+ * other way round), an estimation that is null, of another kind, with scaling, or with no kernel of pcr_loss_kind. */
+typedef struct pcr_point_map pcr_point_map;
+typedef struct {
+    pcr_estimation estimation;   /* kind: PCR_EST_POINT_TO_POINT or PCR_EST_POINT_TO_PLANE; loss, loss_k: the robust kernel of either; epsilon is not read */
+    double relative_fitness;
+    double relative_rmse;
+    int32_t max_iteration;
+    int32_t neighborhood;        /* 1, 7 or 27 candidate cells per source point */
+} pcr_point_map_params;
+/* MAP on the grid of the cloud's own minimum; normals optional (n x 3 float32).  Finished when it returns. */
+int pcr_point_map_create(pcr_context *ctx, const float *xyz, const float *normals, int64_t n, double voxel_size, int max_points_per_voxel, pcr_point_map **out);
+/* MAP ON A GRID, AT A POSE (T optional).  Finished when it returns. */
+int pcr_point_map_create_on_grid(pcr_context *ctx, const float *xyz, const float *normals, int64_t n, double voxel_size, int max_points_per_voxel,
+                                 const double *grid_min3, const double *T, pcr_point_map **out);
+/* Frees the map (waits for the device, so no call is still reading it).  NULL is allowed. */
+int pcr_point_map_destroy(pcr_point_map *map);
+/* rows and occupied cells, each output optional (host) */
+int pcr_point_map_size(const pcr_point_map *map, int64_t *rows, int64_t *cells);
+/* each output optional (device): the cell table in Morton order -- cell3 (cells x 3 int32: ix, iy, iz), first_row (cells int32), count (cells
+ * int32) -- and the rows -- xyz (rows x 3 float32), normals (rows x 3 float32; PCR_EINVAL on a map without).  Asynchronous on the context's stream. */
+int pcr_point_map_read(pcr_context *ctx, const pcr_point_map *map, int32_t *cell3, int32_t *first_row, int32_t *count, float *xyz, float *normals);
+/* the grid and the rule of a map, each output optional (host): grid_min3, origin3 = grid_min3 - voxel_size / 2, voxel_size, M, whether it has normals */
+int pcr_point_map_grid(const pcr_point_map *map, double *grid_min3, double *origin3, double *voxel_size, int *max_points_per_voxel, int *has_normals);
+/* map <- INSERT(map, cloud, T); T optional; normals exactly when the map has normals. */
+int pcr_point_map_insert(pcr_context *ctx, pcr_point_map *map, const float *xyz, const float *normals, int64_t n, const double *T);
+/* map <- MERGE(map, other); other is unchanged and must not be the map itself. */
+int pcr_point_map_merge(pcr_context *ctx, pcr_point_map *map, const pcr_point_map *other);
+/* map <- REMOVE_FAR(map, center3, max_distance); *removed (optional, host) = rows dropped. */
+int pcr_point_map_remove_far(pcr_context *ctx, pcr_point_map *map, const double *center3, double max_distance, int64_t *removed);
+/* the rows (i, map row) at the pose T: rows2 = int32 pairs, capacity n_src rows; *n_rows on the host. */
+int pcr_point_map_correspondences(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T,
+                                  double max_correspondence_distance, int neighborhood, int32_t *rows2, int64_t *n_rows);
+/* UPDATE's sums at the pose T in ONE launch of the iteration kernel, all outputs on the host and each optional: JTJ (36, the full symmetric
+ * matrix), JTr (6), *rows, *sum_d2, *sum_r2 (point to plane: sum of r^2; point to point: sum of |s - t|^2). */
+int pcr_point_map_linearize(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, double max_correspondence_distance,
+                            int neighborhood, const pcr_estimation *estimation, double *JTJ, double *JTr, int64_t *rows, double *sum_d2, double *sum_r2);
+/* the loop of the rule from init_T.  max_iteration < 0 is PCR_EINVAL.  A source without any row is no error: the pose stays init_T, fitness 0.
+ * correspondences: optional device int32, capacity n_src rows: the rows at the returned pose (n_correspondences of them). */
+int pcr_registration_point_map(pcr_context *ctx, const float *src_xyz, int64_t n_src, const pcr_point_map *map, double max_correspondence_distance,
+                               const double *init_T, const pcr_point_map_params *params, pcr_result *result, int32_t *correspondences);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

@@ -81,6 +81,11 @@ class PcrEstimation(C.Structure):
     _fields_ = [("kind", C.c_int32), ("with_scaling", C.c_int32), ("loss", C.c_int32), ("loss_k", C.c_double), ("epsilon", C.c_double)]
 
 
+class PcrPointMapParams(C.Structure):
+    _fields_ = [("estimation", PcrEstimation), ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("max_iteration", C.c_int32),
+                ("neighborhood", C.c_int32)]
+
+
 class PcrPlaneParams(C.Structure):
     _fields_ = [("ransac_n", C.c_int32), ("num_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint64)]
 
@@ -174,6 +179,9 @@ EXPORTS = [
     "pcr_ndt_linearize", "pcr_registration_ndt",
     "pcr_ndt_map_create_on_grid", "pcr_ndt_map_insert", "pcr_ndt_map_merge", "pcr_ndt_map_remove_far", "pcr_ndt_map_rule",
     "pcr_registration_sc2_correspondence", "pcr_spatial_compatibility", "pcr_debug_sc2_seeds",
+    "pcr_point_map_create", "pcr_point_map_create_on_grid", "pcr_point_map_destroy", "pcr_point_map_size", "pcr_point_map_read", "pcr_point_map_grid",
+    "pcr_point_map_insert", "pcr_point_map_merge", "pcr_point_map_remove_far", "pcr_point_map_correspondences", "pcr_point_map_linearize",
+    "pcr_registration_point_map",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -253,6 +261,22 @@ QUERY_PROTOTYPES = {
                                    C.c_void_p], C.c_int),
     "pcr_debug_sc2_seeds": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(PcrSc2Option), C.POINTER(C.c_int64),
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_point_map_create": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_point_map_create_on_grid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_void_p)], C.c_int),
+    "pcr_point_map_destroy": ([C.c_void_p], C.c_int),
+    "pcr_point_map_size": ([C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+    "pcr_point_map_read": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_point_map_grid": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "pcr_point_map_insert": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)], C.c_int),
+    "pcr_point_map_merge": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_point_map_remove_far": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_point_map_correspondences": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_void_p,
+                                       C.POINTER(C.c_int64)], C.c_int),
+    "pcr_point_map_linearize": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcrEstimation),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+    "pcr_registration_point_map": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(PcrPointMapParams),
+                                    C.POINTER(PcrResult), C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

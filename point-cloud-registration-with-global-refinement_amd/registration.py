@@ -68,10 +68,12 @@ class TransformationEstimationForGeneralizedICP(TransformationEstimation):
 
 class TransformationEstimationPointToPoint(TransformationEstimation):
     """Open3D's default ``registration_icp`` estimator: the Umeyama fit of the correspondences (with a uniform scale when
-    ``with_scaling``)."""
+    ``with_scaling``).  ``kernel`` is read by ``registration_point_map`` alone, whose point-to-point update is the weighted Gauss-Newton
+    form; the Umeyama fit of ``registration_icp`` has no weights and ignores it."""
 
-    def __init__(self, with_scaling: bool = False):
+    def __init__(self, with_scaling: bool = False, kernel: RobustKernel | None = None):
         self.with_scaling = bool(with_scaling)
+        self.kernel = kernel if kernel is not None else L2Loss()
 
     def _estimation(self):
         return _lib.PcrEstimation(_lib.EST_POINT_TO_POINT, int(self.with_scaling), _lib.LOSS_L2, 1.0, 1e-3)
@@ -965,6 +967,335 @@ def scan_to_map_odometry_ndt(scans, voxel_size, init=np.eye(4), criteria=None, n
                         lambda: _check_ndt_rule(fn, neighborhood, outlier_ratio, min_points_per_voxel, eigenvalue_ratio), check_scan,
                         lambda s, g, P0: NormalDistributionsMap.on_grid(s, voxel_size, min_points_per_voxel, eigenvalue_ratio, g, P0),
                         lambda s, m, start: registration_ndt(s, m, None, start, criteria, neighborhood, outlier_ratio, min_points_per_voxel))
+
+
+# ---- scan-to-map ICP on a voxel point map (pcr_point_map_*, pcr_registration_point_map; the rule: include/pcr_hip.h)
+def _check_point_map_rule(fn: str, neighborhood=27, max_points_per_voxel=20):
+    if neighborhood not in (1, 7, 27):
+        raise ValueError(f"{fn}: neighborhood must be 1, 7 or 27, got {neighborhood!r}")
+    if not isinstance(max_points_per_voxel, (int, np.integer)) or not 1 <= max_points_per_voxel <= 64:
+        raise ValueError(f"{fn}: max_points_per_voxel must be an integer in 1 .. 64, got {max_points_per_voxel!r}")
+
+
+def _check_distance(fn: str, max_correspondence_distance) -> float:
+    try:
+        d = float(max_correspondence_distance)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: max_correspondence_distance must be a number greater than 0, got {max_correspondence_distance!r}") from None
+    if not np.isfinite(d) or not (d > 0.0):
+        raise ValueError(f"{fn}: max_correspondence_distance must be a finite number greater than 0, got {max_correspondence_distance!r}")
+    return d
+
+
+def _point_map_estimation(fn: str, estimation_method) -> _lib.PcrEstimation:
+    """the estimator of the point map as the C struct: point to point (the default; its ``kernel`` is read here) or point to plane"""
+    est = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
+    if isinstance(est, TransformationEstimationPointToPoint):
+        if est.with_scaling:
+            raise ValueError(f"{fn}: with_scaling is not supported (the point-to-point update is the Gauss-Newton form, not the Umeyama fit)")
+        return _lib.PcrEstimation(_lib.EST_POINT_TO_POINT, 0, int(est.kernel.kind), float(est.kernel.k), 1e-3)
+    if isinstance(est, TransformationEstimationPointToPlane):
+        return _lib.PcrEstimation(_lib.EST_POINT_TO_PLANE, 0, int(est.kernel.kind), float(est.kernel.k), 1e-3)
+    raise RuntimeError(f"{fn}: {type(est).__name__} is neither TransformationEstimationPointToPoint nor TransformationEstimationPointToPlane")
+
+
+class PointMapLinearization:
+    """What ``VoxelPointMap.linearize`` returns: ``JTJ`` (6, 6), ``JTr`` (6,), ``rows``, ``sum_d2``, ``sum_r2``."""
+
+    def __init__(self, JTJ, JTr, rows, sum_d2, sum_r2):
+        self.JTJ, self.JTr, self.rows, self.sum_d2, self.sum_r2 = JTJ, JTr, rows, sum_d2, sum_r2
+
+    def __repr__(self):
+        return f"PointMapLinearization(rows={self.rows}, sum_d2={self.sum_d2!r}, sum_r2={self.sum_r2!r})"
+
+
+class VoxelPointMap(_GrowingVoxelMap):
+    """A local map of raw points (KISS-ICP's: a voxel hash with at most ``max_points_per_voxel`` points per cell) behind a cell hash on the
+    device, the target of ``registration_point_map``.  The rows are the kept points -- with their normals when the target carries normals --
+    ordered by (Morton key of the cell, arrival); ``len(map)`` is the number of rows.  A cell keeps the first ``max_points_per_voxel`` points
+    that arrive in it and drops the others, whether they arrive in one cloud or in many (MAP / MERGE / INSERT of include/pcr_hip.h).
+
+    ``VoxelPointMap(target, voxel_size)`` takes the grid from the target's own minimum; a map that will grow is made by
+    ``VoxelPointMap.on_grid(target, voxel_size, grid_min=centered_grid_min(point, voxel_size))``.  ``insert`` adds a scan at a pose, ``merge``
+    another map of the same grid and rule (NOT commutative: in a full cell the map's own points stay), ``remove_far`` drops the ROWS far from a
+    point.  Each of them replaces the rows as a whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call
+    may use the map while one runs."""
+
+    _C, _NAME = "pcr_point_map", "VoxelPointMap"
+    _COLUMNS = {"cells": (3, "int32"), "starts": (None, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "normals": (3, "float32")}
+    _PER_ROW = ("points", "normals")
+
+    def __init__(self, target: PointCloud, voxel_size: float, max_points_per_voxel: int = 20):
+        self._create(target, voxel_size, max_points_per_voxel, None, None)
+
+    @classmethod
+    def on_grid(cls, target: PointCloud, voxel_size: float, max_points_per_voxel: int = 20, grid_min=None, transformation=None):
+        """The map of ``target`` placed at ``transformation`` (4x4; ``None``: as it lies, bit for bit) on the grid whose origin is
+        ``grid_min - voxel_size / 2`` (``pcr_point_map_create_on_grid``); a pose needs a ``grid_min``.  A point outside the grid's 2^21 cells
+        per axis raises the library's error."""
+        m = cls.__new__(cls)
+        m._create(target, voxel_size, max_points_per_voxel, grid_min, transformation)
+        return m
+
+    def _create(self, target, voxel_size, max_points_per_voxel, grid_min, transformation):
+        fn = "VoxelPointMap"
+        self._voxel_size = _check_voxel_size(fn, voxel_size)
+        _check_point_map_rule(fn, max_points_per_voxel=max_points_per_voxel)
+        self.max_points_per_voxel = int(max_points_per_voxel)
+        if not isinstance(target, PointCloud) or len(target) == 0:
+            raise RuntimeError(f"{fn}: the target must be a PointCloud with at least one point")
+        g, T, Tp = self._placement(grid_min, transformation)
+        self.has_normals = bool(target.has_normals())
+        nrm = target.device_normals() if self.has_normals else None
+        ctx = _lib.Context.current()
+        h = C.c_void_p()
+        if g is None:
+            ctx.check(ctx.lib.pcr_point_map_create(ctx.handle, _ptr(target.device_xyz()), _ptr(nrm), C.c_int64(len(target)), C.c_double(self._voxel_size),
+                                                   C.c_int(self.max_points_per_voxel), C.byref(h)), fn)
+        else:
+            ctx.check(ctx.lib.pcr_point_map_create_on_grid(ctx.handle, _ptr(target.device_xyz()), _ptr(nrm), C.c_int64(len(target)), C.c_double(self._voxel_size),
+                                                           C.c_int(self.max_points_per_voxel), g.ctypes.data_as(C.POINTER(C.c_double)), Tp, C.byref(h)), fn)
+        self._adopt(ctx, h)
+
+    def _refresh(self):
+        rows, cells = C.c_int64(0), C.c_int64(0)
+        self._lib.pcr_point_map_size(self._handle, C.byref(rows), C.byref(cells))
+        self._cells, self._n_cells = int(rows.value), int(cells.value)      # (the base's _cells is what len() returns: the rows)
+
+    def _read(self, what: str):
+        """one column as a device tensor: per row for the points and normals, per cell for the cell table"""
+        h = self._open()
+        if what == "normals" and not self.has_normals:
+            raise RuntimeError("VoxelPointMap.normals: the map has no normals")
+        ctx = _lib.Context.current()
+        torch = _torch()
+        cols, dtype = self._COLUMNS[what]
+        n = self._cells if what in self._PER_ROW else self._n_cells
+        t = torch.empty((n,) if cols is None else (n, cols), dtype=getattr(torch, dtype), device="cuda")
+        args = [_ptr(t if k == what else None) for k in self._COLUMNS]
+        ctx.check(ctx.lib.pcr_point_map_read(ctx.handle, h, *args), f"VoxelPointMap.{what}")
+        return t
+
+    @property
+    def covariances(self):
+        raise AttributeError("VoxelPointMap keeps points, not statistics: it has no covariances")
+
+    @property
+    def starts(self) -> np.ndarray:
+        """(cells,) int32: the first row of every cell; its rows are ``starts[c] .. starts[c] + counts[c] - 1``"""
+        return self._read("starts").cpu().numpy()
+
+    @property
+    def normals(self) -> np.ndarray:
+        """(rows, 3) float32: the normal of every row, as inserted (rotated by the pose, not normalised)"""
+        return self._read("normals").cpu().numpy()
+
+    def _grid(self):
+        h = self._open()
+        g, o = (C.c_double * 3)(), (C.c_double * 3)()
+        self._lib.pcr_point_map_grid(h, g, o, None, None, None)
+        return np.array(g, np.float64), np.array(o, np.float64)
+
+    @property
+    def grid_min(self) -> np.ndarray:
+        """(3,) float64: g of the GRID rule; for a map made without ``grid_min`` the target's minimum"""
+        return self._grid()[0]
+
+    @property
+    def origin(self) -> np.ndarray:
+        """(3,) float64: ``grid_min - voxel_size / 2``, the corner of cell (0, 0, 0)"""
+        return self._grid()[1]
+
+    def to_point_cloud(self) -> PointCloud:
+        """The rows as a cloud, with their normals if the map has normals."""
+        pc = PointCloud()
+        pc._xyz = self._read("points")
+        if self.has_normals:
+            pc._nrm = self._read("normals")
+        return pc
+
+    def insert(self, cloud: PointCloud, transformation=None):
+        """Add ``cloud`` placed at ``transformation`` (``pcr_point_map_insert``; ``None``: as it lies): every point, in the cloud's order, joins
+        its cell's list while that list has fewer than ``max_points_per_voxel`` entries.  A map with normals needs a cloud with normals.  A point
+        outside the grid raises the library's error and leaves the map as it was."""
+        fn = "VoxelPointMap.insert"
+        h = self._open()
+        if not isinstance(cloud, PointCloud) or len(cloud) == 0:
+            raise RuntimeError(f"{fn}: the cloud must be a PointCloud with at least one point")
+        if self.has_normals and not cloud.has_normals():
+            raise RuntimeError(f"{fn}: the map has normals and the cloud has none")
+        T, Tp = self._pose(fn, transformation)
+        ctx = _lib.Context.current()
+        ctx.check(ctx.lib.pcr_point_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), _ptr(cloud.device_normals() if self.has_normals else None),
+                                               C.c_int64(len(cloud)), Tp), fn)
+        self._refresh()
+
+    def correspondences(self, source: PointCloud, T=np.eye(4), max_correspondence_distance=None, neighborhood: int = 27):
+        """The rows (source index, map row) of the rule at the pose ``T``, at most one per source point, ordered by source index: a device
+        tensor (rows, 2) int32."""
+        fn = "VoxelPointMap.correspondences"
+        _check_point_map_rule(fn, neighborhood)
+        d = _check_distance(fn, max_correspondence_distance)
+        h = self._open()
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        rows = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+        n = C.c_int64(0)
+        _, Tp = _T(T)
+        ctx.check(ctx.lib.pcr_point_map_correspondences(ctx.handle, h, _ptr(source.device_xyz()), C.c_int64(ns), Tp, C.c_double(d), C.c_int(int(neighborhood)), _ptr(rows),
+                                                        C.byref(n)), fn)
+        return rows[: n.value]
+
+    def linearize(self, source: PointCloud, T=np.eye(4), max_correspondence_distance=None, estimation_method=None, neighborhood: int = 27) -> PointMapLinearization:
+        """The sums of one update at the pose ``T`` (``pcr_point_map_linearize``, one launch of the iteration kernel, the same bits on every
+        run): the 6x6 matrix, the right-hand side, the number of rows, their summed squared distances and squared residuals."""
+        fn = "VoxelPointMap.linearize"
+        _check_point_map_rule(fn, neighborhood)
+        d = _check_distance(fn, max_correspondence_distance)
+        est = _point_map_estimation(fn, estimation_method)
+        h = self._open()
+        if est.kind == _lib.EST_POINT_TO_PLANE and not self.has_normals:
+            raise RuntimeError(f"{fn}: TransformationEstimationPointToPlane needs a map with normals")
+        ctx = _lib.Context.current()
+        JTJ, JTr = np.zeros((6, 6), np.float64), np.zeros(6, np.float64)
+        sum_d2, sum_r2, rows = C.c_double(0), C.c_double(0), C.c_int64(0)
+        _, Tp = _T(T)
+        dp = C.POINTER(C.c_double)
+        ctx.check(ctx.lib.pcr_point_map_linearize(ctx.handle, h, _ptr(source.device_xyz()), C.c_int64(len(source)), Tp, C.c_double(d), C.c_int(int(neighborhood)), C.byref(est),
+                                                  JTJ.ctypes.data_as(dp), JTr.ctypes.data_as(dp), C.byref(rows), C.byref(sum_d2), C.byref(sum_r2)), fn)
+        return PointMapLinearization(JTJ, JTr, int(rows.value), float(sum_d2.value), float(sum_r2.value))
+
+
+def registration_point_map(source: PointCloud, target_or_map, max_correspondence_distance, voxel_size=None, init=np.eye(4), estimation_method=None, criteria=None,
+                           neighborhood: int = 27, max_points_per_voxel: int = 20) -> RegistrationResult:
+    """Scan-to-map ICP (``pcr_registration_point_map``, include/pcr_hip.h): RegistrationICP's loop in which a source point is matched to the
+    nearest point among the members of the cell of a ``VoxelPointMap`` it falls into (``neighborhood`` 1) or of that cell and its 6 / 26
+    neighbours (7 / 27) -- with 27 and ``max_correspondence_distance <= voxel_size`` the exact nearest map point within that distance.  The
+    cost follows the scan, not the map.  ``estimation_method``: ``TransformationEstimationPointToPoint()`` (the default; its update here is
+    the Gauss-Newton step weighted by its ``kernel``, what KISS-ICP runs, NOT the Umeyama fit of ``registration_icp``; ``with_scaling`` is
+    refused) or ``TransformationEstimationPointToPlane(kernel)``, which needs a map with normals.  ``target_or_map`` is a ``VoxelPointMap``
+    (``voxel_size`` and ``max_points_per_voxel`` are then the map's own) or a ``PointCloud``, for which a map of ``voxel_size`` is built and
+    closed inside the call.  ``correspondence_set`` holds (source index, map row)."""
+    fn = "registration_point_map"
+    _check_point_map_rule(fn, neighborhood, max_points_per_voxel)
+    d = _check_distance(fn, max_correspondence_distance)
+    est = _point_map_estimation(fn, estimation_method)
+    criteria = criteria or ICPConvergenceCriteria()
+    own = None
+    if isinstance(target_or_map, VoxelPointMap):
+        pmap = target_or_map
+        pmap._open()
+    elif isinstance(target_or_map, PointCloud):
+        if voxel_size is None:
+            raise ValueError(f"{fn}: voxel_size is required when the target is a PointCloud")
+        _check_voxel_size(fn, voxel_size)
+        own = pmap = VoxelPointMap(target_or_map, voxel_size, max_points_per_voxel)
+    else:
+        raise TypeError(f"{fn}: the target must be a PointCloud or a VoxelPointMap, got {type(target_or_map).__name__}")
+    try:
+        if est.kind == _lib.EST_POINT_TO_PLANE and not pmap.has_normals:
+            raise RuntimeError(f"{fn}: TransformationEstimationPointToPlane needs a map with normals")
+        ctx = _lib.Context.current()
+        torch = _torch()
+        ns = len(source)
+        corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device="cuda")
+        res = _lib.PcrResult()
+        _, Tp = _T(init)
+        p = _lib.PcrPointMapParams(est, float(criteria.relative_fitness), float(criteria.relative_rmse), int(criteria.max_iteration), int(neighborhood))
+        ctx.check(ctx.lib.pcr_registration_point_map(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), pmap._open(), C.c_double(d), Tp, C.byref(p), C.byref(res),
+                                                     _ptr(corr)), fn)
+        return _result(res, corr)
+    finally:
+        if own is not None:
+            own.close()
+
+
+class AdaptiveThreshold:
+    """The correspondence threshold of KISS-ICP, as this statement specifies it (it has not been compared with KISS-ICP's code): the model
+    error ``sigma = sqrt(sse / samples)`` starts from ``initial_threshold`` (``sse = initial_threshold^2``, one sample); ``update(predicted,
+    estimated)`` forms ``D = inv(predicted) @ estimated``, the deviation of the registration from the motion model's prediction, and
+    ``e = |t_D| + 2 max_range sin(theta_D / 2)`` -- how far a point at ``max_range`` moves under it -- and adds ``e^2`` as one more sample
+    when ``e > min_motion``.  ``scan_to_map_odometry_icp`` registers with ``max_correspondence_distance = 3 sigma`` and ``GMLoss(sigma / 3)``.
+    Plain host Python."""
+
+    def __init__(self, initial_threshold: float, min_motion: float, max_range: float):
+        for name, v in (("initial_threshold", initial_threshold), ("min_motion", min_motion), ("max_range", max_range)):
+            try:
+                x = float(v)
+            except (TypeError, ValueError):
+                x = float("nan")
+            if not np.isfinite(x) or (x < 0.0 if name == "min_motion" else not x > 0.0):
+                raise ValueError(f"AdaptiveThreshold: {name} must be a finite number {'>= 0' if name == 'min_motion' else 'greater than 0'}, got {v!r}")
+        self.initial_threshold, self.min_motion, self.max_range = float(initial_threshold), float(min_motion), float(max_range)
+        self.sse = self.initial_threshold * self.initial_threshold
+        self.samples = 1
+
+    @property
+    def sigma(self) -> float:
+        return float(np.sqrt(self.sse / self.samples))
+
+    @staticmethod
+    def model_error(predicted, estimated, max_range: float) -> float:
+        D = np.linalg.inv(np.asarray(predicted, np.float64)) @ np.asarray(estimated, np.float64)
+        theta = np.arccos(np.clip((np.trace(D[:3, :3]) - 1.0) / 2.0, -1.0, 1.0))
+        return float(np.linalg.norm(D[:3, 3]) + 2.0 * max_range * np.sin(theta / 2.0))
+
+    def update(self, predicted, estimated) -> float:
+        """Take in one registration; returns its model error ``e``."""
+        e = self.model_error(predicted, estimated, self.max_range)
+        if e > self.min_motion:
+            self.sse += e * e
+            self.samples += 1
+        return e
+
+
+def scan_to_map_odometry_icp(scans, voxel_size, max_correspondence_distance=None, init=np.eye(4), estimation_method=None, criteria=None, neighborhood: int = 27,
+                             max_points_per_voxel: int = 20, motion_model: str = "constant_velocity", max_range=None, grid_min=None, adaptive_threshold=None):
+    """LiDAR odometry by scan-to-map ICP on a ``VoxelPointMap`` (KISS-ICP's recipe without deskewing) -> ``(poses, results, map)``.  Exactly
+    these public calls, in this order:
+
+    * ``map = VoxelPointMap.on_grid(scans[0], voxel_size, max_points_per_voxel, grid_min, init)``; ``grid_min=None`` is ``centered_grid_min`` of
+      scan 0's centre placed at ``init``; ``poses[0] = init``, ``results[0] = None``;
+    * for every further scan k: ``results[k] = registration_point_map(scans[k], map, d, None, start, est, criteria, neighborhood,
+      max_points_per_voxel)`` from the motion model's ``start`` (as in ``scan_to_map_odometry``).  With a fixed distance ``d`` is
+      ``max_correspondence_distance`` and ``est`` is ``estimation_method``; with an ``AdaptiveThreshold`` ``d = 3 sigma`` and ``est`` is the
+      estimator with ``GMLoss(sigma / 3)``, and after the call ``adaptive_threshold.update(start, results[k].transformation)``;
+    * ``map.insert(scans[k], poses[k])``, and with a ``max_range``, ``map.remove_far(poses[k][:3, 3], max_range)``.
+
+    Exactly one of ``max_correspondence_distance`` and ``adaptive_threshold`` is given.  Point to plane needs normals on every scan.  The
+    caller owns the returned map and closes it."""
+    fn = "scan_to_map_odometry_icp"
+    estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
+    plane = isinstance(estimation, TransformationEstimationPointToPlane)
+
+    def check_rule():
+        _check_point_map_rule(fn, neighborhood, max_points_per_voxel)
+        _point_map_estimation(fn, estimation)
+        if (max_correspondence_distance is None) == (adaptive_threshold is None):
+            raise ValueError(f"{fn}: exactly one of max_correspondence_distance and adaptive_threshold must be given")
+        if adaptive_threshold is None:
+            _check_distance(fn, max_correspondence_distance)
+        elif not isinstance(adaptive_threshold, AdaptiveThreshold):
+            raise TypeError(f"{fn}: adaptive_threshold must be an AdaptiveThreshold, got {type(adaptive_threshold).__name__}")
+
+    def check_scan(k, s):
+        if not isinstance(s, PointCloud) or len(s) == 0:
+            raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
+        if plane and not s.has_normals():
+            raise RuntimeError(f"{fn}: scan {k} has no normals (TransformationEstimationPointToPlane needs a map with normals)")
+
+    def register(s, m, start):
+        if adaptive_threshold is None:
+            return registration_point_map(s, m, max_correspondence_distance, None, start, estimation_method, criteria, neighborhood, max_points_per_voxel)
+        sigma = adaptive_threshold.sigma
+        est = TransformationEstimationPointToPlane(GMLoss(sigma / 3.0)) if plane else TransformationEstimationPointToPoint(False, GMLoss(sigma / 3.0))
+        res = registration_point_map(s, m, 3.0 * sigma, None, start, est, criteria, neighborhood, max_points_per_voxel)
+        adaptive_threshold.update(start, res.transformation)
+        return res
+
+    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan,
+                        lambda s, g, P0: VoxelPointMap.on_grid(s, voxel_size, max_points_per_voxel, g, P0), register)
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),
