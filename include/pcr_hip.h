@@ -1142,14 +1142,43 @@ int pcr_multiway_linearize(pcr_context *ctx, const pcr_multiway *problem, const 
  *   and |d RMSE| < relative_rmse, or max_iteration.  fitness = rows / n_src, inlier_rmse = sqrt(sum d^2 / rows).
  * SUMS.  Float64, no floating-point atomics.  The source points are taken in caller order in tiles of 512; a tile's sum is a fixed tree over its
  *   points (three rows of a point in the order x, y, z) and the tiles are added in ascending order: the same bits on every run.
+ * ESTIMATE(map, radius rho, min_neighbors k_min).  A third state of a map next to "has the caller's normals" and "has none": ESTIMATED normals, which
+ *   the map computes from its own rows and keeps current by itself.  rho is finite and 0 < rho <= voxel_size; k_min >= 3.
+ *   NEIGHBOURS OF ROW i.  p_i is the row's float32 point widened to float64; its cell is the row's own cell.  Candidates are the members of that
+ *   cell and of its 26 neighbours; a candidate cell with an index outside [0, 2^21) on any axis does not exist (it is neither wrapped nor probed).
+ *   Row j is a neighbour iff d^2 < rho^2 (strict), d^2 exactly the arithmetic of ROW OF A SOURCE POINT with q = p_i, rho^2 one float64 product.  Row
+ *   i is its own neighbour.  count_i is the number of neighbours; by the EXACTNESS lemma they are ALL map rows within rho.
+ *   COVARIANCE AND NORMAL.  e = p_j - p_i in float64 (exact for points this near, and the moments stay at the size of rho^2, not |p|^2).  The sums
+ *   S_a = sum e_a and S_ab = sum e_a e_b (every product rounded once, then added) over the neighbours run in float64, uncontracted, in this order,
+ *   which depends on the map's rows alone: the neighbours are split into eight shares by (rank of the member inside its cell) mod 8; a share is
+ *   added up from zero in the order (candidate cell in the order {-1, 0, 1}^3 lexicographic with dx slowest, member rank ascending); the eight
+ *   shares are added as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  C_ab = S_ab / count - (S_a / count)(S_b / count).  The rest is the rule of
+ *   pcr_estimate_normals without a prior, with the same eigen solver: fewer than 3 neighbours give the identity covariance and so (0, 0, 1); the
+ *   zero covariance gives (0, 0, 1) and a diagonal one the axis of its strictly smallest entry, else z; the output is rounded to float32.  There
+ *   is NO sign rule: the point-to-plane row is invariant under n -> -n bit for bit.
+ *   VALIDITY.  valid_i = count_i >= k_min.
+ *   The normals and counts are a function of (rows, grid, rho, k_min) only: two maps with bit-equal rows on the same grid have bit-equal normals and
+ *   equal counts, however they were reached.
+ *   WHICH MAPS.  A map without normals, or an estimated one (estimated again with the new arguments).  A map with the caller's normals is
+ *   PCR_EINVAL (names normals).
+ *   GROWTH.  On an estimated map INSERT takes points only (normals != NULL is PCR_EINVAL).  MERGE(A, B) with A estimated takes a B without normals
+ *   or an estimated one, whose normals are derived data and are not read; A without normals and B estimated gives a map without; B with the
+ *   caller's normals is the mismatch it always was.  After INSERT, MERGE and REMOVE_FAR the whole new map is estimated again with the stored rho
+ *   and k_min, inside the call and before the new block is swapped in: all or nothing like the rest, and on any error the rows, normals, counts
+ *   and rule are exactly as before.
+ *   USE.  pcr_point_map_correspondences is purely geometric and does not change.  With PCR_EST_POINT_TO_PLANE on an estimated map a match whose
+ *   map row is not valid is NO ROW: it enters neither the 6x6 system nor rows, fitness, inlier_rmse, sum_d2, sum_r2, nor the correspondences of
+ *   pcr_registration_point_map.  Point to point never reads validity: on an estimated map it returns the bits it returns on the same map without
+ *   normals.  On a map with the caller's normals nothing changes.
  * All cloud and row buffers are DEVICE buffers.  The map lives in one device allocation of its own until it is destroyed; any context on the same
- * device may use it.  _insert, _merge and _remove_far change it, all or nothing and finished when they return: the new block with its cell hash is
+ * device may use it.  _insert, _merge, _remove_far and _estimate_normals change it, all or nothing and finished when they return: the new block with its cell hash is
  * built, swapped in, and the old one freed (which waits for the device); on any error the map is exactly as before.  While such a call runs no
  * other call may use the map, and map rows in an earlier correspondence set are stale afterwards (row indices change).
  * Every refusal is PCR_EINVAL with a message naming the argument: a non-finite value in xyz / normals / grid_min3 / T / center3 / src_xyz,
  * voxel_size <= 0, max_points_per_voxel outside 1 .. 64, a neighborhood that is not 1, 7 or 27, a max_correspondence_distance or max_distance
  * that is not finite or <= 0, a NULL map, a map on another device than the context, mismatched maps, normals given to a map without (or the
- * other way round), an estimation that is null, of another kind, with scaling, or with no kernel of pcr_loss_kind. */
+ * other way round, or to a map that estimates them), a radius that is not finite, <= 0 or above voxel_size, min_neighbors < 3, normal counts asked of a
+ * map that is not estimated, an estimation that is null, of another kind, with scaling, or with no kernel of pcr_loss_kind. */
 typedef struct pcr_point_map pcr_point_map;
 typedef struct {
     pcr_estimation estimation;   /* kind: PCR_EST_POINT_TO_POINT or PCR_EST_POINT_TO_PLANE; loss, loss_k: the robust kernel of either; epsilon is not read */
@@ -1170,14 +1199,21 @@ int pcr_point_map_size(const pcr_point_map *map, int64_t *rows, int64_t *cells);
 /* each output optional (device): the cell table in Morton order -- cell3 (cells x 3 int32: ix, iy, iz), first_row (cells int32), count (cells
  * int32) -- and the rows -- xyz (rows x 3 float32), normals (rows x 3 float32; PCR_EINVAL on a map without).  Asynchronous on the context's stream. */
 int pcr_point_map_read(pcr_context *ctx, const pcr_point_map *map, int32_t *cell3, int32_t *first_row, int32_t *count, float *xyz, float *normals);
-/* the grid and the rule of a map, each output optional (host): grid_min3, origin3 = grid_min3 - voxel_size / 2, voxel_size, M, whether it has normals */
+/* the grid and the rule of a map, each output optional (host): grid_min3, origin3 = grid_min3 - voxel_size / 2, voxel_size, M, whether it has normals
+ * (the caller's or estimated ones) */
 int pcr_point_map_grid(const pcr_point_map *map, double *grid_min3, double *origin3, double *voxel_size, int *max_points_per_voxel, int *has_normals);
-/* map <- INSERT(map, cloud, T); T optional; normals exactly when the map has normals. */
+/* map <- INSERT(map, cloud, T); T optional; normals exactly when the map has the caller's normals (NULL for an estimated map). */
 int pcr_point_map_insert(pcr_context *ctx, pcr_point_map *map, const float *xyz, const float *normals, int64_t n, const double *T);
 /* map <- MERGE(map, other); other is unchanged and must not be the map itself. */
 int pcr_point_map_merge(pcr_context *ctx, pcr_point_map *map, const pcr_point_map *other);
 /* map <- REMOVE_FAR(map, center3, max_distance); *removed (optional, host) = rows dropped. */
 int pcr_point_map_remove_far(pcr_context *ctx, pcr_point_map *map, const double *center3, double max_distance, int64_t *removed);
+/* map <- ESTIMATE(map, radius, min_neighbors); *valid_rows (optional, host) = the rows with count >= min_neighbors.  Finished when it returns. */
+int pcr_point_map_estimate_normals(pcr_context *ctx, pcr_point_map *map, double radius, int min_neighbors, int64_t *valid_rows);
+/* count_i of every row of an estimated map: counts = device int32, one entry per row.  Asynchronous on the context's stream. */
+int pcr_point_map_read_normal_counts(pcr_context *ctx, const pcr_point_map *map, int32_t *counts);
+/* the normal rule of a map, each output optional (host): whether it is estimated, and then rho and k_min (0 otherwise) */
+int pcr_point_map_normal_rule(const pcr_point_map *map, int *estimated, double *radius, int *min_neighbors);
 /* the rows (i, map row) at the pose T: rows2 = int32 pairs, capacity n_src rows; *n_rows on the host. */
 int pcr_point_map_correspondences(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T,
                                   double max_correspondence_distance, int neighborhood, int32_t *rows2, int64_t *n_rows);

@@ -181,7 +181,7 @@ EXPORTS = [
     "pcr_registration_sc2_correspondence", "pcr_spatial_compatibility", "pcr_debug_sc2_seeds",
     "pcr_point_map_create", "pcr_point_map_create_on_grid", "pcr_point_map_destroy", "pcr_point_map_size", "pcr_point_map_read", "pcr_point_map_grid",
     "pcr_point_map_insert", "pcr_point_map_merge", "pcr_point_map_remove_far", "pcr_point_map_correspondences", "pcr_point_map_linearize",
-    "pcr_registration_point_map",
+    "pcr_registration_point_map", "pcr_point_map_estimate_normals", "pcr_point_map_read_normal_counts", "pcr_point_map_normal_rule",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -268,6 +268,9 @@ QUERY_PROTOTYPES = {
     "pcr_point_map_size": ([C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "pcr_point_map_read": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_point_map_grid": ([C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "pcr_point_map_estimate_normals": ([C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int64)], C.c_int),
+    "pcr_point_map_read_normal_counts": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_point_map_normal_rule": ([C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)], C.c_int),
     "pcr_point_map_insert": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)], C.c_int),
     "pcr_point_map_merge": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "pcr_point_map_remove_far": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)], C.c_int),

@@ -10,7 +10,7 @@
 #define ISS_G_FACTOR 1e-11          // suppression guard G = ISS_G_FACTOR x salient_radius^2 (include/pcr_hip.h)
 
 // ============================================================================================ eigenvalues of a symmetric 3x3
-// The eigenvalue part of d_fast_eigen3x3 (pcr_cloud.hip; Eberly's non-iterative solver): the matrix scaled by its largest entry, the
+// The eigenvalue part of d_fast_eigen3x3 (pcr_eigen3.h;Eberly's non-iterative solver): the matrix scaled by its largest entry, the
 // trigonometric closed form of the characteristic cubic, and -- as that solver does for its eigenvectors -- a deflation by the eigenvector
 // of the well-separated root.  The closed form alone gives the two roots next to each other (l2 and l3 of a line-like neighbourhood, where
 // acos works at 1 - 1e-10) only to 1e-11 of the largest; the eigenvalues of the 2x2 block in the complement of the separated eigenvector

@@ -13,6 +13,10 @@
 //   k_icp_iter_pmap   the whole iteration, one launch: workgroup b owns the source points [512 b, 512 b + 512) in caller order; octet o searches
 //                     for its own eight points in eight rounds (every cross-lane exchange stands in wave-uniform control flow), then EVERY lane
 //                     forms the rows of its own point and icp_finish reduces them (a fixed tree per workgroup, workgroups ascending)
+//   k_pmap_normals    ESTIMATE, in pm_search's shape: an octet per map row probes the 27 cells around the row's own cell and scans their members
+//                     together for the count and the nine float64 sums of the differences; pm_build runs it on the NEW block, behind its cell
+//                     hash and before the swap, so a map that estimates its normals is never seen with stale ones.  The iteration kernel learns
+//                     validity through its compile-time flag EST, instantiated for point to plane on an estimated map alone
 // Nothing in this unit is contracted: every product and sum of the rule is rounded once.
 #pragma clang fp contract(off)
 #include <cmath>
@@ -20,6 +24,7 @@
 #include <limits>
 #include "pcr_icp_loop.h"
 #include "pcr_pmap.h"
+#include "pcr_eigen3.h"
 
 #define PM_BS 256
 #define PM_MAX_POINTS 64
@@ -85,6 +90,8 @@ struct IcpPmapArgs {
     PmapView map;
     int ns, nbh, plane;        // plane: 1 point to plane, 0 point to point
     double max_d2;
+    const int32_t *ncount;     // k_icp_iter_pmap<true> alone (point to plane on an estimated map): a match whose row has ncount < kmin is no row
+    int kmin;
 };
 __device__ static inline double pm_weight(int loss, double k, double r) {
     if (loss == PCR_LOSS_L1) return 1.0 / fmax(fabs(r), 1e-300);
@@ -113,6 +120,8 @@ __device__ static inline void pm_rows(const IcpArgs &a, const IcpPmapArgs &v, do
         icp_row6(w, J0, ex, acc); icp_row6(w, J1, ey, acc); icp_row6(w, J2, ez, acc);
     }
 }
+// EST: the map's normals are its own (ESTIMATE) and the estimator reads them; instantiated for that case alone
+template <bool EST>
 __global__ void __launch_bounds__(LIN_BS) k_icp_iter_pmap(IcpArgs a, IcpPmapArgs v) {
     IcpState *st = a.state;
     if (st->done) return;
@@ -134,6 +143,7 @@ __global__ void __launch_bounds__(LIN_BS) k_icp_iter_pmap(IcpArgs a, IcpPmapArgs
     if (live) vg_transform(T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], qx, qy, qz);
     double d2; int row;
     pm_match_own(v.map, v.nbh, live, qx, qy, qz, v.max_d2, d2, row);
+    if (EST && row >= 0 && v.ncount[row] < v.kmin) row = -1;
     if (live && row >= 0) pm_rows(a, v, qx, qy, qz, row, d2, acc);
     icp_finish<ICP_MODE_P2PL, LIN_BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);      // (to icp_finish this is point to plane: the 6x6 LDLT update, fitness = rows / ns)
 }
@@ -150,6 +160,12 @@ __global__ void __launch_bounds__(PM_BS) k_pmap_match(const float *__restrict__ 
     pm_match_own(m, nbh, live, qx, qy, qz, max_d2, d2, row);
     if (live) { match[i] = row; flags[i] = row >= 0 ? 1 : 0; }
 }
+// point to plane on an estimated map: a match whose row is not valid is no row
+__global__ void __launch_bounds__(PM_BS) k_pmap_drop_invalid(const int32_t *__restrict__ ncount, int kmin, int ns, int32_t *__restrict__ match, uint8_t *__restrict__ flags) {
+    const int i = blockIdx.x * PM_BS + threadIdx.x;
+    if (i >= ns || !flags[i]) return;
+    if (ncount[match[i]] < kmin) { match[i] = -1; flags[i] = 0; }
+}
 __global__ void __launch_bounds__(PM_BS) k_pmap_emit(const int32_t *__restrict__ match, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int ns,
                                                      int32_t *__restrict__ rows2) {
     const int i = blockIdx.x * PM_BS + threadIdx.x;
@@ -158,9 +174,10 @@ __global__ void __launch_bounds__(PM_BS) k_pmap_emit(const int32_t *__restrict__
     rows2[2 * (size_t)o] = i; rows2[2 * (size_t)o + 1] = match[i];
 }
 
+static inline bool pm_reads_validity(const pcr_point_map *map, const pcr_estimation *est) { return map->estimated && est->kind == PCR_EST_POINT_TO_PLANE; }
 // The loop of voxelized GICP (vgicp_loop, pcr_vgicp.hip) with this unit's kernel: one launch per iteration, chunks replayed as cached graphs.
 // single: linearise once at T0 and stop (pcr_point_map_linearize); *sums then receives the 30 sums.
-static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, const PmapView *map, int neighborhood, double max_d2, const pcr_estimation *est,
+static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, const pcr_point_map *map, int neighborhood, double max_d2, const pcr_estimation *est,
                      const double *T0, double rel_fit, double rel_rmse, int max_it, bool single, pcr_result *out, double *sums) {
     ArenaMark mark(ctx);
     int chunk = 8; bool graph = true;
@@ -175,10 +192,15 @@ static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, i
     a.loss = est->loss; a.loss_k = est->loss_k; a.a = 1.0;
     a.rel_fit = rel_fit; a.rel_rmse = rel_rmse; a.max_it = max_it; a.single = single ? 1 : 0;
     IcpPmapArgs v; memset(&v, 0, sizeof v);
-    v.src_xyz = src_xyz; v.map = *map; v.ns = ns; v.nbh = neighborhood; v.plane = est->kind == PCR_EST_POINT_TO_PLANE ? 1 : 0; v.max_d2 = max_d2;
+    v.src_xyz = src_xyz; v.map = map->view; v.ns = ns; v.nbh = neighborhood; v.plane = est->kind == PCR_EST_POINT_TO_PLANE ? 1 : 0; v.max_d2 = max_d2;
+    const bool validity = pm_reads_validity(map, est);      // (point to point never reads it: on an estimated map it runs the launch of a map without normals)
+    if (validity) { v.ncount = map->ncount; v.kmin = map->est_min; }
     IcpInit in; memcpy(in.T, T0, sizeof in.T);
     PCR_LAUNCH(ctx, k_pmap_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
-    auto enqueue = [&](int) { PCR_LAUNCH(ctx, k_icp_iter_pmap, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v); };
+    auto enqueue = [&](int) {
+        if (validity) PCR_LAUNCH(ctx, k_icp_iter_pmap<true>, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v);
+        else PCR_LAUNCH(ctx, k_icp_iter_pmap<false>, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v);
+    };
     IcpState fin;
     if (single) {
         enqueue(0);
@@ -193,7 +215,7 @@ static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, i
         if (graph && !ragged) {
             std::string key((const char *)&a, sizeof a);
             key.append((const char *)&v, sizeof v);
-            const int extra[3] = {nb, c, 9 /* this loop (the ICP_MODE_* numbers end at 8) */};
+            const int extra[3] = {nb, c, validity ? 10 : 9 /* this loop, by its kernel (the ICP_MODE_* numbers end at 8) */};
             key.append((const char *)extra, sizeof extra);
             IcpGraph *hit = icp_graph_find(ctx, key);
             if (!hit) {
@@ -345,6 +367,91 @@ __global__ void __launch_bounds__(PM_BS) k_pmap_read_cells(const uint64_t *__res
     if (count) count[c] = cell_first[c + 1] - f;
 }
 
+// ================================================================ ESTIMATE: the normals of a map from its own rows
+// An octet per row, in pm_search's shape: lane l probes candidate cell 8 r + l of the row's own cell (from its key) in round r, then the octet scans
+// every occupied cell together, lane l the members first + l, first + l + 8, ...  Each lane keeps its count and the nine float64 sums of the
+// differences e = p_j - p_i of its neighbours (d^2 < rho^2), in the order it meets them: candidate cells ascending, members ascending.  A lane's
+// share is therefore fixed by the rows alone (the members of a cell whose rank inside the cell is l mod 8), and the xor tree of width 8 adds the
+// eight shares in one fixed shape, ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  Lane 0 of the octet finishes the row.
+struct PmNormalArgs {
+    PmapView map;              // of the block the rows live in: xyz, the cell hash (nrm is what is written, through `nrm` below)
+    const uint64_t *keys;      // the Morton key of every row's cell
+    int rows, kmin;
+    double r2;                 // rho^2, one float64 product
+    float *nrm; int32_t *ncount; int *nvalid;
+};
+__global__ void __launch_bounds__(PM_BS) k_pmap_normals(PmNormalArgs a) {
+    const int ol = threadIdx.x & 7;
+    const int i = blockIdx.x * (PM_BS / 8) + (threadIdx.x >> 3);
+    const bool live = i < a.rows;
+    const unsigned mask = *a.map.dmask;
+    GridView g;
+    g.tab = a.map.tab; g.dmask = a.map.dmask; g.L = 0;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    int cx = 0, cy = 0, cz = 0;
+    if (live) {
+        const float *q = a.map.xyz + (size_t)i * 3;
+        qx = q[0]; qy = q[1]; qz = q[2];
+        const uint64_t key = a.keys[i];
+        cx = pm_compact21(key); cy = pm_compact21(key >> 1); cz = pm_compact21(key >> 2);
+    }
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int n = 0;
+    for (int r = 0; r < 4; r++) {                                        // (wave-uniform)
+        const int k = r * 8 + ol;
+        int first = 0, cnt = 0;
+        if (live && k < 27) {
+            int dx, dy, dz;
+            vg_offset(27, k, dx, dy, dz);
+            const int2 e = pcr_grid_lookup(g, mask, cx + dx, cy + dy, cz + dz);      // (a cell outside [0, 2^21) does not exist: not probed)
+            if (e.y > 0 && e.x >= 0 && e.x < a.rows) { first = e.x; cnt = min(e.y, a.rows - e.x); }
+        }
+        if (__ballot(cnt > 0) == 0ull) continue;                         // (wave-uniform)
+        for (int l = 0; l < 8; l++) {                                    // (wave-uniform: the exchanges below are reached by all 64 lanes together)
+            const int f = __shfl(first, l, 8), c = __shfl(cnt, l, 8);
+            for (int j = ol; j < c; j += 8) {
+                const float *p = a.map.xyz + (size_t)(f + j) * 3;
+                const double px = p[0], py = p[1], pz = p[2];
+                const double dx = qx - px, dy = qy - py, dz = qz - pz;
+                const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+                double d2 = xx + yy;
+                d2 = d2 + zz;
+                if (d2 < a.r2) {
+                    const double ex = px - qx, ey = py - qy, ez = pz - qz;
+                    n++;
+                    s[0] += ex; s[1] += ey; s[2] += ez;
+                    s[3] += ex * ex; s[4] += ex * ey; s[5] += ex * ez; s[6] += ey * ey; s[7] += ey * ez; s[8] += ez * ez;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 1; w < 8; w <<= 1) {
+        n += __shfl_xor(n, w, 8);
+#pragma unroll
+        for (int t = 0; t < 9; t++) s[t] += __shfl_xor(s[t], w, 8);
+    }
+    bool valid = false;
+    if (live && ol == 0) {
+        double C6[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};                   // fewer than 3 neighbours: the identity
+        if (n >= 3) {
+            const double c = (double)n;
+            const double mx = s[0] / c, my = s[1] / c, mz = s[2] / c;
+            C6[0] = s[3] / c - mx * mx; C6[1] = s[4] / c - mx * my; C6[2] = s[5] / c - mx * mz;
+            C6[3] = s[6] / c - my * my; C6[4] = s[7] / c - my * mz; C6[5] = s[8] / c - mz * mz;
+        }
+        double nv[3];
+        d_fast_eigen3x3(C6, nv);
+        const double nn = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+        if (nn == 0.0 || !(nn == nn)) { nv[0] = 0.0; nv[1] = 0.0; nv[2] = 1.0; }
+        a.nrm[(size_t)i * 3] = (float)nv[0]; a.nrm[(size_t)i * 3 + 1] = (float)nv[1]; a.nrm[(size_t)i * 3 + 2] = (float)nv[2];
+        a.ncount[i] = n;
+        valid = n >= a.kmin;
+    }
+    const unsigned long long vb = __ballot(valid);
+    if ((threadIdx.x & 63) == 0 && vb != 0ull) atomicAdd(a.nvalid, __popcll(vb));
+}
+
 // ================================================================ the map: host
 struct PmGrid { double grid_min[3], voxel; };
 static void pm_origin(const PmGrid &g, double *org) { for (int d = 0; d < 3; d++) org[d] = g.grid_min[d] - g.voxel * 0.5; }      // (pcr_dev_voxel's expression)
@@ -413,8 +520,12 @@ static int pm_cloud_seq(pcr_context *ctx, const char *call, const float *xyz, co
 // The one pass from a sequence to a map block (see the head of this file).  near: optional flag per entry that must hold too (remove_far).  On
 // PCR_OK the block is adopted by m (a new map has block == nullptr; an old block is freed, which waits for the device) and m holds the counts; on
 // an error m is untouched.  No row kept: PCR_EINVAL (would leave the map empty).
-template <bool NRM>
-static int pm_build_t(pcr_context *ctx, const char *call, const PmSeq &seq, const uint8_t *near, const PmSources &s, int max_points, pcr_point_map *m) {
+// The normals of the new block (PmKind): none; the sources' own, row by row; or ESTIMATE(radius, min_neighbors) on the new block's rows, enqueued
+// behind its cell hash and finished before the block is adopted -- the sources' normals are not read then.
+struct PmKind { bool normals, estimated; double radius; int min_neighbors; };
+static PmKind pm_kind_of(const pcr_point_map *m) { return PmKind{m->normals, m->estimated, m->est_radius, m->est_min}; }
+template <bool NRM, bool EST>
+static int pm_build_t(pcr_context *ctx, const char *call, const PmSeq &seq, const uint8_t *near, const PmSources &s, int max_points, const PmKind &kind, pcr_point_map *m) {
     const int n = seq.n;
     uint8_t *head = arena<uint8_t>(ctx, (size_t)n), *keep = arena<uint8_t>(ctx, (size_t)n), *chead = arena<uint8_t>(ctx, (size_t)n);
     int *hpos = arena<int>(ctx, (size_t)n), *seg_start = arena<int>(ctx, (size_t)n), *kpos = arena<int>(ctx, (size_t)n), *cpos = arena<int>(ctx, (size_t)n), *word = arena<int>(ctx, 3);
@@ -438,19 +549,41 @@ static int pm_build_t(pcr_context *ctx, const char *call, const PmSeq &seq, cons
     int64_t cells = 0;
     PCR_TRY(pcr_read_count(ctx, word + 2, &cells));
     if (cells < 1 || cells > rows) { ctx->err = std::string(call) + ": the scan of the cells is out of range"; return PCR_EHIP; }
-    typedef PmapRow<NRM> Row;
+    typedef PmapRow<NRM, EST> Row;
     MapBlock<Row> nb;
     PCR_TRY(map_build_block<Row>(ctx, call, rows, &nb, [&](const typename Row::Out &o) -> int {
         PCR_LAUNCH(ctx, k_pmap_gather, gr, bs, 0, ctx->stream, s, (const uint64_t *)ckeys, (const uint32_t *)csrc, (const uint8_t *)chead, (const int *)cpos, (int)rows, (int)cells,
-                   o.xyz, o.nrm, o.keys, o.cell_first);
+                   o.xyz, EST ? (float *)nullptr : o.nrm, o.keys, o.cell_first);
+        if (EST) PCR_HIP_CHECK(ctx, hipMemsetAsync(o.nvalid, 0, sizeof(int), ctx->stream));
         return PCR_OK;
-    }, [](const MapBlock<Row> &) -> int { return PCR_OK; }));
+    }, [&](const MapBlock<Row> &b) -> int {
+        if (!EST) return PCR_OK;
+        PmNormalArgs a; memset(&a, 0, sizeof a);
+        a.map = m->view;                                      // the grid (origin, voxel size); the arrays are the new block's
+        a.map.tab = b.gv.tab; a.map.dmask = b.gv.dmask; a.map.xyz = b.out.xyz; a.map.nrm = nullptr;
+        a.keys = b.out.keys; a.rows = (int)rows; a.kmin = kind.min_neighbors; a.r2 = kind.radius * kind.radius;
+        a.nrm = b.out.nrm; a.ncount = b.out.ncount; a.nvalid = b.out.nvalid;
+        PCR_LAUNCH(ctx, k_pmap_normals, dim3(pm_blocks((size_t)rows * 8)), dim3(PM_BS), 0, ctx->stream, a);
+        return PCR_OK;
+    }));
+    int valid = 0;
+    if (EST) {                                                // (the stream is idle: map_build_block has waited)
+        const hipError_t e = hipMemcpy(&valid, nb.out.nvalid, sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess || valid < 0 || valid > rows) {
+            (void)hipFree(nb.block);
+            ctx->err = std::string(call) + ": the count of the valid rows could not be read";
+            return PCR_EHIP;
+        }
+    }
     map_adopt<Row>(m, nb, rows);
     m->n_cells = cells;
+    m->normals = NRM; m->estimated = EST;
+    m->est_radius = EST ? kind.radius : 0.0; m->est_min = EST ? kind.min_neighbors : 0; m->valid_rows = valid;
     return PCR_OK;
 }
-static int pm_build(pcr_context *ctx, const char *call, const PmSeq &seq, const uint8_t *near, const PmSources &s, int max_points, bool normals, pcr_point_map *m) {
-    return normals ? pm_build_t<true>(ctx, call, seq, near, s, max_points, m) : pm_build_t<false>(ctx, call, seq, near, s, max_points, m);
+static int pm_build(pcr_context *ctx, const char *call, const PmSeq &seq, const uint8_t *near, const PmSources &s, int max_points, const PmKind &kind, pcr_point_map *m) {
+    if (kind.estimated) return pm_build_t<true, true>(ctx, call, seq, near, s, max_points, kind, m);
+    return kind.normals ? pm_build_t<true, false>(ctx, call, seq, near, s, max_points, kind, m) : pm_build_t<false, false>(ctx, call, seq, near, s, max_points, kind, m);
 }
 
 static int pm_create(pcr_context *ctx, const char *call, const float *xyz, const float *normals, int64_t n, double voxel_size, int max_points, const double *grid_min3,
@@ -473,7 +606,7 @@ static int pm_create(pcr_context *ctx, const char *call, const float *xyz, const
     pm_origin(g, m->view.org);
     m->view.voxel = voxel_size;
     const PmSources s{mx, mn, (int)n, nullptr, nullptr, 0};
-    const int rc = pm_build(ctx, call, seq, nullptr, s, max_points, m->normals, m);
+    const int rc = pm_build(ctx, call, seq, nullptr, s, max_points, PmKind{m->normals, false, 0.0, 0}, m);
     if (rc != PCR_OK) { delete m; return rc; }
     *out = m;
     return PCR_OK;
@@ -530,6 +663,43 @@ extern "C" int pcr_point_map_read(pcr_context *ctx, const pcr_point_map *map, in
     });
 }
 
+// ESTIMATE: the map's own sequence through pm_build once more -- every row is kept (its rank is below M), so the new block has the same rows bit
+// for bit, with room for the normals and the counts, which the build computes before it swaps the block in
+extern "C" int pcr_point_map_estimate_normals(pcr_context *ctx, pcr_point_map *map, double radius, int min_neighbors, int64_t *valid_rows) {
+    return pcr_api_call(ctx, [&]() -> int {
+    const char *call = "point_map_estimate_normals";
+    if (valid_rows) *valid_rows = 0;
+    PCR_TRY(pm_check_map(ctx, map, call));
+    if (map->normals && !map->estimated) { ctx->err = "point_map_estimate_normals: the map has normals of the caller's (normals are estimated on a map without)"; return PCR_EINVAL; }
+    if (!std::isfinite(radius) || !(radius > 0.0) || !(radius <= map->view.voxel)) { ctx->err = "point_map_estimate_normals: radius must be finite, greater than 0 and at most voxel_size"; return PCR_EINVAL; }
+    if (min_neighbors < 3) { ctx->err = "point_map_estimate_normals: min_neighbors must be at least 3"; return PCR_EINVAL; }
+    PCR_TRY(pcr_arena_reserve(ctx, pm_scratch(map->cells)));
+    const int n = (int)map->cells;
+    const PmSources s{map->view.xyz, nullptr, n, nullptr, nullptr, 0};
+    PCR_TRY(pm_build(ctx, call, PmSeq{map->keys, nullptr, n}, nullptr, s, map->max_points, PmKind{true, true, radius, min_neighbors}, map));
+    if (valid_rows) *valid_rows = map->valid_rows;
+    return PCR_OK;
+    });
+}
+
+extern "C" int pcr_point_map_read_normal_counts(pcr_context *ctx, const pcr_point_map *map, int32_t *counts) {
+    return pcr_api_call(ctx, [&]() -> int {
+    PCR_TRY(pm_check_map(ctx, map, "point_map_read_normal_counts"));
+    if (!map->estimated) { ctx->err = "point_map_read_normal_counts: the map does not estimate its normals"; return PCR_EINVAL; }
+    if (!counts) { ctx->err = "point_map_read_normal_counts: counts is null"; return PCR_EINVAL; }
+    PCR_HIP_CHECK(ctx, hipMemcpyAsync(counts, map->ncount, sizeof(int32_t) * (size_t)map->cells, hipMemcpyDeviceToDevice, ctx->stream));
+    return PCR_OK;
+    });
+}
+
+extern "C" int pcr_point_map_normal_rule(const pcr_point_map *map, int *estimated, double *radius, int *min_neighbors) {
+    if (!map) return PCR_EINVAL;
+    if (estimated) *estimated = map->estimated ? 1 : 0;
+    if (radius) *radius = map->est_radius;
+    if (min_neighbors) *min_neighbors = map->est_min;
+    return PCR_OK;
+}
+
 // map <- the rows of the merge path of the map's rows and the sequence b (sources: the arrays bx / bn with b_rows rows)
 static int pm_merge_into(pcr_context *ctx, const char *call, pcr_point_map *map, const PmSeq &b, const float *bx, const float *bn, int b_rows) {
     const size_t total = (size_t)map->cells + (size_t)b.n;
@@ -539,7 +709,7 @@ static int pm_merge_into(pcr_context *ctx, const char *call, pcr_point_map *map,
     if (!mk || !ms) return PCR_ENOMEM;
     PCR_LAUNCH(ctx, k_pmap_merge_path, dim3(pm_blocks(total)), dim3(PM_BS), 0, ctx->stream, (const uint64_t *)map->keys, (int)map->cells, b.keys, b.src, b.n, mk, ms);
     const PmSources s{map->view.xyz, map->view.nrm, (int)map->cells, bx, bn, b_rows};
-    return pm_build(ctx, call, PmSeq{mk, ms, (int)total}, nullptr, s, map->max_points, map->normals, map);
+    return pm_build(ctx, call, PmSeq{mk, ms, (int)total}, nullptr, s, map->max_points, pm_kind_of(map), map);
 }
 
 extern "C" int pcr_point_map_insert(pcr_context *ctx, pcr_point_map *map, const float *xyz, const float *normals, int64_t n, const double *T) {
@@ -547,7 +717,8 @@ extern "C" int pcr_point_map_insert(pcr_context *ctx, pcr_point_map *map, const 
     const char *call = "point_map_insert";
     PCR_TRY(pm_check_map(ctx, map, call));
     PCR_TRY(pm_check_cloud(ctx, call, xyz, n, T));
-    if ((normals != nullptr) != map->normals) { ctx->err = "point_map_insert: normals must be given exactly when the map has normals"; return PCR_EINVAL; }
+    if (map->estimated && normals) { ctx->err = "point_map_insert: normals must be null for a map that estimates its normals"; return PCR_EINVAL; }
+    if (!map->estimated && (normals != nullptr) != map->normals) { ctx->err = "point_map_insert: normals must be given exactly when the map has normals"; return PCR_EINVAL; }
     PCR_TRY(pcr_arena_reserve(ctx, pm_scratch(2 * n + map->cells)));
     PmGrid g; memcpy(g.grid_min, map->grid_min, sizeof g.grid_min); g.voxel = map->view.voxel;
     PmSeq seq; const float *mx, *mn;
@@ -567,7 +738,7 @@ extern "C" int pcr_point_map_merge(pcr_context *ctx, pcr_point_map *map, const p
         ctx->err = "point_map_merge: other is not on the map's grid (voxel size and origin must be equal bit for bit)"; return PCR_EINVAL;
     }
     if (map->max_points != other->max_points) { ctx->err = "point_map_merge: other has another max_points_per_voxel"; return PCR_EINVAL; }
-    if (map->normals != other->normals) { ctx->err = "point_map_merge: one map has normals and the other has none"; return PCR_EINVAL; }
+    if ((map->normals && !map->estimated) != (other->normals && !other->estimated)) { ctx->err = "point_map_merge: one map has normals and the other has none"; return PCR_EINVAL; }
     PCR_TRY(pcr_arena_reserve(ctx, pm_scratch(map->cells + other->cells)));
     return pm_merge_into(ctx, call, map, PmSeq{other->keys, nullptr, (int)other->cells}, other->view.xyz, other->view.nrm, (int)other->cells);
     });
@@ -592,7 +763,7 @@ extern "C" int pcr_point_map_remove_far(pcr_context *ctx, pcr_point_map *map, co
     PCR_TRY(pcr_read_count(ctx, total, &kept));
     if (kept == n) return PCR_OK;                             // every row stays, with its bits and its place
     const PmSources s{map->view.xyz, map->view.nrm, n, nullptr, nullptr, 0};
-    PCR_TRY(pm_build(ctx, call, PmSeq{map->keys, nullptr, n}, near, s, map->max_points, map->normals, map));
+    PCR_TRY(pm_build(ctx, call, PmSeq{map->keys, nullptr, n}, near, s, map->max_points, pm_kind_of(map), map));
     if (removed) *removed = (int64_t)n - map->cells;
     return PCR_OK;
     });
@@ -623,7 +794,9 @@ static int pm_check_src_finite(pcr_context *ctx, const char *call, const float *
 static size_t pm_search_scratch(int64_t n_src) { return (size_t)(n_src > 0 ? n_src : 1) * 24 + (4u << 20); }
 
 // the rows at the pose T (16 doubles, host) into rows2; scratch from the arena the caller has reserved
-static int pm_rows_at(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, int nbh, double max_d2, int32_t *rows2, int64_t *n_rows) {
+// valid_only: a match whose row is not valid (ESTIMATE) is no row
+static int pm_rows_at(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, int nbh, double max_d2, bool valid_only, int32_t *rows2,
+                      int64_t *n_rows) {
     *n_rows = 0;
     if (n_src == 0) return PCR_OK;
     ArenaMark mark(ctx);
@@ -633,6 +806,7 @@ static int pm_rows_at(pcr_context *ctx, const pcr_point_map *map, const float *s
     if (!match || !flags || !pos || !count) return PCR_ENOMEM;
     PmPose pose; memcpy(pose.T, T, sizeof pose.T);
     PCR_LAUNCH(ctx, k_pmap_match, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, src_xyz, (int)n_src, pose, map->view, nbh, max_d2, match, flags);
+    if (valid_only) PCR_LAUNCH(ctx, k_pmap_drop_invalid, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, (const int32_t *)map->ncount, map->est_min, (int)n_src, match, flags);
     PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)n_src, pos, count));
     PCR_LAUNCH(ctx, k_pmap_emit, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, (const int32_t *)match, (const uint8_t *)flags, (const int *)pos, (int)n_src, rows2);
     return pcr_read_count(ctx, count, n_rows);
@@ -646,7 +820,7 @@ extern "C" int pcr_point_map_correspondences(pcr_context *ctx, const pcr_point_m
     if (!n_rows || (n_src > 0 && !rows2)) { ctx->err = "point_map_correspondences: rows2 / n_rows is null"; return PCR_EINVAL; }
     PCR_TRY(pcr_arena_reserve(ctx, pm_search_scratch(n_src)));
     PCR_TRY(pm_check_src_finite(ctx, call, src_xyz, n_src));
-    return pm_rows_at(ctx, map, src_xyz, n_src, T, neighborhood, max_correspondence_distance * max_correspondence_distance, rows2, n_rows);
+    return pm_rows_at(ctx, map, src_xyz, n_src, T, neighborhood, max_correspondence_distance * max_correspondence_distance, false, rows2, n_rows);
     });
 }
 
@@ -659,7 +833,7 @@ extern "C" int pcr_point_map_linearize(pcr_context *ctx, const pcr_point_map *ma
     PCR_TRY(pcr_arena_reserve(ctx, pm_search_scratch(n_src)));
     PCR_TRY(pm_check_src_finite(ctx, call, src_xyz, n_src));
     double h[NV];
-    PCR_TRY(pmap_loop(ctx, call, src_xyz, n_src, &map->view, neighborhood, max_correspondence_distance * max_correspondence_distance, estimation, T, 0.0, 0.0, 0, true, nullptr, h));
+    PCR_TRY(pmap_loop(ctx, call, src_xyz, n_src, map, neighborhood, max_correspondence_distance * max_correspondence_distance, estimation, T, 0.0, 0.0, 0, true, nullptr, h));
     if (JTJ) {
         int t = 0;
         for (int p = 0; p < 6; p++) for (int q = p; q < 6; q++) { JTJ[p * 6 + q] = h[t]; JTJ[q * 6 + p] = h[t]; t++; }
@@ -683,11 +857,11 @@ extern "C" int pcr_registration_point_map(pcr_context *ctx, const float *src_xyz
     PCR_TRY(pcr_arena_reserve(ctx, pm_search_scratch(n_src)));
     PCR_TRY(pm_check_src_finite(ctx, call, src_xyz, n_src));
     const double max_d2 = max_correspondence_distance * max_correspondence_distance;
-    PCR_TRY(pmap_loop(ctx, call, src_xyz, n_src, &map->view, params->neighborhood, max_d2, &params->estimation, init_T, params->relative_fitness, params->relative_rmse,
+    PCR_TRY(pmap_loop(ctx, call, src_xyz, n_src, map, params->neighborhood, max_d2, &params->estimation, init_T, params->relative_fitness, params->relative_rmse,
                       params->max_iteration, false, result, nullptr));
     if (correspondences) {      // the rows of the last launch: those at the returned pose
         int64_t rows = 0;
-        PCR_TRY(pm_rows_at(ctx, map, src_xyz, n_src, result->transformation, params->neighborhood, max_d2, correspondences, &rows));
+        PCR_TRY(pm_rows_at(ctx, map, src_xyz, n_src, result->transformation, params->neighborhood, max_d2, pm_reads_validity(map, &params->estimation), correspondences, &rows));
         if (rows != result->n_correspondences) { ctx->err = "registration_point_map: the correspondence set does not match the last iteration's rows"; return PCR_EHIP; }
     }
     return PCR_OK;

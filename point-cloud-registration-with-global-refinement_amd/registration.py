@@ -1019,7 +1019,11 @@ class VoxelPointMap(_GrowingVoxelMap):
     ``VoxelPointMap.on_grid(target, voxel_size, grid_min=centered_grid_min(point, voxel_size))``.  ``insert`` adds a scan at a pose, ``merge``
     another map of the same grid and rule (NOT commutative: in a full cell the map's own points stay), ``remove_far`` drops the ROWS far from a
     point.  Each of them replaces the rows as a whole: row indices of an earlier ``correspondence_set`` are stale afterwards, and no other call
-    may use the map while one runs."""
+    may use the map while one runs.
+
+    A map made from a target without normals can compute them from its own rows: ``estimate_normals(radius, min_neighbors)`` (ESTIMATE of
+    include/pcr_hip.h).  From then on the map keeps them current through ``insert``, ``merge`` and ``remove_far``, and point-to-plane ICP runs on
+    it with scans that carry no normals; a row with fewer than ``min_neighbors`` neighbours is not valid and gives the estimator no row."""
 
     _C, _NAME = "pcr_point_map", "VoxelPointMap"
     _COLUMNS = {"cells": (3, "int32"), "starts": (None, "int32"), "counts": (None, "int32"), "points": (3, "float32"), "normals": (3, "float32")}
@@ -1061,6 +1065,72 @@ class VoxelPointMap(_GrowingVoxelMap):
         rows, cells = C.c_int64(0), C.c_int64(0)
         self._lib.pcr_point_map_size(self._handle, C.byref(rows), C.byref(cells))
         self._cells, self._n_cells = int(rows.value), int(cells.value)      # (the base's _cells is what len() returns: the rows)
+        nrm = C.c_int(0)
+        self._lib.pcr_point_map_grid(self._handle, None, None, None, None, C.byref(nrm))
+        self.has_normals = bool(nrm.value)                                  # (a merge with an estimated map, or estimate_normals, may change it)
+
+    def _normal_rule(self):
+        est, radius, kmin = C.c_int(0), C.c_double(0), C.c_int(0)
+        self._lib.pcr_point_map_normal_rule(self._open(), C.byref(est), C.byref(radius), C.byref(kmin))
+        return bool(est.value), float(radius.value), int(kmin.value)
+
+    @property
+    def normals_estimated(self) -> bool:
+        """whether the normals are the map's own (``estimate_normals``), kept current by the map itself"""
+        return self._normal_rule()[0]
+
+    @property
+    def normal_radius(self):
+        """the radius of ``estimate_normals``, or ``None`` on a map that does not estimate its normals"""
+        est, radius, _ = self._normal_rule()
+        return radius if est else None
+
+    @property
+    def normal_min_neighbors(self):
+        """``min_neighbors`` of ``estimate_normals``, or ``None`` on a map that does not estimate its normals"""
+        est, _, kmin = self._normal_rule()
+        return kmin if est else None
+
+    @property
+    def normal_counts(self) -> np.ndarray:
+        """(rows,) int32: the map rows within ``normal_radius`` of every row, itself included (an estimated map only)"""
+        h = self._open()
+        if not self.normals_estimated:
+            raise RuntimeError("VoxelPointMap.normal_counts: the map does not estimate its normals (estimate_normals)")
+        ctx = _lib.Context.current()
+        t = _torch().empty((self._cells,), dtype=_torch().int32, device="cuda")
+        ctx.check(ctx.lib.pcr_point_map_read_normal_counts(ctx.handle, h, _ptr(t)), "VoxelPointMap.normal_counts")
+        return t.cpu().numpy()
+
+    @property
+    def normal_valid(self) -> np.ndarray:
+        """(rows,) bool: ``normal_counts >= normal_min_neighbors``, the rows point-to-plane ICP takes"""
+        return self.normal_counts >= self.normal_min_neighbors
+
+    def estimate_normals(self, radius=None, min_neighbors: int = 5) -> int:
+        """Compute the normal of every row from the map rows within ``radius`` of it (``pcr_point_map_estimate_normals``; ``None``: the voxel
+        size, the largest radius for which the 27 cells around a row hold every such row) and return the number of valid rows, those with at
+        least ``min_neighbors`` neighbours (the row itself counts).  The map keeps the rule: ``insert``, ``merge`` and ``remove_far`` estimate
+        the whole new map again.  Refused on a map with normals of the caller's; on an estimated map it estimates again with the new arguments.
+        The normals carry no orientation (the point-to-plane row does not read the sign)."""
+        fn = "VoxelPointMap.estimate_normals"
+        h = self._open()
+        r = self._voxel_size if radius is None else radius
+        try:
+            r = float(r)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: radius must be a number in (0, voxel_size], got {radius!r}") from None
+        if not np.isfinite(r) or not (0.0 < r <= self._voxel_size):
+            raise ValueError(f"{fn}: radius must be a finite number in (0, voxel_size = {self._voxel_size!r}], got {radius!r}")
+        if not isinstance(min_neighbors, (int, np.integer)) or isinstance(min_neighbors, bool) or min_neighbors < 3:
+            raise ValueError(f"{fn}: min_neighbors must be an integer of at least 3, got {min_neighbors!r}")
+        if self.has_normals and not self.normals_estimated:
+            raise RuntimeError(f"{fn}: the map has normals of the caller's; normals are estimated on a map made without")
+        ctx = _lib.Context.current()
+        valid = C.c_int64(0)
+        ctx.check(ctx.lib.pcr_point_map_estimate_normals(ctx.handle, h, C.c_double(r), C.c_int(int(min_neighbors)), C.byref(valid)), fn)
+        self._refresh()
+        return int(valid.value)
 
     def _read(self, what: str):
         """one column as a device tensor: per row for the points and normals, per cell for the cell table"""
@@ -1087,7 +1157,7 @@ class VoxelPointMap(_GrowingVoxelMap):
 
     @property
     def normals(self) -> np.ndarray:
-        """(rows, 3) float32: the normal of every row, as inserted (rotated by the pose, not normalised)"""
+        """(rows, 3) float32: the normal of every row, as inserted (rotated by the pose, not normalised), or as estimated by the map"""
         return self._read("normals").cpu().numpy()
 
     def _grid(self):
@@ -1116,17 +1186,19 @@ class VoxelPointMap(_GrowingVoxelMap):
 
     def insert(self, cloud: PointCloud, transformation=None):
         """Add ``cloud`` placed at ``transformation`` (``pcr_point_map_insert``; ``None``: as it lies): every point, in the cloud's order, joins
-        its cell's list while that list has fewer than ``max_points_per_voxel`` entries.  A map with normals needs a cloud with normals.  A point
+        its cell's list while that list has fewer than ``max_points_per_voxel`` entries.  A map with normals of the caller's needs a cloud with
+        normals; a map that estimates its normals takes the points alone (normals the cloud carries are not read) and estimates again.  A point
         outside the grid raises the library's error and leaves the map as it was."""
         fn = "VoxelPointMap.insert"
         h = self._open()
         if not isinstance(cloud, PointCloud) or len(cloud) == 0:
             raise RuntimeError(f"{fn}: the cloud must be a PointCloud with at least one point")
-        if self.has_normals and not cloud.has_normals():
+        own = self.has_normals and not self.normals_estimated
+        if own and not cloud.has_normals():
             raise RuntimeError(f"{fn}: the map has normals and the cloud has none")
         T, Tp = self._pose(fn, transformation)
         ctx = _lib.Context.current()
-        ctx.check(ctx.lib.pcr_point_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), _ptr(cloud.device_normals() if self.has_normals else None),
+        ctx.check(ctx.lib.pcr_point_map_insert(ctx.handle, h, _ptr(cloud.device_xyz()), _ptr(cloud.device_normals() if own else None),
                                                C.c_int64(len(cloud)), Tp), fn)
         self._refresh()
 
@@ -1149,7 +1221,8 @@ class VoxelPointMap(_GrowingVoxelMap):
 
     def linearize(self, source: PointCloud, T=np.eye(4), max_correspondence_distance=None, estimation_method=None, neighborhood: int = 27) -> PointMapLinearization:
         """The sums of one update at the pose ``T`` (``pcr_point_map_linearize``, one launch of the iteration kernel, the same bits on every
-        run): the 6x6 matrix, the right-hand side, the number of rows, their summed squared distances and squared residuals."""
+        run): the 6x6 matrix, the right-hand side, the number of rows, their summed squared distances and squared residuals.  Point to plane on
+        a map that estimates its normals counts the rows whose map row is valid, and no others."""
         fn = "VoxelPointMap.linearize"
         _check_point_map_rule(fn, neighborhood)
         d = _check_distance(fn, max_correspondence_distance)
@@ -1174,7 +1247,9 @@ def registration_point_map(source: PointCloud, target_or_map, max_correspondence
     neighbours (7 / 27) -- with 27 and ``max_correspondence_distance <= voxel_size`` the exact nearest map point within that distance.  The
     cost follows the scan, not the map.  ``estimation_method``: ``TransformationEstimationPointToPoint()`` (the default; its update here is
     the Gauss-Newton step weighted by its ``kernel``, what KISS-ICP runs, NOT the Umeyama fit of ``registration_icp``; ``with_scaling`` is
-    refused) or ``TransformationEstimationPointToPlane(kernel)``, which needs a map with normals.  ``target_or_map`` is a ``VoxelPointMap``
+    refused) or ``TransformationEstimationPointToPlane(kernel)``, which needs a map with normals -- the caller's, or the map's own
+    (``VoxelPointMap.estimate_normals``), with which a match to a row that is not valid is no row: ``fitness``, ``inlier_rmse`` and
+    ``correspondence_set`` are those of the counted rows.  ``target_or_map`` is a ``VoxelPointMap``
     (``voxel_size`` and ``max_points_per_voxel`` are then the map's own) or a ``PointCloud``, for which a map of ``voxel_size`` is built and
     closed inside the call.  ``correspondence_set`` holds (source index, map row)."""
     fn = "registration_point_map"
@@ -1263,9 +1338,37 @@ def scan_to_map_odometry_icp(scans, voxel_size, max_correspondence_distance=None
       estimator with ``GMLoss(sigma / 3)``, and after the call ``adaptive_threshold.update(start, results[k].transformation)``;
     * ``map.insert(scans[k], poses[k])``, and with a ``max_range``, ``map.remove_far(poses[k][:3, 3], max_range)``.
 
-    Exactly one of ``max_correspondence_distance`` and ``adaptive_threshold`` is given.  Point to plane needs normals on every scan.  The
+    Exactly one of ``max_correspondence_distance`` and ``adaptive_threshold`` is given.  Point to plane needs normals on every scan
+    (``scan_to_map_odometry_icp_map_normals`` runs it on scans without, on normals the map estimates from its own rows).  The
     caller owns the returned map and closes it."""
-    fn = "scan_to_map_odometry_icp"
+    return _scan_to_map_odometry_icp("scan_to_map_odometry_icp", scans, voxel_size, max_correspondence_distance, init, estimation_method, criteria, neighborhood,
+                                     max_points_per_voxel, motion_model, max_range, grid_min, adaptive_threshold, False, None, 5)
+
+
+def scan_to_map_odometry_icp_map_normals(scans, voxel_size, max_correspondence_distance=None, init=np.eye(4), estimation_method=None, criteria=None,
+                                         neighborhood: int = 27, max_points_per_voxel: int = 20, motion_model: str = "constant_velocity", max_range=None, grid_min=None,
+                                         adaptive_threshold=None, map_normal_radius=None, map_normal_min_neighbors: int = 5):
+    """Point-to-plane ``scan_to_map_odometry_icp`` on a map that estimates its normals from its own rows, where the scans of a drive have
+    filled in the surface -> ``(poses, results, map)``.  The scans need no normals, and those they carry are not read.  The recipe is that
+    of ``scan_to_map_odometry_icp`` with ``estimate_normals`` once after ``on_grid``; exactly these public calls, in this order:
+
+    * ``map = VoxelPointMap.on_grid(PointCloud(scans[0].points), voxel_size, max_points_per_voxel, grid_min, init)`` (the points alone, so
+      the map has no normals of the caller's), then once ``map.estimate_normals(map_normal_radius, map_normal_min_neighbors)``
+      (``map_normal_radius=None``: the voxel size); ``poses[0] = init``, ``results[0] = None``;
+    * for every further scan k the ``registration_point_map`` call of ``scan_to_map_odometry_icp``, whose estimator is
+      ``TransformationEstimationPointToPlane`` (``estimation_method=None``: with ``L2Loss``; any other estimator is refused);
+    * ``map.insert(scans[k], poses[k])``, and with a ``max_range``, ``map.remove_far(poses[k][:3, 3], max_range)``, each of which estimates
+      the whole new map again.
+
+    It is a function of its own so that ``scan_to_map_odometry_icp`` keeps its signature.  The caller owns the returned map and closes it."""
+    return _scan_to_map_odometry_icp("scan_to_map_odometry_icp_map_normals", scans, voxel_size, max_correspondence_distance, init,
+                                     TransformationEstimationPointToPlane() if estimation_method is None else estimation_method, criteria, neighborhood, max_points_per_voxel,
+                                     motion_model, max_range, grid_min, adaptive_threshold, True, map_normal_radius, map_normal_min_neighbors)
+
+
+def _scan_to_map_odometry_icp(fn, scans, voxel_size, max_correspondence_distance, init, estimation_method, criteria, neighborhood, max_points_per_voxel, motion_model,
+                              max_range, grid_min, adaptive_threshold, map_normals, map_normal_radius, map_normal_min_neighbors):
+    """the body of ``scan_to_map_odometry_icp`` (``map_normals`` False) and of ``scan_to_map_odometry_icp_map_normals`` (True)"""
     estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
     plane = isinstance(estimation, TransformationEstimationPointToPlane)
 
@@ -1278,12 +1381,24 @@ def scan_to_map_odometry_icp(scans, voxel_size, max_correspondence_distance=None
             _check_distance(fn, max_correspondence_distance)
         elif not isinstance(adaptive_threshold, AdaptiveThreshold):
             raise TypeError(f"{fn}: adaptive_threshold must be an AdaptiveThreshold, got {type(adaptive_threshold).__name__}")
+        if map_normals:
+            if not plane:
+                raise ValueError(f"{fn}: estimation_method must be a TransformationEstimationPointToPlane (point to point reads no normals)")
+            v = _check_voxel_size(fn, voxel_size)
+            try:
+                r = v if map_normal_radius is None else float(map_normal_radius)
+            except (TypeError, ValueError):
+                r = float("nan")
+            if not np.isfinite(r) or not (0.0 < r <= v):
+                raise ValueError(f"{fn}: map_normal_radius must be a finite number in (0, voxel_size], got {map_normal_radius!r}")
+            if not isinstance(map_normal_min_neighbors, (int, np.integer)) or isinstance(map_normal_min_neighbors, bool) or map_normal_min_neighbors < 3:
+                raise ValueError(f"{fn}: map_normal_min_neighbors must be an integer of at least 3, got {map_normal_min_neighbors!r}")
 
     def check_scan(k, s):
         if not isinstance(s, PointCloud) or len(s) == 0:
             raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
-        if plane and not s.has_normals():
-            raise RuntimeError(f"{fn}: scan {k} has no normals (TransformationEstimationPointToPlane needs a map with normals)")
+        if plane and not map_normals and not s.has_normals():
+            raise RuntimeError(f"{fn}: scan {k} has no normals (TransformationEstimationPointToPlane needs a map with normals; see scan_to_map_odometry_icp_map_normals)")
 
     def register(s, m, start):
         if adaptive_threshold is None:
@@ -1294,8 +1409,20 @@ def scan_to_map_odometry_icp(scans, voxel_size, max_correspondence_distance=None
         adaptive_threshold.update(start, res.transformation)
         return res
 
-    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan,
-                        lambda s, g, P0: VoxelPointMap.on_grid(s, voxel_size, max_points_per_voxel, g, P0), register)
+    def make_map(s, g, P0):
+        if not map_normals:
+            return VoxelPointMap.on_grid(s, voxel_size, max_points_per_voxel, g, P0)
+        bare = PointCloud()
+        bare._xyz = s.device_xyz()
+        m = VoxelPointMap.on_grid(bare, voxel_size, max_points_per_voxel, g, P0)
+        try:
+            m.estimate_normals(map_normal_radius, map_normal_min_neighbors)
+        except BaseException:
+            m.close()
+            raise
+        return m
+
+    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register)
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),

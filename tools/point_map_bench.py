@@ -5,6 +5,9 @@ pair (both clouds at voxel 0.2: 118k points each).  The method of tools/ndt_benc
 call runs exactly N iterations; a call is timed by device events (it ends in a synchronise), after a warm-up call per shape, as the median of
 `reps`, and microseconds per iteration = (t(N = 40) - t(N = 10)) / 30: what a call does once (graph capture, the correspondence set, and for
 registration_icp the search structure over the whole map) cancels -- the per-call figures are printed beside it for that reason.
+In the same run, for a map that estimates its normals from its own rows (radius = the voxel, min_neighbors 5): estimate_normals on the map of the
+target, next to PointCloud.estimate_normals(KDTreeSearchParamRadius(radius)) on map.to_point_cloud(); insert into the estimated map next to insert
+into the same map without normals; and one point-to-plane iteration on the estimated map next to one on the map with the caller's normals.
 usage: point_map_bench.py [reps]"""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +18,7 @@ R = P.registration
 M = R.VoxelPointMap
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 VOXEL, CAP, DIST, LO, HI = 1.0, 20, 1.0, 10, 40
+RHO, K_MIN = VOXEL, 5
 
 
 def timed(fn, setup=lambda: None, done=lambda s, out: None):
@@ -57,6 +61,21 @@ def run(label, src_xyz, tgt_xyz, T0, T_place, voxel):
         per_iteration("registration_point_map(point to point, neighborhood=27)", lambda c: R.registration_point_map(src, m, DIST, None, T0, None, c, 27))
         cloud = m.to_point_cloud()
         per_iteration(f"registration_icp(point to plane) on map.to_point_cloud() ({len(cloud)} points)", lambda c: R.registration_icp(src, cloud, DIST, T0, est, c))
+    bare_src, bare_tgt = P.PointCloud(src._xyz.cpu().numpy()), P.PointCloud(tgt._xyz.cpu().numpy())
+
+    def estimated():
+        m = M.on_grid(bare_tgt, VOXEL, CAP, g)
+        m.estimate_normals(RHO, K_MIN)
+        return m
+
+    with estimated() as m:
+        print(f"  the map estimates its normals (radius {RHO}, min_neighbors {K_MIN}): {int(m.normal_valid.sum())} of {len(m)} rows valid, largest count {int(m.normal_counts.max())}", flush=True)
+        per_iteration("registration_point_map(point to plane, neighborhood=27) on the estimated map", lambda c: R.registration_point_map(bare_src, m, DIST, None, T0, est, c, 27))
+        cloud = m.to_point_cloud()
+        print(f"  PointCloud.estimate_normals(KDTreeSearchParamRadius({RHO})) on map.to_point_cloud(): " + fmt(timed(lambda _: cloud.estimate_normals(P.KDTreeSearchParamRadius(RHO)))), flush=True)
+    print("  estimate_normals:             " + fmt(timed(lambda m: m.estimate_normals(RHO, K_MIN), lambda: M.on_grid(bare_tgt, VOXEL, CAP, g), lambda m, _: m.close())), flush=True)
+    print("  insert, estimated map:        " + fmt(timed(lambda m: m.insert(bare_src, T_place), estimated, lambda m, _: m.close())), flush=True)
+    print("  insert, map without normals:  " + fmt(timed(lambda m: m.insert(bare_src, T_place), lambda: M.on_grid(bare_tgt, VOXEL, CAP, g), lambda m, _: m.close())), flush=True)
     placed = (src._xyz.cpu().numpy().astype(np.float64) @ T_place[:3, :3].T + T_place[:3, 3]).astype(np.float32)
     both = P.PointCloud(np.concatenate([tgt._xyz.cpu().numpy(), placed]))
     both.normals = np.concatenate([tgt._nrm.cpu().numpy(), (src._nrm.cpu().numpy().astype(np.float64) @ T_place[:3, :3].T).astype(np.float32)])
