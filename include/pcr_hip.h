@@ -1226,6 +1226,63 @@ int pcr_point_map_linearize(pcr_context *ctx, const pcr_point_map *map, const fl
 int pcr_registration_point_map(pcr_context *ctx, const float *src_xyz, int64_t n_src, const pcr_point_map *map, double max_correspondence_distance,
                                const double *init_T, const pcr_point_map_params *params, pcr_result *result, int32_t *correspondences);
 
+/* ============================================================================================ continuous time
+ * A spinning LiDAR on a moving platform does not produce a rigid cloud: every point is measured at its own time, from its own pose.  A cloud may
+ * carry one time per point; pcr_deskew moves every point by the fraction of a KNOWN relative motion that belongs to its time (KISS-ICP, Vizzo et
+ * al. 2023), and pcr_point_map_linearize_continuous linearises a registration that ESTIMATES a begin pose and an end pose of the sweep, every point
+ * placed at the pose interpolated at its own time (CT-ICP, Dellenbach et al. 2022), on the voxel point map above.  This statement is the
+ * specification (tests/continuous_time_reference.py restates it in numpy on top of tests/point_map_reference.py).  Open3D has no such call.  The
+ * rule is written from the papers' descriptions; NOBODY HAS COMPARED IT WITH KISS-ICP'S OR CT-ICP'S CODE.
+ *   TIMES.  One float32 per point.  alpha_i = (time_i - t0) / (t1 - t0) in float64 on the widened float32, with t0 < t1 finite doubles (the Python
+ *   layer defaults them to the cloud's minimum and maximum time).  alpha is NOT clamped: a time outside [t0, t1] extrapolates.  t1 <= t0 is
+ *   PCR_EINVAL (names t1), a non-finite time PCR_EINVAL (names times / src_times).
+ *   POSE AT alpha.  T_b = (R_b, t_b) and T_e = (R_e, t_e) are float64 4x4, row-major.  phi = Log(R_b^T R_e) is the rotation vector with its
+ *   angle in [0, pi], computed ONCE per call on the host side of the C call, in float64.  R(alpha) = R_b E(alpha phi), a 3x3 product with every
+ *   entry (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j, and t(alpha) = t_b + alpha (t_e - t_b): T_b == T_e gives t_b exactly.
+ *   E(v) = I + A [v]x + B [v]x^2 with theta^2 = (x x + y y) + z z and theta its root: for theta >= 1e-4 A = sin(theta) / theta and
+ *   B = (1 - cos(theta)) / theta^2; below that A = 1 - theta^2 / 6 and B = 1/2 - theta^2 / 24 (the truncation is below 1e-18); theta == 0
+ *   gives I exactly.  The diagonal is 1 - B (y y + z z) and so on, an off-diagonal entry B x y -+ A z.
+ *   q_i = R(alpha_i) p_i + t(alpha_i) in float64 by the ROWS expression of the voxel maps, ((r0 x + r1 y) + r2 z) + t, uncontracted; q_i is not
+ *   rounded to float32.  u_i = (r0 x + r1 y) + r2 z, the sum before t is added, is the ROTATED POINT.
+ *   DESKEW(cloud, D, alpha_ref).  D = T_b^-1 T_e is the relative motion over the sweep; the model is applied with T_b = I and T_e = D (R(alpha) is
+ *   then E(alpha phi) itself).  With tau = t_D:  p'_i = float32( R(alpha_ref)^T ( (u_i + alpha_i tau) - alpha_ref tau ) ), the transposed product
+ *   entry by entry (r_0d w_0 + r_1d w_1) + r_2d w_2 -- the point in the sensor frame at alpha_ref.  alpha_ref = 1, the end of the sweep, is the
+ *   Python layer's default, so that the pose a registration then finds is the END pose (KISS-ICP's earlier releases used 0.5).  A normal becomes
+ *   float32(R(alpha_ref)^T R(alpha_i) n), not normalised.  Times and colours are carried unchanged by the Python layer; COVARIANCES ARE NOT
+ *   CARRIED (the deskewed cloud has none).  D = I returns the input values: theta == 0 and tau == 0 make every term exact.
+ *   ROW.  The match of q_i is the ROW rule of the voxel point map, unchanged: the neighbourhood 1 / 7 / 27, the order (float64 d^2, row), the
+ *   strict < max_correspondence_distance^2, and, for point to plane on an estimated map, the validity of the matched row.
+ *   UPDATE.  With m and n the matched row and w the kernels of the UPDATE rule above:  point to plane, one row, r = ((q - m) . n) grouped as
+ *   there, J6 = [u x n, n];  point to point, three rows, r = q - m, J6 = [-skew(u) | I], all weighted by w(|q - m|).  u stands here instead of
+ *   the world point s of the rigid estimators, because the STEP below adds to the translations and does not left-multiply the pose.  The
+ *   12-column row is J12 = [(1 - alpha) J6, alpha J6], and the outputs are H = sum w J12^T J12 (12x12, the full symmetric matrix),
+ *   g = sum w J12^T r (12), rows, sum_d2, sum_r2.  A point's terms are the 27 rigid values (upper w J6^T J6, w J6^T r) times (1 - alpha)^2,
+ *   alpha (1 - alpha), alpha^2 resp. (1 - alpha), alpha.
+ *   LIMITATION.  The rotation columns are FIRST ORDER in the rotation between the two poses: they are exact when phi = 0, and otherwise the usual
+ *   linear interpolation of the two increments (the exact slerp Jacobian is not built).  A zero-residual fixed point stays where it is.
+ *   SUMS.  The SUMS rule of the point map: no floating-point atomics; source points in caller order in tiles of 512; a fixed tree inside a tile
+ *   (the pairs (l, l ^ 1), ^ 2, ^ 4, ^ 8 inside 16 consecutive points, then the 32 groups of 16 in ascending order); tiles added in ascending
+ *   order.  The same bits on every run.
+ *   STEP (host, float64; the Python layer).  delta = -(H + P)^-1 (g + p) by a Cholesky solve; a failed factorisation or a non-finite delta is no
+ *   error: the identity update, which ends the loop.  R_b <- E(delta[0:3]) R_b, t_b <- t_b + delta[3:6], R_e <- E(delta[6:9]) R_e,
+ *   t_e <- t_e + delta[9:12].  begin = "fixed" solves the lower-right 6x6 block alone and leaves T_b bit for bit; begin = "free" solves all
+ *   twelve, with an optional prior (w_rot, w_trans) around the T_begin the call was given: rows w_rot I3 and rows w_trans I3 on the begin
+ *   block's diagonal, rows w_rot Log(R_b R_p^T) and rows w_trans (t_b - t_p) on g.
+ *   LOOP.  RegistrationICP's loop on the host: sums at the start poses, then step / sums until |d fitness| < relative_fitness and |d RMSE| <
+ *   relative_rmse, or max_iteration; fitness = rows / n_src, inlier_rmse = sqrt(sum_d2 / rows).  One iteration is one launch and one read-back
+ *   of 160 doubles.
+ * Every refusal is PCR_EINVAL with a message naming the argument: NULL or non-finite times, t1 <= t0 or a non-finite t0 / t1 / alpha_ref, a pose
+ * that is NULL, holds a non-finite value or whose last row is not 0 0 0 1, and every refusal of pcr_point_map_linearize. */
+/* DESKEW: xyz, normals (optional), times, out_xyz and out_normals (exactly when normals is given) are device buffers of n rows; motion16 = D
+ * (host).  out_xyz may be xyz.  Asynchronous on the context's stream. */
+int pcr_deskew(pcr_context *ctx, const float *xyz, const float *normals, const float *times, int64_t n, const double *motion16, double t0, double t1, double alpha_ref,
+               float *out_xyz, float *out_normals);
+/* UPDATE's sums at the poses (T_begin16, T_end16) in ONE launch, all outputs on the host and each optional: H144 (the full symmetric 12x12 matrix,
+ * begin columns first), g12, *rows, *sum_d2, *sum_r2; matches: optional DEVICE int32, one map row or -1 per source point. */
+int pcr_point_map_linearize_continuous(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, const float *src_times, int64_t n_src, const double *T_begin16,
+                                       const double *T_end16, double t0, double t1, double max_correspondence_distance, int neighborhood, const pcr_estimation *estimation,
+                                       double *H144, double *g12, int64_t *rows, double *sum_d2, double *sum_r2, int32_t *matches);
+
 /* ---- measurement hooks (bench.py): no reference counterpart -------------------------- */
 /* While enabled, pcr_multiscale_gicp / pcr_registration_generalized_icp bracket every chunk of GICP-iteration
  * launches with HIP events on the context stream and the kernel stamps itself with s_memrealtime.

@@ -182,6 +182,7 @@ EXPORTS = [
     "pcr_point_map_create", "pcr_point_map_create_on_grid", "pcr_point_map_destroy", "pcr_point_map_size", "pcr_point_map_read", "pcr_point_map_grid",
     "pcr_point_map_insert", "pcr_point_map_merge", "pcr_point_map_remove_far", "pcr_point_map_correspondences", "pcr_point_map_linearize",
     "pcr_registration_point_map", "pcr_point_map_estimate_normals", "pcr_point_map_read_normal_counts", "pcr_point_map_normal_rule",
+    "pcr_deskew", "pcr_point_map_linearize_continuous",
 ]
 
 # prototypes of the cloud queries, the keypoint detector, the clustering, the plane segmentation, the search index, the farthest point sampler, the normal orientation, the calls on a correspondence list, the boundary detector and the multiway problem (include/pcr_hip.h), set on the handle by load(): (argtypes, restype)
@@ -280,6 +281,10 @@ QUERY_PROTOTYPES = {
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
     "pcr_registration_point_map": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(PcrPointMapParams),
                                     C.POINTER(PcrResult), C.c_void_p], C.c_int),
+    "pcr_deskew": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p], C.c_int),
+    "pcr_point_map_linearize_continuous": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
+                                            C.c_double, C.c_int, C.POINTER(PcrEstimation), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p], C.c_int),
     "pcr_debug_scale_clouds": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }

@@ -6,7 +6,7 @@ ARCH=${PCR_ARCH:-gfx950}
 FLAGS="-O3 --offload-arch=$ARCH -fPIC -std=c++17 -Wall -Wno-unused-function -Wno-unused-variable $PCR_EXTRA_FLAGS"
 OUT=${PCR_OUT:-../libpcr_hip.so}
 objs=""
-for f in pcr_sort pcr_cloud pcr_query pcr_search pcr_keypoint pcr_cluster pcr_gicp pcr_colored pcr_vgicp pcr_vmap pcr_ndt pcr_nmap pcr_pmap pcr_featnn pcr_fgr pcr_ransac pcr_sc2 pcr_corres pcr_segment pcr_sample pcr_orient pcr_boundary pcr_place pcr_multiway pcr_api; do
+for f in pcr_sort pcr_cloud pcr_query pcr_search pcr_keypoint pcr_cluster pcr_gicp pcr_colored pcr_vgicp pcr_vmap pcr_ndt pcr_nmap pcr_pmap pcr_ctime pcr_featnn pcr_fgr pcr_ransac pcr_sc2 pcr_corres pcr_segment pcr_sample pcr_orient pcr_boundary pcr_place pcr_multiway pcr_api; do
   [ -f $f.hip ] || continue
   stale=0
   for h in $f.hip *.h ../../include/pcr_hip.h; do [ $h -nt $f.o ] && stale=1; done

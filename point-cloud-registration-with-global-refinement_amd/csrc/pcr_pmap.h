@@ -50,3 +50,72 @@ template <bool NRM, bool EST = false> struct PmapRow {
     }
     static void set_view(Map *m, const Out &o) { m->view.xyz = o.xyz; m->view.nrm = o.nrm; m->cell_first = o.cell_first; m->ncount = o.ncount; }
 };
+
+// ================================================================ the search (pcr_pmap.hip, pcr_ctime.hip)
+__device__ static inline void pm_search(const PmapView &m, unsigned mask, int nbh, bool live, double qx, double qy, double qz, int ol, double &best_d2, int &best_row) {
+    GridView g;
+    g.tab = m.tab; g.dmask = m.dmask; g.L = 0;
+    const int cx = vg_cell(qx, m.org[0], m.voxel), cy = vg_cell(qy, m.org[1], m.voxel), cz = vg_cell(qz, m.org[2], m.voxel);
+    double bd = INFINITY; int br = 0x7fffffff;
+    const int rounds = nbh == 27 ? 4 : 1;
+    for (int r = 0; r < rounds; r++) {                                   // (wave-uniform)
+        const int k = r * 8 + ol;
+        int first = 0, cnt = 0;
+        if (live && k < nbh) {
+            int dx, dy, dz;
+            vg_offset(nbh, k, dx, dy, dz);
+            const int2 e = pcr_grid_lookup(g, mask, cx + dx, cy + dy, cz + dz);
+            if (e.y > 0) { first = e.x; cnt = e.y; }
+        }
+        if (__ballot(cnt > 0) == 0ull) continue;                         // (wave-uniform)
+        for (int l = 0; l < 8; l++) {                                    // (wave-uniform: the exchanges below are reached by all 64 lanes together)
+            const int f = __shfl(first, l, 8), c = __shfl(cnt, l, 8);
+            for (int j = ol; j < c; j += 8) {
+                const int row = f + j;
+                const float *p = m.xyz + (size_t)row * 3;
+                const double dx = qx - (double)p[0], dy = qy - (double)p[1], dz = qz - (double)p[2];
+                const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+                double d2 = xx + yy;
+                d2 = d2 + zz;
+                if (d2 < bd || (d2 == bd && row < br)) { bd = d2; br = row; }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 1; s < 8; s <<= 1) {
+        const double od = __shfl_xor(bd, s, 8); const int orow = __shfl_xor(br, s, 8);
+        if (od < bd || (od == bd && orow < br)) { bd = od; br = orow; }
+    }
+    best_d2 = bd; best_row = br == 0x7fffffff ? -1 : br;
+}
+// the match of every lane's own point: lane t of an octet holds point t of the octet's eight; round r searches for the point of lane r
+__device__ static inline void pm_match_own(const PmapView &m, int nbh, bool live, double qx, double qy, double qz, double max_d2, double &my_d2, int &my_row) {
+    const unsigned mask = *m.dmask;
+    const int ol = threadIdx.x & 7;
+    my_d2 = 0.0; my_row = -1;
+    for (int r = 0; r < 8; r++) {                                        // (wave-uniform)
+        const double bx = __shfl(qx, r, 8), by = __shfl(qy, r, 8), bz = __shfl(qz, r, 8);
+        const bool bl = __shfl(live ? 1 : 0, r, 8) != 0;
+        if (__ballot(bl) == 0ull) continue;                              // (wave-uniform)
+        double d2; int row;
+        pm_search(m, mask, nbh, bl, bx, by, bz, ol, d2, row);
+        if (ol == r && row >= 0 && d2 < max_d2) { my_d2 = d2; my_row = row; }
+    }
+}
+
+// the robust kernels of the UPDATE rule
+__device__ static inline double pm_weight(int loss, double k, double r) {
+    if (loss == PCR_LOSS_L1) return 1.0 / fmax(fabs(r), 1e-300);
+    if (loss == PCR_LOSS_GM) { const double rr = r * r; const double d = k + rr; return k / (d * d); }
+    return 1.0;
+}
+
+// what the calls that search the map check alike, and their scratch (pcr_pmap.hip): the map, the neighbourhood, the source, the distance and one pose
+// (named T_name); the estimator against the map; the source's coordinates (one read-back)
+int pm_check_search(pcr_context *ctx, const char *call, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, const char *T_name, int nbh,
+                    double max_distance);
+int pm_check_estimation(pcr_context *ctx, const char *call, const pcr_point_map *map, const pcr_estimation *est);
+int pm_check_src_finite(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src);
+size_t pm_search_scratch(int64_t n_src);
+// point to plane on a map that estimates its normals: a match whose row is not valid is no row
+static inline bool pm_reads_validity(const pcr_point_map *map, const pcr_estimation *est) { return map->estimated && est->kind == PCR_EST_POINT_TO_PLANE; }

@@ -6,7 +6,7 @@
 //                     sequences (merge, insert), or the map's own rows with a far flag (remove_far).  pm_build ranks every entry inside its
 //                     cell (head flags, their scan, the segment's start), keeps rank < M (and the flag), compacts, finds the cells of the
 //                     kept rows, and gathers rows, keys and the cell table into a new block whose cell hash map_build_block makes
-//   pm_search         the ROW rule, eight lanes per query: each lane probes one candidate cell of the cell hash per round (1 / 1 / 4 rounds for
+//   pm_search         (pcr_pmap.h, shared with pcr_ctime.hip) the ROW rule, eight lanes per query: each lane probes one candidate cell of the cell hash per round (1 / 1 / 4 rounds for
 //                     neighbourhood 1 / 7 / 27), then the octet scans the member range of every occupied cell together, lane l rows first + l,
 //                     first + l + 8, ... -- consecutive rows, so the loads of an octet are one contiguous stretch -- keeping the smallest
 //                     (float64 d^2, row); three exchange steps give the octet's minimum.  min over (d^2, row) does not depend on who saw what
@@ -32,58 +32,6 @@ static unsigned pm_blocks(size_t n) { return (unsigned)((n + PM_BS - 1) / PM_BS)
 
 struct PmPose { double T[12]; };
 
-// ================================================================ the search
-__device__ static inline void pm_search(const PmapView &m, unsigned mask, int nbh, bool live, double qx, double qy, double qz, int ol, double &best_d2, int &best_row) {
-    GridView g;
-    g.tab = m.tab; g.dmask = m.dmask; g.L = 0;
-    const int cx = vg_cell(qx, m.org[0], m.voxel), cy = vg_cell(qy, m.org[1], m.voxel), cz = vg_cell(qz, m.org[2], m.voxel);
-    double bd = INFINITY; int br = 0x7fffffff;
-    const int rounds = nbh == 27 ? 4 : 1;
-    for (int r = 0; r < rounds; r++) {                                   // (wave-uniform)
-        const int k = r * 8 + ol;
-        int first = 0, cnt = 0;
-        if (live && k < nbh) {
-            int dx, dy, dz;
-            vg_offset(nbh, k, dx, dy, dz);
-            const int2 e = pcr_grid_lookup(g, mask, cx + dx, cy + dy, cz + dz);
-            if (e.y > 0) { first = e.x; cnt = e.y; }
-        }
-        if (__ballot(cnt > 0) == 0ull) continue;                         // (wave-uniform)
-        for (int l = 0; l < 8; l++) {                                    // (wave-uniform: the exchanges below are reached by all 64 lanes together)
-            const int f = __shfl(first, l, 8), c = __shfl(cnt, l, 8);
-            for (int j = ol; j < c; j += 8) {
-                const int row = f + j;
-                const float *p = m.xyz + (size_t)row * 3;
-                const double dx = qx - (double)p[0], dy = qy - (double)p[1], dz = qz - (double)p[2];
-                const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
-                double d2 = xx + yy;
-                d2 = d2 + zz;
-                if (d2 < bd || (d2 == bd && row < br)) { bd = d2; br = row; }
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < 8; s <<= 1) {
-        const double od = __shfl_xor(bd, s, 8); const int orow = __shfl_xor(br, s, 8);
-        if (od < bd || (od == bd && orow < br)) { bd = od; br = orow; }
-    }
-    best_d2 = bd; best_row = br == 0x7fffffff ? -1 : br;
-}
-// the match of every lane's own point: lane t of an octet holds point t of the octet's eight; round r searches for the point of lane r
-__device__ static inline void pm_match_own(const PmapView &m, int nbh, bool live, double qx, double qy, double qz, double max_d2, double &my_d2, int &my_row) {
-    const unsigned mask = *m.dmask;
-    const int ol = threadIdx.x & 7;
-    my_d2 = 0.0; my_row = -1;
-    for (int r = 0; r < 8; r++) {                                        // (wave-uniform)
-        const double bx = __shfl(qx, r, 8), by = __shfl(qy, r, 8), bz = __shfl(qz, r, 8);
-        const bool bl = __shfl(live ? 1 : 0, r, 8) != 0;
-        if (__ballot(bl) == 0ull) continue;                              // (wave-uniform)
-        double d2; int row;
-        pm_search(m, mask, nbh, bl, bx, by, bz, ol, d2, row);
-        if (ol == r && row >= 0 && d2 < max_d2) { my_d2 = d2; my_row = row; }
-    }
-}
-
 // ================================================================ the iteration
 struct IcpPmapArgs {
     const float *src_xyz;      // packed, caller order
@@ -93,11 +41,6 @@ struct IcpPmapArgs {
     const int32_t *ncount;     // k_icp_iter_pmap<true> alone (point to plane on an estimated map): a match whose row has ncount < kmin is no row
     int kmin;
 };
-__device__ static inline double pm_weight(int loss, double k, double r) {
-    if (loss == PCR_LOSS_L1) return 1.0 / fmax(fabs(r), 1e-300);
-    if (loss == PCR_LOSS_GM) { const double rr = r * r; const double d = k + rr; return k / (d * d); }
-    return 1.0;
-}
 // the rows of one correspondence into the 30 sums: [0, 21) upper JTJ, [21, 27) JTr, [27] sum r^2, [28] sum d^2, [29] rows
 __device__ static inline void pm_rows(const IcpArgs &a, const IcpPmapArgs &v, double sx, double sy, double sz, int row, double d2, double *acc) {
     const float *p = v.map.xyz + (size_t)row * 3;
@@ -174,7 +117,6 @@ __global__ void __launch_bounds__(PM_BS) k_pmap_emit(const int32_t *__restrict__
     rows2[2 * (size_t)o] = i; rows2[2 * (size_t)o + 1] = match[i];
 }
 
-static inline bool pm_reads_validity(const pcr_point_map *map, const pcr_estimation *est) { return map->estimated && est->kind == PCR_EST_POINT_TO_PLANE; }
 // The loop of voxelized GICP (vgicp_loop, pcr_vgicp.hip) with this unit's kernel: one launch per iteration, chunks replayed as cached graphs.
 // single: linearise once at T0 and stop (pcr_point_map_linearize); *sums then receives the 30 sums.
 static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, const pcr_point_map *map, int neighborhood, double max_d2, const pcr_estimation *est,
@@ -770,7 +712,7 @@ extern "C" int pcr_point_map_remove_far(pcr_context *ctx, pcr_point_map *map, co
 }
 
 // ================================================================ search and registration: host
-static int pm_check_search(pcr_context *ctx, const char *call, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, const char *T_name, int nbh,
+int pm_check_search(pcr_context *ctx, const char *call, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, const char *T_name, int nbh,
                            double max_distance) {
     PCR_TRY(pm_check_map(ctx, map, call));
     if (nbh != 1 && nbh != 7 && nbh != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
@@ -778,7 +720,7 @@ static int pm_check_search(pcr_context *ctx, const char *call, const pcr_point_m
     if (!std::isfinite(max_distance) || !(max_distance > 0.0)) { ctx->err = std::string(call) + ": max_correspondence_distance must be finite and greater than 0"; return PCR_EINVAL; }
     return vg_check_T(ctx, call, T_name, T);
 }
-static int pm_check_estimation(pcr_context *ctx, const char *call, const pcr_point_map *map, const pcr_estimation *est) {
+int pm_check_estimation(pcr_context *ctx, const char *call, const pcr_point_map *map, const pcr_estimation *est) {
     if (!est) { ctx->err = std::string(call) + ": estimation is null"; return PCR_EINVAL; }
     if (est->kind != PCR_EST_POINT_TO_POINT && est->kind != PCR_EST_POINT_TO_PLANE) { ctx->err = std::string(call) + ": estimation.kind must be point to point or point to plane"; return PCR_EINVAL; }
     if (est->kind == PCR_EST_POINT_TO_POINT && est->with_scaling) { ctx->err = std::string(call) + ": estimation.with_scaling is not supported (the update is the Gauss-Newton form)"; return PCR_EINVAL; }
@@ -787,11 +729,11 @@ static int pm_check_estimation(pcr_context *ctx, const char *call, const pcr_poi
     if (est->kind == PCR_EST_POINT_TO_PLANE && !map->normals) { ctx->err = std::string(call) + ": point to plane needs a map with normals"; return PCR_EINVAL; }
     return PCR_OK;
 }
-static int pm_check_src_finite(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src) {
+int pm_check_src_finite(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src) {
     const float *ptr[1] = {src_xyz}; const size_t cnt[1] = {(size_t)n_src * 3}; const char *name[1] = {"src_xyz"};
     return vg_check_finite(ctx, call, ptr, cnt, name, 1);
 }
-static size_t pm_search_scratch(int64_t n_src) { return (size_t)(n_src > 0 ? n_src : 1) * 24 + (4u << 20); }
+size_t pm_search_scratch(int64_t n_src) { return (size_t)(n_src > 0 ? n_src : 1) * 24 + (4u << 20); }
 
 // the rows at the pose T (16 doubles, host) into rows2; scratch from the arena the caller has reserved
 // valid_only: a match whose row is not valid (ESTIMATE) is no row

@@ -71,6 +71,7 @@ class PointCloud:
         self._nrm = None          # torch (N,3) float32 cuda
         self._cov = None          # torch (N,6) float32 cuda  (xx,xy,xz,yy,yz,zz)
         self._col = None          # torch (N,3) float32 cuda  (r,g,b in [0, 1])
+        self._tim = None          # torch (N,) float32 cuda   (one time per point: the rule "continuous time" of include/pcr_hip.h)
         if points is not None:
             self.points = points
 
@@ -87,6 +88,7 @@ class PointCloud:
         self._nrm = None
         self._cov = None
         self._col = None
+        self._tim = None
 
     @property
     def normals(self):
@@ -107,6 +109,21 @@ class PointCloud:
     @colors.setter
     def colors(self, value):
         self._col = _dev_f32(value, 3)
+
+    @property
+    def times(self):
+        """One time per point, float32 (n,); empty on a cloud without times.  A spinning LiDAR measures every point of a sweep at its own time:
+        ``deskew`` and the continuous-time registration (``registration_point_map_continuous``) read them."""
+        if self._tim is None:
+            return np.zeros((0,), np.float32)
+        return self._tim.detach().cpu().numpy()
+
+    @times.setter
+    def times(self, value):
+        t = _dev_f32(value, 1).reshape(-1)
+        if t.shape[0] != len(self):
+            raise ValueError(f"times must hold one value per point ({len(self)}), got {t.shape[0]}")
+        self._tim = t.contiguous()
 
     @property
     def covariances(self):
@@ -145,6 +162,9 @@ class PointCloud:
     def has_colors(self):
         return self._col is not None and self._col.shape[0] == len(self) and len(self) > 0
 
+    def has_times(self):
+        return self._tim is not None and self._tim.shape[0] == len(self) and len(self) > 0
+
     def paint_uniform_color(self, color):
         """``PointCloud.paint_uniform_color`` (ALL_FUNCTIONS.py:23,155-156): every point gets the colour ``color`` = (r, g, b) in [0, 1]; returns self."""
         torch = _torch()
@@ -158,6 +178,7 @@ class PointCloud:
         out._nrm = None if self._nrm is None else self._nrm.clone()
         out._cov = None if self._cov is None else self._cov.clone()
         out._col = None if self._col is None else self._col.clone()
+        out._tim = None if self._tim is None else self._tim.clone()
         return out
 
     def __repr__(self):
@@ -174,6 +195,9 @@ class PointCloud:
 
     def device_colors(self):
         return self._col
+
+    def device_times(self):
+        return self._tim
 
     # ---- methods -----------------------------------------------------------------------------
     def get_min_bound(self):
@@ -214,6 +238,16 @@ class PointCloud:
             out._nrm = out_nrm[: m.value].contiguous()
         if out_col is not None:
             out._col = out_col[: m.value].contiguous()
+        if self.has_times():           # the per-voxel mean of the times, with the arithmetic of a colour channel: a second call whose colours are (t, t, t)
+            ttt = self._tim.reshape(-1, 1).repeat(1, 3).contiguous()
+            t_xyz = torch.empty((max(n, 1), 3), dtype=torch.float32, device="cuda")
+            t_col = torch.empty((max(n, 1), 3), dtype=torch.float32, device="cuda")
+            mt = C.c_int64(0)
+            ctx.check(ctx.lib.pcr_voxel_down_sample_ex(ctx.handle, _ptr(xyz), None, _ptr(ttt), C.c_int64(n), C.c_double(voxel_size), _ptr(t_xyz), None, _ptr(t_col),
+                                                       C.byref(mt)), "voxel_down_sample")
+            if mt.value != m.value:
+                raise RuntimeError("voxel_down_sample: the pass over the times gave another number of voxels")
+            out._tim = t_col[: m.value, 0].contiguous()
         return out
 
     def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
@@ -396,6 +430,8 @@ class PointCloud:
             out._cov = self._cov[idx].contiguous()
         if self.has_colors():
             out._col = self._col[idx].contiguous()
+        if self.has_times():
+            out._tim = self._tim[idx].contiguous()
         return out
 
     def random_down_sample(self, sampling_ratio: float, seed=None) -> "PointCloud":
@@ -435,8 +471,46 @@ class PointCloud:
                                                    C.c_double(radius), _ptr(out)), "estimate_covariances")
         self._cov = out[:n].contiguous()
 
+    def deskew(self, motion, reference: float = 1.0, t_begin=None, t_end=None) -> "PointCloud":
+        """The cloud with the motion of the sensor during the sweep taken out (``pcr_deskew``; DESKEW of include/pcr_hip.h, KISS-ICP's step):
+        ``motion`` is the relative motion ``inv(T_begin) @ T_end`` over the sweep (4x4), a point measured at the fraction
+        ``alpha = (time - t_begin) / (t_end - t_begin)`` of it is moved into the sensor frame at the fraction ``reference`` (1.0: the end of
+        the sweep, so that the pose a rigid registration then finds is the END pose; 0.5: the middle, as KISS-ICP's earlier releases).
+        ``t_begin`` / ``t_end`` default to the cloud's minimum / maximum time; ``alpha`` is not clamped.  Normals are rotated the same way
+        (not normalised), times and colours are carried unchanged; covariances are NOT carried (the result has none).  Needs times."""
+        fn = "PointCloud.deskew"
+        if not self.has_times():
+            raise RuntimeError(f"{fn}: the cloud has no times (PointCloud.times)")
+        D = np.ascontiguousarray(np.asarray(motion, dtype=np.float64))
+        if D.shape != (4, 4):
+            raise ValueError(f"{fn}: motion must have shape (4, 4), got {D.shape}")
+        t0, t1 = self._time_span(fn, t_begin, t_end)
+        ctx = _lib.Context.current()
+        torch = _torch()
+        n = len(self)
+        out = PointCloud()
+        out._xyz = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        has_n = self.has_normals()
+        if has_n:
+            out._nrm = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        ctx.check(ctx.lib.pcr_deskew(ctx.handle, _ptr(self._xyz), _ptr(self._nrm if has_n else None), _ptr(self._tim), C.c_int64(n),
+                                     D.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(t0), C.c_double(t1), C.c_double(float(reference)), _ptr(out._xyz),
+                                     _ptr(out._nrm if has_n else None)), fn)
+        out._tim = self._tim.clone()
+        if self.has_colors():
+            out._col = self._col.clone()
+        return out
+
+    def _time_span(self, fn, t_begin=None, t_end=None):
+        """(t0, t1) of the TIMES rule as Python floats: the arguments, or the cloud's minimum / maximum time; ``ValueError`` unless t0 < t1"""
+        t0 = float(self._tim.min().item()) if t_begin is None else float(t_begin)
+        t1 = float(self._tim.max().item()) if t_end is None else float(t_end)
+        if not (np.isfinite(t0) and np.isfinite(t1) and t1 > t0):
+            raise ValueError(f"{fn}: t_end must be greater than t_begin and both finite, got {t0!r}, {t1!r}")
+        return t0, t1
+
     def transform(self, T):
-        """In place, like Open3D (points, normals; covariances rotated; colours untouched)."""
+        """In place, like Open3D (points, normals; covariances rotated; colours and times untouched)."""
         torch = _torch()
         T = np.asarray(T, dtype=np.float64).reshape(4, 4)
         R = torch.as_tensor(T[:3, :3], dtype=torch.float64, device="cuda")

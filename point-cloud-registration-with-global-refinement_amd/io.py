@@ -177,6 +177,40 @@ def write_pcd_xyz(path: str, xyz: np.ndarray) -> None:
         f.write(xyz.tobytes())
 
 
+_PCD_TIME_FIELDS = ("time", "t", "timestamp")
+
+
+def read_pcd_times(path: str, field=None):
+    """The per-point times of a PCD file as an (N,) float32 array, for the points ``read_pcd_xyz`` keeps (non-finite points are dropped): the
+    4-byte float field ``field``, or with ``field=None`` the first of ``time`` / ``t`` / ``timestamp`` the file has; ``None`` when the file
+    has no such float32 field."""
+    rec = _read_pcd_records(path)
+    names = rec.dtype.names or ()
+    name = next((f for f in ((field,) if field is not None else _PCD_TIME_FIELDS) if f in names), None)
+    if name is None or rec.dtype[name] != np.dtype("<f4"):
+        return None
+    xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32)
+    ok = np.isfinite(xyz).all(axis=1)
+    return np.ascontiguousarray(rec[name][ok], dtype=np.float32)
+
+
+def write_pcd_xyzt(path: str, xyz: np.ndarray, times: np.ndarray) -> None:
+    """Write points and one float32 time per point as the binary PCD v0.7 layout ``x y z time``."""
+    xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(times, dtype="<f4").reshape(-1)
+    if t.shape[0] != xyz.shape[0]:
+        raise ValueError("write_pcd_xyzt: one time per point is required")
+    n = xyz.shape[0]
+    rec = np.empty(n, dtype=[("xyz", "<f4", (3,)), ("time", "<f4")])
+    rec["xyz"] = xyz
+    rec["time"] = t
+    hdr = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z time\nSIZE 4 4 4 4\nTYPE F F F F\n"
+           f"COUNT 1 1 1 1\nWIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(rec.tobytes())
+
+
 def read_pose(path: str) -> np.ndarray:
     T = np.loadtxt(path, dtype=np.float64)
     if T.shape != (4, 4):

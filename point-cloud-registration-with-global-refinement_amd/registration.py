@@ -688,12 +688,12 @@ def registration_voxelized_gicp(source: PointCloud, target_or_map, voxel_size=No
             own.close()
 
 
-def _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register):
+def _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register, prepare=None):
     """The recipe of ``scan_to_map_odometry`` and ``scan_to_map_odometry_ndt`` -> ``(poses, results, map)``: the argument checks
     (``check_rule()`` for the caller's own, ``check_scan(k, scan)`` per scan), ``map = make_map(scans[0], grid_min, init)`` with
     ``centered_grid_min`` of scan 0's centre placed at ``init`` for a ``grid_min`` of ``None``, then per further scan
-    ``register(scan, map, start)`` from the motion model's start, ``map.insert`` and, with a ``max_range``, ``map.remove_far``.  An error
-    closes the map."""
+    ``register(scan, map, start)`` from the motion model's start, ``map.insert`` and, with a ``max_range``, ``map.remove_far``.  With a
+    ``prepare(k, scan, poses)`` the scan it returns is what is registered and inserted.  An error closes the map."""
     if motion_model not in ("constant_velocity", "static"):
         raise ValueError(f"{fn}: motion_model must be 'constant_velocity' or 'static', got {motion_model!r}")
     _check_voxel_size(fn, voxel_size)
@@ -718,10 +718,11 @@ def _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min,
             start = poses[-1]
             if motion_model == "constant_velocity" and k >= 2:
                 start = poses[-1] @ np.linalg.inv(poses[-2]) @ poses[-1]
-            res = register(scans[k], gmap, start)
+            scan = scans[k] if prepare is None else prepare(k, scans[k], poses)
+            res = register(scan, gmap, start)
             poses.append(np.array(res.transformation, np.float64))
             results.append(res)
-            gmap.insert(scans[k], poses[-1])
+            gmap.insert(scan, poses[-1])
             if max_range is not None:
                 gmap.remove_far(poses[-1][:3, 3], max_range)
     except BaseException:
@@ -1239,6 +1240,37 @@ class VoxelPointMap(_GrowingVoxelMap):
                                                   JTJ.ctypes.data_as(dp), JTr.ctypes.data_as(dp), C.byref(rows), C.byref(sum_d2), C.byref(sum_r2)), fn)
         return PointMapLinearization(JTJ, JTr, int(rows.value), float(sum_d2.value), float(sum_r2.value))
 
+    def linearize_continuous(self, source: PointCloud, T_begin, T_end, max_correspondence_distance, estimation_method=None, neighborhood: int = 27, t_begin=None, t_end=None,
+                             return_matches: bool = False) -> "ContinuousTimeLinearization":
+        """The sums of one continuous-time update at the pose pair (``T_begin``, ``T_end``) of the sweep
+        (``pcr_point_map_linearize_continuous``, one launch, the same bits on every run): every source point is placed at the pose
+        interpolated at its own time (``source.times``; ``t_begin`` / ``t_end`` default to their minimum / maximum), matched by the map's own
+        rule, and gives the 12-column rows ``[(1 - alpha) J6, alpha J6]`` of include/pcr_hip.h (continuous time): ``H`` (12, 12), ``g`` (12,),
+        ``rows``, ``sum_d2``, ``sum_r2`` and, with ``return_matches``, ``matches`` -- a device int32 tensor with the map row of every source
+        point, or -1."""
+        fn = "VoxelPointMap.linearize_continuous"
+        _check_point_map_rule(fn, neighborhood)
+        d = _check_distance(fn, max_correspondence_distance)
+        est = _point_map_estimation(fn, estimation_method)
+        if not isinstance(source, PointCloud) or not source.has_times():
+            raise RuntimeError(f"{fn}: the source must be a PointCloud with times (PointCloud.times)")
+        t0, t1 = source._time_span(fn, t_begin, t_end)
+        h = self._open()
+        if est.kind == _lib.EST_POINT_TO_PLANE and not self.has_normals:
+            raise RuntimeError(f"{fn}: TransformationEstimationPointToPlane needs a map with normals")
+        ctx = _lib.Context.current()
+        ns = len(source)
+        H, g = np.zeros((12, 12), np.float64), np.zeros(12, np.float64)
+        sum_d2, sum_r2, rows = C.c_double(0), C.c_double(0), C.c_int64(0)
+        matches = _torch().empty((ns,), dtype=_torch().int32, device="cuda") if return_matches else None
+        _, Tb = _T(T_begin)
+        _, Te = _T(T_end)
+        dp = C.POINTER(C.c_double)
+        ctx.check(ctx.lib.pcr_point_map_linearize_continuous(ctx.handle, h, _ptr(source.device_xyz()), _ptr(source.device_times()), C.c_int64(ns), Tb, Te, C.c_double(t0),
+                                                             C.c_double(t1), C.c_double(d), C.c_int(int(neighborhood)), C.byref(est), H.ctypes.data_as(dp), g.ctypes.data_as(dp),
+                                                             C.byref(rows), C.byref(sum_d2), C.byref(sum_r2), _ptr(matches)), fn)
+        return ContinuousTimeLinearization(H, g, int(rows.value), float(sum_d2.value), float(sum_r2.value), matches)
+
 
 def registration_point_map(source: PointCloud, target_or_map, max_correspondence_distance, voxel_size=None, init=np.eye(4), estimation_method=None, criteria=None,
                            neighborhood: int = 27, max_points_per_voxel: int = 20) -> RegistrationResult:
@@ -1281,6 +1313,194 @@ def registration_point_map(source: PointCloud, target_or_map, max_correspondence
         ctx.check(ctx.lib.pcr_registration_point_map(ctx.handle, _ptr(source.device_xyz()), C.c_int64(ns), pmap._open(), C.c_double(d), Tp, C.byref(p), C.byref(res),
                                                      _ptr(corr)), fn)
         return _result(res, corr)
+    finally:
+        if own is not None:
+            own.close()
+
+
+class ContinuousTimeLinearization:
+    """What ``VoxelPointMap.linearize_continuous`` returns: ``H`` (12, 12), ``g`` (12,), ``rows``, ``sum_d2``, ``sum_r2``, ``matches`` (or None)."""
+
+    def __init__(self, H, g, rows, sum_d2, sum_r2, matches=None):
+        self.H, self.g, self.rows, self.sum_d2, self.sum_r2, self.matches = H, g, rows, sum_d2, sum_r2, matches
+
+    def __repr__(self):
+        return f"ContinuousTimeLinearization(rows={self.rows}, sum_d2={self.sum_d2!r}, sum_r2={self.sum_r2!r})"
+
+
+class ContinuousTimeResult:
+    """What ``registration_point_map_continuous`` returns: ``begin_pose`` and ``end_pose`` of the sweep (4x4 float64), ``transformation`` (the
+    end pose), ``fitness``, ``inlier_rmse``, ``iterations``, ``converged`` and ``correspondence_set`` ((source index, map row) at the
+    returned poses, int32)."""
+
+    def __init__(self, begin_pose, end_pose, fitness, inlier_rmse, iterations, converged, matches=None):
+        self.begin_pose = np.array(begin_pose, np.float64).reshape(4, 4)
+        self.end_pose = np.array(end_pose, np.float64).reshape(4, 4)
+        self.transformation = self.end_pose
+        self.fitness, self.inlier_rmse, self.iterations, self.converged = float(fitness), float(inlier_rmse), int(iterations), bool(converged)
+        self._matches = matches
+
+    @property
+    def correspondence_set(self):
+        if self._matches is None:
+            return np.zeros((0, 2), np.int32)
+        m = self._matches if isinstance(self._matches, np.ndarray) else self._matches.cpu().numpy()
+        self._matches = m
+        i = np.nonzero(m >= 0)[0]
+        return np.stack([i, m[i]], 1).astype(np.int32)
+
+    def __repr__(self):
+        return f"ContinuousTimeResult with fitness={self.fitness:e}, inlier_rmse={self.inlier_rmse:e}, iterations={self.iterations}"
+
+
+def _ct_exp3(v) -> np.ndarray:
+    """E(v) = I + A [v]x + B [v]x^2 of the rule (include/pcr_hip.h, continuous time), float64"""
+    x, y, z = (float(c) for c in np.asarray(v, np.float64).reshape(3))
+    xx, yy, zz = x * x, y * y, z * z
+    t2 = (xx + yy) + zz
+    th = np.sqrt(t2)
+    if th >= 1e-4:
+        A, B = np.sin(th) / th, (1.0 - np.cos(th)) / t2
+    else:
+        A, B = 1.0 - t2 / 6.0, 0.5 - t2 / 24.0
+    xy, xz, yz = x * y, x * z, y * z
+    return np.array([[1.0 - B * (yy + zz), B * xy - A * z, B * xz + A * y],
+                     [B * xy + A * z, 1.0 - B * (xx + zz), B * yz - A * x],
+                     [B * xz - A * y, B * yz + A * x, 1.0 - B * (xx + yy)]], np.float64)
+
+
+def _ct_log3(R) -> np.ndarray:
+    """Log(R): the rotation vector with its angle in [0, pi] (the host expression of pcr_ctime.hip)"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) * 0.5
+    s = np.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    c = ((R[0, 0] + R[1, 1]) + R[2, 2] - 1.0) * 0.5
+    theta = np.arctan2(s, c)
+    if s < 1e-8 and c > 0.0:
+        return w
+    if c > -0.99:
+        return w * (theta / s)
+    d = np.diag(R)
+    k = int(np.argmax(d))
+    a = np.zeros(3)
+    a[k] = np.sqrt(max((d[k] - c) / (1.0 - c), 0.0))
+    for j in range(3):
+        if j != k:
+            a[j] = (R[k, j] + R[j, k]) * 0.5 / ((1.0 - c) * a[k]) if a[k] > 0.0 else 0.0
+    n = np.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
+    sign = -1.0 if (a[0] * w[0] + a[1] * w[1]) + a[2] * w[2] < 0.0 else 1.0
+    return sign * theta * a / n if n > 0.0 else np.zeros(3)
+
+
+def _ct_step(H, g, rows, T_b, T_e, begin, prior, prior_weight):
+    """STEP of the rule -> (T_b, T_e, applied): the Cholesky solve of the free block and the update of the poses; a failed factorisation or a
+    non-finite solution applies nothing"""
+    T_b, T_e = np.array(T_b, np.float64), np.array(T_e, np.float64)
+    H, g = np.array(H, np.float64), np.array(g, np.float64)
+    if begin == "free" and prior_weight is not None:
+        w_rot, w_trans = float(prior_weight[0]), float(prior_weight[1])
+        H[0:3, 0:3] += rows * w_rot * np.eye(3)
+        H[3:6, 3:6] += rows * w_trans * np.eye(3)
+        g[0:3] += rows * w_rot * _ct_log3(T_b[:3, :3] @ prior[:3, :3].T)
+        g[3:6] += rows * w_trans * (T_b[:3, 3] - prior[:3, 3])
+    lo = 6 if begin == "fixed" else 0
+    delta = np.zeros(12)
+    try:
+        L = np.linalg.cholesky(H[lo:, lo:])
+        delta[lo:] = -np.linalg.solve(L.T, np.linalg.solve(L, g[lo:]))
+    except np.linalg.LinAlgError:
+        return T_b, T_e, False
+    if not np.isfinite(delta).all():
+        return T_b, T_e, False
+    if begin != "fixed":
+        T_b[:3, :3] = _ct_exp3(delta[0:3]) @ T_b[:3, :3]
+        T_b[:3, 3] = T_b[:3, 3] + delta[3:6]
+    T_e[:3, :3] = _ct_exp3(delta[6:9]) @ T_e[:3, :3]
+    T_e[:3, 3] = T_e[:3, 3] + delta[9:12]
+    return T_b, T_e, True
+
+
+def _check_ct_begin(fn, begin, begin_prior_weight):
+    if begin not in ("fixed", "free"):
+        raise ValueError(f"{fn}: begin must be 'fixed' or 'free', got {begin!r}")
+    if begin_prior_weight is None:
+        return None
+    if begin != "free":
+        raise ValueError(f"{fn}: begin_prior_weight needs begin='free'")
+    try:
+        w = (float(begin_prior_weight[0]), float(begin_prior_weight[1]))
+        ok = len(begin_prior_weight) == 2
+    except (TypeError, ValueError, IndexError):
+        ok, w = False, None
+    if not ok or not all(np.isfinite(v) and v >= 0.0 for v in w):
+        raise ValueError(f"{fn}: begin_prior_weight must be two finite numbers (w_rot, w_trans) >= 0, got {begin_prior_weight!r}")
+    return w
+
+
+def _ct_pose(fn, name, T):
+    T = np.array(np.asarray(T, np.float64), np.float64)
+    if T.shape != (4, 4):
+        raise ValueError(f"{fn}: {name} must have shape (4, 4), got {T.shape}")
+    return T
+
+
+def registration_point_map_continuous(source: PointCloud, target_or_map, max_correspondence_distance, T_begin, T_end=None, voxel_size=None, estimation_method=None,
+                                      criteria=None, neighborhood: int = 27, max_points_per_voxel: int = 20, begin: str = "fixed", begin_prior_weight=None, t_begin=None,
+                                      t_end=None) -> ContinuousTimeResult:
+    """Continuous-time scan-to-map ICP (CT-ICP's elastic formulation as include/pcr_hip.h, continuous time, specifies it; not compared with
+    CT-ICP's code): the registration estimates the pose of the sensor at the begin and at the end of the sweep, and every source point is
+    placed at the pose interpolated at its own time (``source.times``; ``t_begin`` / ``t_end`` default to their minimum / maximum).  The loop
+    is RegistrationICP's, on the host: ``VoxelPointMap.linearize_continuous`` at the start poses (``T_end=None``: ``T_begin``), then a
+    Cholesky step on the 12x12 system and the sums again, until the criteria hold or ``max_iteration`` -- one launch and one read-back of 160
+    doubles per iteration.  ``begin="fixed"`` (the default) keeps ``T_begin`` bit for bit -- it is the end pose of the sweep before -- and
+    estimates the end pose alone; ``begin="free"`` estimates both, optionally held to the given ``T_begin`` by ``begin_prior_weight=(w_rot,
+    w_trans)`` per row.  The estimators, the neighbourhoods and the map are those of ``registration_point_map``.  The rotation columns are
+    first order in the rotation between the two poses (exact when there is none)."""
+    fn = "registration_point_map_continuous"
+    _check_point_map_rule(fn, neighborhood, max_points_per_voxel)
+    d = _check_distance(fn, max_correspondence_distance)
+    _point_map_estimation(fn, estimation_method)
+    prior_weight = _check_ct_begin(fn, begin, begin_prior_weight)
+    criteria = criteria or ICPConvergenceCriteria()
+    T_b = _ct_pose(fn, "T_begin", T_begin)
+    T_e = T_b.copy() if T_end is None else _ct_pose(fn, "T_end", T_end)
+    if not isinstance(source, PointCloud) or not source.has_times():
+        raise RuntimeError(f"{fn}: the source must be a PointCloud with times (PointCloud.times)")
+    t0, t1 = source._time_span(fn, t_begin, t_end)
+    own = None
+    if isinstance(target_or_map, VoxelPointMap):
+        pmap = target_or_map
+        pmap._open()
+    elif isinstance(target_or_map, PointCloud):
+        if voxel_size is None:
+            raise ValueError(f"{fn}: voxel_size is required when the target is a PointCloud")
+        _check_voxel_size(fn, voxel_size)
+        own = pmap = VoxelPointMap(target_or_map, voxel_size, max_points_per_voxel)
+    else:
+        raise TypeError(f"{fn}: the target must be a PointCloud or a VoxelPointMap, got {type(target_or_map).__name__}")
+    try:
+        n = len(source)
+        prior = T_b.copy()
+
+        def sums(T_b, T_e):
+            s = pmap.linearize_continuous(source, T_b, T_e, d, estimation_method, neighborhood, t0, t1, True)
+            return s, (s.rows / n if n else 0.0), (float(np.sqrt(s.sum_d2 / s.rows)) if s.rows else 0.0)
+
+        s, fit, rmse = sums(T_b, T_e)
+        it, converged = 0, False
+        while it < int(criteria.max_iteration):
+            applied = False
+            if s.rows:
+                T_b, T_e, applied = _ct_step(s.H, s.g, s.rows, T_b, T_e, begin, prior, prior_weight)
+            if not applied:
+                break
+            before = (fit, rmse)
+            s, fit, rmse = sums(T_b, T_e)
+            it += 1
+            if abs(before[0] - fit) < float(criteria.relative_fitness) and abs(before[1] - rmse) < float(criteria.relative_rmse):
+                converged = True
+                break
+        return ContinuousTimeResult(T_b, T_e, fit, rmse, it, converged, s.matches)
     finally:
         if own is not None:
             own.close()
@@ -1367,8 +1587,9 @@ def scan_to_map_odometry_icp_map_normals(scans, voxel_size, max_correspondence_d
 
 
 def _scan_to_map_odometry_icp(fn, scans, voxel_size, max_correspondence_distance, init, estimation_method, criteria, neighborhood, max_points_per_voxel, motion_model,
-                              max_range, grid_min, adaptive_threshold, map_normals, map_normal_radius, map_normal_min_neighbors):
-    """the body of ``scan_to_map_odometry_icp`` (``map_normals`` False) and of ``scan_to_map_odometry_icp_map_normals`` (True)"""
+                              max_range, grid_min, adaptive_threshold, map_normals, map_normal_radius, map_normal_min_neighbors, deskew=False):
+    """the body of ``scan_to_map_odometry_icp`` (``map_normals`` False) and of ``scan_to_map_odometry_icp_map_normals`` (True); ``deskew``: that of
+    ``scan_to_map_odometry_icp_deskew``"""
     estimation = TransformationEstimationPointToPoint() if estimation_method is None else estimation_method
     plane = isinstance(estimation, TransformationEstimationPointToPlane)
 
@@ -1399,6 +1620,13 @@ def _scan_to_map_odometry_icp(fn, scans, voxel_size, max_correspondence_distance
             raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
         if plane and not map_normals and not s.has_normals():
             raise RuntimeError(f"{fn}: scan {k} has no normals (TransformationEstimationPointToPlane needs a map with normals; see scan_to_map_odometry_icp_map_normals)")
+        if deskew and not s.has_times():
+            raise RuntimeError(f"{fn}: scan {k} has no times (deskewing needs PointCloud.times on every scan)")
+
+    prepare = None
+    if deskew and motion_model == "constant_velocity":
+        def prepare(k, s, poses):
+            return s.deskew(np.linalg.inv(poses[-2]) @ poses[-1]) if k >= 2 else s
 
     def register(s, m, start):
         if adaptive_threshold is None:
@@ -1422,7 +1650,79 @@ def _scan_to_map_odometry_icp(fn, scans, voxel_size, max_correspondence_distance
             raise
         return m
 
-    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register)
+    return _scan_to_map(fn, scans, voxel_size, init, motion_model, max_range, grid_min, check_rule, check_scan, make_map, register, prepare)
+
+
+def scan_to_map_odometry_icp_deskew(scans, voxel_size, max_correspondence_distance=None, init=np.eye(4), estimation_method=None, criteria=None, neighborhood: int = 27,
+                                    max_points_per_voxel: int = 20, motion_model: str = "constant_velocity", max_range=None, grid_min=None, adaptive_threshold=None,
+                                    map_normals: bool = False, map_normal_radius=None, map_normal_min_neighbors: int = 5):
+    """``scan_to_map_odometry_icp`` (``map_normals=False``) or ``scan_to_map_odometry_icp_map_normals`` (``True``) WITH deskewing -- KISS-ICP's
+    whole recipe -> ``(poses, results, map)``.  Every scan must carry times.  Under ``"constant_velocity"`` scan k >= 2 is replaced by
+    ``scans[k].deskew(inv(poses[k - 2]) @ poses[k - 1])`` -- the motion of the sweep before, taken as the motion of this one, with the end of
+    the sweep as the reference -- before it is registered and inserted; scans 0 and 1, and every scan under ``"static"``, are taken as they
+    are.  Everything else is the recipe of the function it extends, call by call.  It is a function of its own so that the two others keep
+    their signatures."""
+    fn = "scan_to_map_odometry_icp_deskew"
+    est = estimation_method
+    if map_normals and est is None:
+        est = TransformationEstimationPointToPlane()
+    return _scan_to_map_odometry_icp(fn, scans, voxel_size, max_correspondence_distance, init, est, criteria, neighborhood, max_points_per_voxel, motion_model, max_range,
+                                     grid_min, adaptive_threshold, bool(map_normals), map_normal_radius, map_normal_min_neighbors, deskew=True)
+
+
+def scan_to_map_odometry_ct(scans, voxel_size, max_correspondence_distance, init=np.eye(4), estimation_method=None, criteria=None, neighborhood: int = 27,
+                            max_points_per_voxel: int = 20, max_range=None, grid_min=None, begin: str = "fixed", begin_prior_weight=None):
+    """LiDAR odometry by continuous-time scan-to-map ICP on a ``VoxelPointMap`` -> ``(begin_poses, end_poses, results, map)``.  Every scan
+    from the second on must carry times.  Exactly these public calls, in this order:
+
+    * ``map = VoxelPointMap.on_grid(scans[0], voxel_size, max_points_per_voxel, grid_min, init)`` -- scan 0 as it is; ``grid_min=None`` is
+      ``centered_grid_min`` of scan 0's centre placed at ``init``; ``begin_poses[0] = end_poses[0] = init``, ``results[0] = None``;
+    * for every further scan k: ``T_b = end_poses[k - 1]`` and ``T_e = end_poses[k - 1] @ inv(begin_poses[k - 1]) @ end_poses[k - 1]`` (for
+      k = 1 that is ``T_b``), then ``results[k] = registration_point_map_continuous(scans[k], map, max_correspondence_distance, T_b, T_e,
+      None, estimation_method, criteria, neighborhood, max_points_per_voxel, begin, begin_prior_weight)``; ``begin_poses[k]`` and
+      ``end_poses[k]`` are its poses (with ``begin="fixed"``, ``begin_poses[k]`` is ``end_poses[k - 1]`` bit for bit);
+    * ``map.insert(scans[k].deskew(inv(begin_poses[k]) @ end_poses[k], reference=1.0), end_poses[k])``, and with a ``max_range``,
+      ``map.remove_far(end_poses[k][:3, 3], max_range)``.
+
+    Point to plane needs normals on every scan.  The caller owns the returned map and closes it."""
+    fn = "scan_to_map_odometry_ct"
+    _check_voxel_size(fn, voxel_size)
+    _check_point_map_rule(fn, neighborhood, max_points_per_voxel)
+    _check_distance(fn, max_correspondence_distance)
+    est = _point_map_estimation(fn, estimation_method)
+    _check_ct_begin(fn, begin, begin_prior_weight)
+    if max_range is not None and (not np.isfinite(float(max_range)) or not float(max_range) > 0.0):
+        raise ValueError(f"{fn}: max_range must be a finite number greater than 0, got {max_range!r}")
+    scans = list(scans)
+    if not scans:
+        raise ValueError(f"{fn}: at least one scan is needed")
+    for k, s in enumerate(scans):
+        if not isinstance(s, PointCloud) or len(s) == 0:
+            raise RuntimeError(f"{fn}: scan {k} must be a PointCloud with at least one point")
+        if k and not s.has_times():
+            raise RuntimeError(f"{fn}: scan {k} has no times (PointCloud.times)")
+        if est.kind == _lib.EST_POINT_TO_PLANE and not s.has_normals():
+            raise RuntimeError(f"{fn}: scan {k} has no normals (TransformationEstimationPointToPlane needs a map with normals)")
+    P0 = _ct_pose(fn, "init", init)
+    if grid_min is None:
+        c = np.asarray(scans[0].get_center(), np.float64).reshape(3)
+        grid_min = _GrowingVoxelMap.centered_grid_min(P0[:3, :3] @ c + P0[:3, 3], voxel_size)
+    gmap = VoxelPointMap.on_grid(scans[0], voxel_size, max_points_per_voxel, grid_min, P0)
+    begins, ends, results = [P0], [P0], [None]
+    try:
+        for k in range(1, len(scans)):
+            T_b = ends[-1]
+            T_e = ends[-1] @ np.linalg.inv(begins[-1]) @ ends[-1] if k > 1 else T_b
+            res = registration_point_map_continuous(scans[k], gmap, max_correspondence_distance, T_b, T_e, None, estimation_method, criteria, neighborhood,
+                                                    max_points_per_voxel, begin, begin_prior_weight)
+            begins.append(res.begin_pose); ends.append(res.end_pose); results.append(res)
+            gmap.insert(scans[k].deskew(np.linalg.inv(res.begin_pose) @ res.end_pose, reference=1.0), res.end_pose)
+            if max_range is not None:
+                gmap.remove_far(res.end_pose[:3, 3], max_range)
+    except BaseException:
+        gmap.close()
+        raise
+    return begins, ends, results, gmap
 
 
 def multiscale_gicp(source: PointCloud, target: PointCloud, voxel_sizes, max_correspondence_distances, init=np.eye(4),

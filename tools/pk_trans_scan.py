@@ -12,7 +12,7 @@ atexit.register(shutil.rmtree, tmp, True)
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 csrc = os.path.join(root, "point-cloud-registration-with-global-refinement_amd", "csrc")
 llvm = "/opt/rocm/lib/llvm/bin"
-units = sys.argv[1:] or ["pcr_sort", "pcr_cloud", "pcr_keypoint", "pcr_cluster", "pcr_gicp", "pcr_colored", "pcr_vgicp", "pcr_vmap", "pcr_ndt", "pcr_nmap", "pcr_pmap", "pcr_featnn", "pcr_fgr", "pcr_ransac", "pcr_sc2", "pcr_corres", "pcr_segment", "pcr_sample", "pcr_orient", "pcr_boundary", "pcr_place", "pcr_multiway", "pcr_api"]
+units = sys.argv[1:] or ["pcr_sort", "pcr_cloud", "pcr_keypoint", "pcr_cluster", "pcr_gicp", "pcr_colored", "pcr_vgicp", "pcr_vmap", "pcr_ndt", "pcr_nmap", "pcr_pmap", "pcr_ctime", "pcr_featnn", "pcr_fgr", "pcr_ransac", "pcr_sc2", "pcr_corres", "pcr_segment", "pcr_sample", "pcr_orient", "pcr_boundary", "pcr_place", "pcr_multiway", "pcr_api"]
 TRANS = re.compile(r"^v_(rsq|rcp|sqrt|exp|log|sin|cos|rcp_iflag)_(f32|f16|f64|legacy_f32)")
 WINDOW = 64
 def regs(tok):
