@@ -194,25 +194,8 @@ __global__ void __launch_bounds__(CT_BS) k_pmap_lin_ct(CtLinArgs a) {
     for (int k = 0; k < 27; k++) A[k] = 0.0;
     double sr2 = 0.0, sd2 = 0.0, cnt = 0.0;
     if (live && row >= 0) {
-        const float *p = a.map.xyz + (size_t)row * 3;
-        const double ex = qx - (double)p[0], ey = qy - (double)p[1], ez = qz - (double)p[2];
         sd2 = d2; cnt = 1.0;
-        if (a.plane) {
-            const float *nf = a.map.nrm + (size_t)row * 3;
-            const double nx = nf[0], ny = nf[1], nz = nf[2];
-            double r = ex * nx + ey * ny;
-            r = r + ez * nz;
-            const double J[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
-            sr2 = r * r;
-            icp_row6(pm_weight(a.loss, a.loss_k, r), J, r, A);
-        } else {
-            double nn = ex * ex + ey * ey;
-            nn = nn + ez * ez;
-            const double w = pm_weight(a.loss, a.loss_k, sqrt(nn));
-            sr2 = nn;
-            const double J0[6] = {0.0, uz, -uy, 1.0, 0.0, 0.0}, J1[6] = {-uz, 0.0, ux, 0.0, 1.0, 0.0}, J2[6] = {uy, -ux, 0.0, 0.0, 0.0, 1.0};
-            icp_row6(w, J0, ex, A); icp_row6(w, J1, ey, A); icp_row6(w, J2, ez, A);
-        }
+        sr2 = pm_row27(a.map, a.plane, a.loss, a.loss_k, row, qx, qy, qz, ux, uy, uz, A);      // (the lever is u = R p)
     }
     // ---- the workgroup's sums: three passes of the halving butterfly (lane r of a 16-lane row ends with the sums of values r and 16 + r), so that a
     // lane holds one alpha moment of the rigid part at a time, then the 32 rows in order

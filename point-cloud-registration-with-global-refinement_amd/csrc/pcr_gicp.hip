@@ -24,8 +24,7 @@
 #include "pcr_solve6.h"
 
 #include "pcr_icp_loop.h"
-__global__ void k_icp_init(IcpState *st, IcpInit in) { d_icp_init(st, in); }
-// group form: state g of a lockstep group starts from pose g (poses in device memory)
+// (k_icp_init: pcr_icp_loop.h)  group form: state g of a lockstep group starts from pose g (poses in device memory)
 __global__ void k_icp_init_g(IcpState *st, const IcpInit *in) { d_icp_init(st + blockIdx.x, in[blockIdx.x]); }
 
 // ---- exact 1-NN of one query per octet over the target's linear octree.  Called by all 64 lanes of a wavefront;

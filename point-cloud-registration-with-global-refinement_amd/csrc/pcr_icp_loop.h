@@ -1,7 +1,10 @@
 // pcr_icp_loop.h -- what the iteration kernels of the ICP loops share, and the host side of a loop: the problem state and the argument block, the
 // end of an iteration (icp_finish: workgroup reduction, last-workgroup gather, convergence test, 6x6 solve, pose update), the graph cache and the
-// chunk pump.  Included by pcr_gicp.hip (GICP, the three ICP estimators, colored ICP, the lockstep groups), by pcr_vgicp.hip (voxelized GICP) and by
-// pcr_ndt.hip (NDT), each of which is a unit of its own so that the search kernels of pcr_gicp.hip compile to what they compiled to before it existed.
+// chunk pump; and the frame of the map loops, whose iteration is ONE kernel over the source points in caller order (icp_iter_frame on the device,
+// icp_map_loop on the host).  Included by pcr_gicp.hip (GICP, the three ICP estimators, colored ICP, the lockstep groups), by
+// pcr_vgicp.hip (voxelized GICP), pcr_ndt.hip (NDT) and pcr_pmap.hip (the voxel point map), which run a map loop, and by pcr_ctime.hip (continuous
+// time, for icp_row6 and the tile size); each is a unit of its own so that the search kernels of pcr_gicp.hip compile to what they compiled to
+// before the others existed.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -76,6 +79,8 @@ __device__ static inline void d_icp_init(IcpState *st, const IcpInit &in) {
         for (int k = 0; k < NVP; k++) st->sums[k] = 0;
     }
 }
+// the one init kernel of every loop that starts from one pose (internal linkage: every unit that includes this header gets its own)
+__global__ static void k_icp_init(IcpState *st, IcpInit in) { d_icp_init(st, in); }
 
 // ---- workgroup reduction of acc[], write-through partial row + ticket, and -- in the last-arriving workgroup -- the end of
 // the iteration: gather the rows, fixed-order sums, convergence test, 6x6 solve, pose update.  BS = workgroup size.
@@ -256,6 +261,30 @@ __device__ static inline void icp_finish(const IcpArgs &a, IcpState *st, const d
     }
 }
 
+// ---- the frame of an iteration kernel that is the whole iteration (the map loops: no search kernel in front of it).  Workgroup b owns the source
+// points [BS b, BS b + BS) in caller order.  The frame owns the exit of a finished loop and of surplus workgroups, the entry stamp, the pose, the
+// zeroed sums and icp_finish; point(i, live, T, acc) adds the rows of source point i at the pose T into the lane's sums.  EVERY lane makes the call
+// (live = i < ns), so that a body may exchange values across lanes.
+template <int MODE, int BS, class Point>
+__device__ static inline void icp_iter_frame(const IcpArgs &a, int ns, Point &&point) {
+    IcpState *st = a.state;
+    if (st->done) return;
+    int nb = (ns + BS - 1) / BS;
+    if (nb < 1) nb = 1;
+    if ((int)blockIdx.x >= nb) return;
+    const unsigned long long t_entry = wall_clock64();
+    const int launches = st->launches;
+    double T[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) T[k] = st->T[k];
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) acc[k] = 0.0;
+    const int i = blockIdx.x * BS + threadIdx.x;
+    point(i, i < ns, T, acc);
+    icp_finish<MODE, BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);
+}
+
 __device__ static inline void icp_row6(double w, const double *J, double r, double *acc) {
     int t = 0;
 #pragma unroll
@@ -384,3 +413,66 @@ struct IcpPump {
         return PCR_OK;
     }
 };
+
+// ---- the host side of a map loop: RegistrationICP's loop with ONE kernel per iteration (an icp_iter_frame kernel of LIN_BS lanes) and nothing to
+// prepare -- no imported source, no tree, no certificates -- pumped in chunks that replay as cached graphs.  The caller checks what is its own,
+// zeroes both argument blocks with memset and fills them (loss, criteria and max_it in `a`; the rest is set here); launch(nb) enqueues one
+// iteration of nb workgroups on the context's stream.  Every launch of a chunk is the same launch: one graph per chunk length, under the key
+// (bytes of a, bytes of the second block, {nb, chunk length, tag}) -- `tag` names the KERNEL, so two kernel forms never share a cached graph.
+// single: linearise once at T0 and stop, no graph; *sums then receives the NV sums (out is not written).
+template <class Launch>
+static int icp_map_loop(pcr_context *ctx, const char *call, IcpArgs &a, const void *block, size_t block_bytes, int ns, int tag, Launch &&launch, const double *T0, bool single,
+                        pcr_result *out, double *sums) {
+    const std::string who(call);
+    ArenaMark mark(ctx);
+    int chunk = 8; bool graph = true;
+    pcr_icp_loop_switches(&chunk, &graph);
+    const int nb = ns > 0 ? (ns + LIN_BS - 1) / LIN_BS : 1;
+    IcpState *st = arena<IcpState>(ctx, 1);
+    double *partials = arena<double>(ctx, (size_t)nb * NVP);
+    if (!st || !partials) return PCR_ENOMEM;
+    a.state = st; a.partials = partials; a.src_cap = ns > 0 ? ns : 1; a.grid.L = -1; a.single = single ? 1 : 0;
+    IcpInit in; memcpy(in.T, T0, sizeof in.T);
+    PCR_LAUNCH(ctx, k_icp_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
+    auto enqueue = [&](int) { launch(nb); };
+    IcpState fin;
+    if (single) {
+        enqueue(0);
+        PCR_HIP_CHECK(ctx, hipMemcpyAsync(&fin, st, sizeof fin, hipMemcpyDeviceToHost, ctx->stream));
+        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (!fin.done) { ctx->err = who + ": the launch left no sums"; return PCR_EHIP; }
+        if (sums) memcpy(sums, fin.sums, sizeof(double) * NV);
+        return PCR_OK;
+    }
+    auto issue = [&](int k, int c, bool ragged) -> int {
+        hipGraphExec_t ge = nullptr;
+        if (graph && !ragged) {
+            std::string key((const char *)&a, sizeof a);
+            key.append((const char *)block, block_bytes);
+            const int extra[3] = {nb, c, tag};
+            key.append((const char *)extra, sizeof extra);
+            IcpGraph *hit = icp_graph_find(ctx, key);
+            if (!hit) {
+                PCR_TRY(icp_graph_capture(ctx, key, c, 0, enqueue, &hit));
+                (void)hipGraphDestroy(hit->graph); hit->graph = nullptr;      // no node of it is patched later: the instantiated graph is all that is kept
+            }
+            ge = hit->exec;
+        }
+        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
+        else for (int i = 0; i < c; i++) enqueue(k + i);
+        return PCR_OK;
+    };
+    auto judge = [&](const IcpState *s, int, int *next) -> int {
+        if (s->done) { fin = *s; *next = 0; }
+        else *next = chunk;
+        return PCR_OK;
+    };
+    IcpPump pump;
+    PCR_TRY(pump.init(ctx, st, 1));
+    PCR_TRY(pump.run(chunk, a.max_it + 1, issue, judge));
+    if (!pump.done) { ctx->err = who + ": the loop ended without a final state"; return PCR_EHIP; }
+    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // the launches after 'done' return at once; the arena and the pinned slots are free again
+    state_to_result(fin, out);
+    for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = who + ": non-finite pose"; return PCR_ENUMERIC; }
+    return PCR_OK;
+}

@@ -88,77 +88,20 @@ struct IcpNdtArgs {
     int ns, nbh;
 };
 __global__ void __launch_bounds__(LIN_BS) k_icp_iter_ndt(IcpArgs a, IcpNdtArgs v) {
-    IcpState *st = a.state;
-    if (st->done) return;
-    const int ns = v.ns;
-    int nb = (ns + LIN_BS - 1) / LIN_BS;
-    if (nb < 1) nb = 1;
-    if ((int)blockIdx.x >= nb) return;
-    const unsigned long long t_entry = wall_clock64();
-    const int launches = st->launches;
-    double T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = st->T[k];
-    double acc[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) acc[k] = 0.0;
-    const int i = blockIdx.x * LIN_BS + threadIdx.x;
-    if (i < ns) ndt_point<false>(v.map, v.nbh, v.sc, T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], acc);
-    icp_finish<ICP_MODE_NDT, LIN_BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);
+    icp_iter_frame<ICP_MODE_NDT, LIN_BS>(a, v.ns, [&](int i, bool live, const double *T, double *acc) {
+        if (live) ndt_point<false>(v.map, v.nbh, v.sc, T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], acc);
+    });
 }
-__global__ void k_ndt_init(IcpState *st, IcpInit in) { d_icp_init(st, in); }
 
-// RegistrationICP's loop with ONE kernel per iteration, pumped in chunks that replay as cached graphs: vgicp_loop (pcr_vgicp.hip) with this kernel
+// The map loop (icp_map_loop, pcr_icp_loop.h) with this unit's kernel and argument block.
 static int ndt_loop(pcr_context *ctx, const float *src_xyz, int64_t n_src, const NdtMapView *map, const NdtScore &sc, const double *T0, const pcr_ndt_params *p, pcr_result *out) {
-    ArenaMark mark(ctx);
-    int chunk = 8; bool graph = true;
-    pcr_icp_loop_switches(&chunk, &graph);
-    const int ns = (int)n_src;
-    const int nb = ns > 0 ? (ns + LIN_BS - 1) / LIN_BS : 1;
-    IcpState *st = arena<IcpState>(ctx, 1);
-    double *partials = arena<double>(ctx, (size_t)nb * NVP);
-    if (!st || !partials) return PCR_ENOMEM;
     IcpArgs a; memset(&a, 0, sizeof a);           // (the bytes of both argument blocks are the graph key)
-    a.state = st; a.partials = partials; a.src_cap = ns > 0 ? ns : 1; a.grid.L = -1;
     a.loss = PCR_LOSS_L2; a.loss_k = 1.0; a.a = 1.0;
     a.rel_fit = p->relative_fitness; a.rel_rmse = p->relative_rmse; a.max_it = p->max_iteration;
     IcpNdtArgs v; memset(&v, 0, sizeof v);
-    v.src_xyz = src_xyz; v.map = *map; v.sc = sc; v.ns = ns; v.nbh = p->neighborhood;
-    IcpInit in; memcpy(in.T, T0, sizeof in.T);
-    PCR_LAUNCH(ctx, k_ndt_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
-    auto enqueue = [&](int) { PCR_LAUNCH(ctx, k_icp_iter_ndt, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v); };
-    auto issue = [&](int k, int c, bool ragged) -> int {
-        hipGraphExec_t ge = nullptr;
-        if (graph && !ragged) {
-            std::string key((const char *)&a, sizeof a);
-            key.append((const char *)&v, sizeof v);
-            const int extra[3] = {nb, c, ICP_MODE_NDT};
-            key.append((const char *)extra, sizeof extra);
-            IcpGraph *hit = icp_graph_find(ctx, key);
-            if (!hit) {
-                PCR_TRY(icp_graph_capture(ctx, key, c, 0, enqueue, &hit));
-                (void)hipGraphDestroy(hit->graph); hit->graph = nullptr;      // no node of it is patched later: the instantiated graph is all that is kept
-            }
-            ge = hit->exec;
-        }
-        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-        else for (int i = 0; i < c; i++) enqueue(k + i);
-        return PCR_OK;
-    };
-    IcpState fin;
-    auto judge = [&](const IcpState *s, int, int *next) -> int {
-        if (s->done) { fin = *s; *next = 0; }
-        else *next = chunk;
-        return PCR_OK;
-    };
-    IcpPump pump;
-    PCR_TRY(pump.init(ctx, st, 1));
-    PCR_TRY(pump.run(chunk, a.max_it + 1, issue, judge));
-    if (!pump.done) { ctx->err = "registration_ndt: the loop ended without a final state"; return PCR_EHIP; }
-    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // the launches after 'done' return at once; the arena and the pinned slots are free again
-    state_to_result(fin, out);
-    for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = "registration_ndt: non-finite pose"; return PCR_ENUMERIC; }
-    return PCR_OK;
+    v.src_xyz = src_xyz; v.map = *map; v.sc = sc; v.ns = (int)n_src; v.nbh = p->neighborhood;
+    auto launch = [&](int nb) { PCR_LAUNCH(ctx, k_icp_iter_ndt, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v); };
+    return icp_map_loop(ctx, "registration_ndt", a, &v, sizeof v, v.ns, ICP_MODE_NDT, launch, T0, false, out, nullptr);
 }
 
 // ================================================================ the linearisation at one pose
@@ -278,7 +221,7 @@ __global__ void __launch_bounds__(NDT_BS) k_ndt_read(const uint64_t *__restrict_
     if (info6) for (int t = 0; t < 6; t++) info6[(size_t)v * 6 + t] = m.info6[(size_t)v * 6 + t];
 }
 
-// ---- rows at a pose: slot[i * nbh + k] = map row of candidate k of source point i, or -1; flags for the scan
+// ---- rows at a pose: slot[i * nbh + k] = map row of candidate k of source point i, or -1; flags for the scan (the tail: vg_emit_rows, pcr_vgicp.hip)
 __global__ void __launch_bounds__(NDT_BS) k_ndt_rows(const float *__restrict__ src_xyz, int ns, NdtPose pose, NdtMapView m, int nbh, int32_t *__restrict__ slot,
                                                      uint8_t *__restrict__ flags) {
     const int i = blockIdx.x * NDT_BS + threadIdx.x;
@@ -297,29 +240,10 @@ __global__ void __launch_bounds__(NDT_BS) k_ndt_rows(const float *__restrict__ s
         flags[(size_t)i * nbh + k] = row >= 0 ? 1 : 0;
     }
 }
-__global__ void __launch_bounds__(NDT_BS) k_ndt_emit(const int32_t *__restrict__ slot, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int total, int nbh,
-                                                     int32_t *__restrict__ rows2) {
-    const int e = blockIdx.x * NDT_BS + threadIdx.x;
-    if (e >= total || !flags[e]) return;
-    const int o = pos[e];
-    rows2[2 * (size_t)o] = e / nbh; rows2[2 * (size_t)o + 1] = slot[e];
-}
 
 static unsigned ndt_blocks(size_t n) { return (unsigned)((n + NDT_BS - 1) / NDT_BS); }
 
-int ndt_check_map(pcr_context *ctx, const pcr_ndt_map *map, const char *call) {
-    if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
-    if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
-    return PCR_OK;
-}
-static int ndt_check_nbh(pcr_context *ctx, const char *call, int neighborhood) {
-    if (neighborhood != 1 && neighborhood != 7 && neighborhood != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
-    return PCR_OK;
-}
-static int ndt_check_src(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, int nbh) {
-    if (n_src < 0 || (n_src > 0 && !src_xyz) || (double)n_src * nbh > (double)(0x7fffffff / 4)) { ctx->err = std::string(call) + ": src_xyz is null or too large"; return PCR_EINVAL; }
-    return PCR_OK;
-}
+int ndt_check_map(pcr_context *ctx, const pcr_ndt_map *map, const char *call) { return vg_check_handle(ctx, map, call); }      // (pcr_nmap.hip calls it too)
 // SCORE CONSTANTS of the rule, in float64 on the host
 static int ndt_score(pcr_context *ctx, const char *call, double outlier_ratio, double voxel, NdtScore *sc) {
     if (!(outlier_ratio > 0.0) || !(outlier_ratio < 1.0)) { ctx->err = std::string(call) + ": outlier_ratio must lie in (0, 1)"; return PCR_EINVAL; }
@@ -450,13 +374,10 @@ static int ndt_rows(pcr_context *ctx, const pcr_ndt_map *map, const float *src_x
     const size_t total = (size_t)n_src * nbh;
     int32_t *slot = arena<int32_t>(ctx, total);
     uint8_t *flags = arena<uint8_t>(ctx, total);
-    int *pos = arena<int>(ctx, total), *count = arena<int>(ctx, 1);
-    if (!slot || !flags || !pos || !count) return PCR_ENOMEM;
+    if (!slot || !flags) return PCR_ENOMEM;
     NdtPose pose; memcpy(pose.T, T, sizeof pose.T);
     PCR_LAUNCH(ctx, k_ndt_rows, dim3(ndt_blocks((size_t)n_src)), dim3(NDT_BS), 0, ctx->stream, src_xyz, (int)n_src, pose, map->view, nbh, slot, flags);
-    PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)total, pos, count));
-    PCR_LAUNCH(ctx, k_ndt_emit, dim3(ndt_blocks(total)), dim3(NDT_BS), 0, ctx->stream, (const int32_t *)slot, (const uint8_t *)flags, (const int *)pos, (int)total, nbh, rows2);
-    return pcr_read_count(ctx, count, n_rows);
+    return vg_emit_rows(ctx, slot, flags, total, nbh, rows2, n_rows);
 }
 static size_t ndt_rows_scratch(int64_t n_src, int nbh) { return (size_t)(n_src > 0 ? n_src : 1) * nbh * 10 + (1u << 20); }
 
@@ -465,8 +386,8 @@ extern "C" int pcr_ndt_map_correspondences(pcr_context *ctx, const pcr_ndt_map *
     return pcr_api_call(ctx, [&]() -> int {
     const char *call = "ndt_map_correspondences";
     PCR_TRY(ndt_check_map(ctx, map, call));
-    PCR_TRY(ndt_check_nbh(ctx, call, neighborhood));
-    PCR_TRY(ndt_check_src(ctx, call, src_xyz, n_src, neighborhood));
+    PCR_TRY(vg_check_nbh(ctx, call, neighborhood));
+    PCR_TRY(vg_check_src(ctx, call, src_xyz, n_src, neighborhood));
     if (!n_rows || (n_src > 0 && !rows2)) { ctx->err = "ndt_map_correspondences: rows2 / n_rows is null"; return PCR_EINVAL; }
     PCR_TRY(vg_check_T(ctx, call, "T", T));
     PCR_TRY(pcr_arena_reserve(ctx, ndt_rows_scratch(n_src, neighborhood)));
@@ -481,8 +402,8 @@ extern "C" int pcr_ndt_linearize(pcr_context *ctx, const pcr_ndt_map *map, const
     return pcr_api_call(ctx, [&]() -> int {
     const char *call = "ndt_linearize";
     PCR_TRY(ndt_check_map(ctx, map, call));
-    PCR_TRY(ndt_check_nbh(ctx, call, neighborhood));
-    PCR_TRY(ndt_check_src(ctx, call, src_xyz, n_src, neighborhood));
+    PCR_TRY(vg_check_nbh(ctx, call, neighborhood));
+    PCR_TRY(vg_check_src(ctx, call, src_xyz, n_src, neighborhood));
     PCR_TRY(vg_check_T(ctx, call, "T", T));
     NdtScore sc;
     PCR_TRY(ndt_score(ctx, call, outlier_ratio, map->view.voxel, &sc));
@@ -520,8 +441,8 @@ extern "C" int pcr_registration_ndt(pcr_context *ctx, const float *src_xyz, int6
     const char *call = "registration_ndt";
     if (!params || !result) { ctx->err = "registration_ndt: params / result is null"; return PCR_EINVAL; }
     PCR_TRY(ndt_check_map(ctx, map, call));
-    PCR_TRY(ndt_check_nbh(ctx, call, params->neighborhood));
-    PCR_TRY(ndt_check_src(ctx, call, src_xyz, n_src, params->neighborhood));
+    PCR_TRY(vg_check_nbh(ctx, call, params->neighborhood));
+    PCR_TRY(vg_check_src(ctx, call, src_xyz, n_src, params->neighborhood));
     if (params->max_iteration < 0) { ctx->err = "registration_ndt: params.max_iteration < 0"; return PCR_EINVAL; }
     NdtScore sc;
     PCR_TRY(ndt_score(ctx, call, params->outlier_ratio, map->view.voxel, &sc));

@@ -2,6 +2,7 @@
 // block builder of the maps that grow (map_build_block / map_adopt, pcr_mapgrow.h).  The rule is the statement in include/pcr_hip.h (voxel point map).
 // This map has many rows per cell, so of the frame it takes the builder and the adoption only; merge and remove_far are its own (pcr_pmap.hip).
 #pragma once
+#include "pcr_icp_loop.h"
 #include "pcr_mapgrow.h"
 
 // Rows are the kept points, ordered by (Morton key of the cell, arrival): xyz[3 r .. 3 r + 2] and, in a map with normals, nrm[3 r .. 3 r + 2], packed
@@ -108,6 +109,29 @@ __device__ static inline double pm_weight(int loss, double k, double r) {
     if (loss == PCR_LOSS_L1) return 1.0 / fmax(fabs(r), 1e-300);
     if (loss == PCR_LOSS_GM) { const double rr = r * r; const double d = k + rr; return k / (d * d); }
     return 1.0;
+}
+
+// The rows of one correspondence -- the point q at its pose against map row `row` -- into the 27 sums of A: [0, 21) upper w J^T J, [21, 27) w J^T r;
+// returns the squared residual (point to plane: r^2; point to point: |e|^2).  (lx, ly, lz) is the lever of the rotation columns: q itself for the
+// rigid pose of pcr_pmap.hip, u = R p (q without its translation) for the pose pair of pcr_ctime.hip.  Called from units that contract nothing.
+__device__ static inline double pm_row27(const PmapView &m, int plane, int loss, double loss_k, int row, double qx, double qy, double qz, double lx, double ly, double lz, double *A) {
+    const float *p = m.xyz + (size_t)row * 3;
+    const double ex = qx - (double)p[0], ey = qy - (double)p[1], ez = qz - (double)p[2];
+    if (plane) {
+        const float *nf = m.nrm + (size_t)row * 3;
+        const double nx = nf[0], ny = nf[1], nz = nf[2];
+        double r = ex * nx + ey * ny;
+        r = r + ez * nz;
+        const double J[6] = {ly * nz - lz * ny, lz * nx - lx * nz, lx * ny - ly * nx, nx, ny, nz};
+        icp_row6(pm_weight(loss, loss_k, r), J, r, A);
+        return r * r;
+    }
+    double nn = ex * ex + ey * ey;
+    nn = nn + ez * ez;
+    const double w = pm_weight(loss, loss_k, sqrt(nn));
+    const double J0[6] = {0.0, lz, -ly, 1.0, 0.0, 0.0}, J1[6] = {-lz, 0.0, lx, 0.0, 1.0, 0.0}, J2[6] = {ly, -lx, 0.0, 0.0, 0.0, 1.0};
+    icp_row6(w, J0, ex, A); icp_row6(w, J1, ey, A); icp_row6(w, J2, ez, A);
+    return nn;
 }
 
 // what the calls that search the map check alike, and their scratch (pcr_pmap.hip): the map, the neighbourhood, the source, the distance and one pose

@@ -41,56 +41,22 @@ struct IcpPmapArgs {
     const int32_t *ncount;     // k_icp_iter_pmap<true> alone (point to plane on an estimated map): a match whose row has ncount < kmin is no row
     int kmin;
 };
-// the rows of one correspondence into the 30 sums: [0, 21) upper JTJ, [21, 27) JTr, [27] sum r^2, [28] sum d^2, [29] rows
-__device__ static inline void pm_rows(const IcpArgs &a, const IcpPmapArgs &v, double sx, double sy, double sz, int row, double d2, double *acc) {
-    const float *p = v.map.xyz + (size_t)row * 3;
-    const double ex = sx - (double)p[0], ey = sy - (double)p[1], ez = sz - (double)p[2];
-    acc[28] += d2; acc[29] += 1.0;
-    if (v.plane) {
-        const float *nf = v.map.nrm + (size_t)row * 3;
-        const double nx = nf[0], ny = nf[1], nz = nf[2];
-        double r = ex * nx + ey * ny;
-        r = r + ez * nz;
-        const double J[6] = {sy * nz - sz * ny, sz * nx - sx * nz, sx * ny - sy * nx, nx, ny, nz};
-        acc[27] += r * r;
-        icp_row6(pm_weight(a.loss, a.loss_k, r), J, r, acc);
-    } else {
-        double nn = ex * ex + ey * ey;
-        nn = nn + ez * ez;
-        const double w = pm_weight(a.loss, a.loss_k, sqrt(nn));
-        acc[27] += nn;
-        const double J0[6] = {0.0, sz, -sy, 1.0, 0.0, 0.0}, J1[6] = {-sz, 0.0, sx, 0.0, 1.0, 0.0}, J2[6] = {sy, -sx, 0.0, 0.0, 0.0, 1.0};
-        icp_row6(w, J0, ex, acc); icp_row6(w, J1, ey, acc); icp_row6(w, J2, ez, acc);
-    }
-}
 // EST: the map's normals are its own (ESTIMATE) and the estimator reads them; instantiated for that case alone
 template <bool EST>
 __global__ void __launch_bounds__(LIN_BS) k_icp_iter_pmap(IcpArgs a, IcpPmapArgs v) {
-    IcpState *st = a.state;
-    if (st->done) return;
-    const int ns = v.ns;
-    int nb = (ns + LIN_BS - 1) / LIN_BS;
-    if (nb < 1) nb = 1;
-    if ((int)blockIdx.x >= nb) return;
-    const unsigned long long t_entry = wall_clock64();
-    const int launches = st->launches;
-    double T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = st->T[k];
-    double acc[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) acc[k] = 0.0;
-    const int i = blockIdx.x * LIN_BS + threadIdx.x;
-    const bool live = i < ns;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    if (live) vg_transform(T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], qx, qy, qz);
-    double d2; int row;
-    pm_match_own(v.map, v.nbh, live, qx, qy, qz, v.max_d2, d2, row);
-    if (EST && row >= 0 && v.ncount[row] < v.kmin) row = -1;
-    if (live && row >= 0) pm_rows(a, v, qx, qy, qz, row, d2, acc);
-    icp_finish<ICP_MODE_P2PL, LIN_BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);      // (to icp_finish this is point to plane: the 6x6 LDLT update, fitness = rows / ns)
+    // (to icp_finish this is point to plane: the 6x6 LDLT update, fitness = rows / ns)
+    icp_iter_frame<ICP_MODE_P2PL, LIN_BS>(a, v.ns, [&](int i, bool live, const double *T, double *acc) {
+        double qx = 0.0, qy = 0.0, qz = 0.0;
+        if (live) vg_transform(T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], qx, qy, qz);
+        double d2; int row;
+        pm_match_own(v.map, v.nbh, live, qx, qy, qz, v.max_d2, d2, row);
+        if (EST && row >= 0 && v.ncount[row] < v.kmin) row = -1;
+        if (live && row >= 0) {      // the rows (pm_row27, the lever is q) into the 30 sums: [27] sum r^2, [28] sum d^2, [29] rows
+            acc[28] += d2; acc[29] += 1.0;
+            acc[27] += pm_row27(v.map, v.plane, a.loss, a.loss_k, row, qx, qy, qz, qx, qy, qz, acc);
+        }
+    });
 }
-__global__ void k_pmap_init(IcpState *st, IcpInit in) { d_icp_init(st, in); }
 
 // match[i] = the row of source point i at the pose, or -1; flags for the scan
 __global__ void __launch_bounds__(PM_BS) k_pmap_match(const float *__restrict__ src_xyz, int ns, PmPose pose, PmapView m, int nbh, double max_d2, int32_t *__restrict__ match,
@@ -109,80 +75,23 @@ __global__ void __launch_bounds__(PM_BS) k_pmap_drop_invalid(const int32_t *__re
     if (i >= ns || !flags[i]) return;
     if (ncount[match[i]] < kmin) { match[i] = -1; flags[i] = 0; }
 }
-__global__ void __launch_bounds__(PM_BS) k_pmap_emit(const int32_t *__restrict__ match, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int ns,
-                                                     int32_t *__restrict__ rows2) {
-    const int i = blockIdx.x * PM_BS + threadIdx.x;
-    if (i >= ns || !flags[i]) return;
-    const int o = pos[i];
-    rows2[2 * (size_t)o] = i; rows2[2 * (size_t)o + 1] = match[i];
-}
 
-// The loop of voxelized GICP (vgicp_loop, pcr_vgicp.hip) with this unit's kernel: one launch per iteration, chunks replayed as cached graphs.
+// The map loop (icp_map_loop, pcr_icp_loop.h) with this unit's kernel forms and argument block.
 // single: linearise once at T0 and stop (pcr_point_map_linearize); *sums then receives the 30 sums.
 static int pmap_loop(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, const pcr_point_map *map, int neighborhood, double max_d2, const pcr_estimation *est,
                      const double *T0, double rel_fit, double rel_rmse, int max_it, bool single, pcr_result *out, double *sums) {
-    ArenaMark mark(ctx);
-    int chunk = 8; bool graph = true;
-    pcr_icp_loop_switches(&chunk, &graph);
-    const int ns = (int)n_src;
-    const int nb = ns > 0 ? (ns + LIN_BS - 1) / LIN_BS : 1;
-    IcpState *st = arena<IcpState>(ctx, 1);
-    double *partials = arena<double>(ctx, (size_t)nb * NVP);
-    if (!st || !partials) return PCR_ENOMEM;
     IcpArgs a; memset(&a, 0, sizeof a);           // (the bytes of both argument blocks are the graph key)
-    a.state = st; a.partials = partials; a.src_cap = ns > 0 ? ns : 1; a.grid.L = -1;
     a.loss = est->loss; a.loss_k = est->loss_k; a.a = 1.0;
-    a.rel_fit = rel_fit; a.rel_rmse = rel_rmse; a.max_it = max_it; a.single = single ? 1 : 0;
+    a.rel_fit = rel_fit; a.rel_rmse = rel_rmse; a.max_it = max_it;
     IcpPmapArgs v; memset(&v, 0, sizeof v);
-    v.src_xyz = src_xyz; v.map = map->view; v.ns = ns; v.nbh = neighborhood; v.plane = est->kind == PCR_EST_POINT_TO_PLANE ? 1 : 0; v.max_d2 = max_d2;
+    v.src_xyz = src_xyz; v.map = map->view; v.ns = (int)n_src; v.nbh = neighborhood; v.plane = est->kind == PCR_EST_POINT_TO_PLANE ? 1 : 0; v.max_d2 = max_d2;
     const bool validity = pm_reads_validity(map, est);      // (point to point never reads it: on an estimated map it runs the launch of a map without normals)
     if (validity) { v.ncount = map->ncount; v.kmin = map->est_min; }
-    IcpInit in; memcpy(in.T, T0, sizeof in.T);
-    PCR_LAUNCH(ctx, k_pmap_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
-    auto enqueue = [&](int) {
+    auto launch = [&](int nb) {
         if (validity) PCR_LAUNCH(ctx, k_icp_iter_pmap<true>, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v);
         else PCR_LAUNCH(ctx, k_icp_iter_pmap<false>, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v);
     };
-    IcpState fin;
-    if (single) {
-        enqueue(0);
-        PCR_HIP_CHECK(ctx, hipMemcpyAsync(&fin, st, sizeof fin, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (!fin.done) { ctx->err = std::string(call) + ": the launch left no sums"; return PCR_EHIP; }
-        if (sums) memcpy(sums, fin.sums, sizeof(double) * NV);
-        return PCR_OK;
-    }
-    auto issue = [&](int k, int c, bool ragged) -> int {
-        hipGraphExec_t ge = nullptr;
-        if (graph && !ragged) {
-            std::string key((const char *)&a, sizeof a);
-            key.append((const char *)&v, sizeof v);
-            const int extra[3] = {nb, c, validity ? 10 : 9 /* this loop, by its kernel (the ICP_MODE_* numbers end at 8) */};
-            key.append((const char *)extra, sizeof extra);
-            IcpGraph *hit = icp_graph_find(ctx, key);
-            if (!hit) {
-                PCR_TRY(icp_graph_capture(ctx, key, c, 0, enqueue, &hit));
-                (void)hipGraphDestroy(hit->graph); hit->graph = nullptr;      // no node of it is patched later: the instantiated graph is all that is kept
-            }
-            ge = hit->exec;
-        }
-        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-        else for (int i = 0; i < c; i++) enqueue(k + i);
-        return PCR_OK;
-    };
-    auto judge = [&](const IcpState *s, int, int *next) -> int {
-        if (s->done) { fin = *s; *next = 0; }
-        else *next = chunk;
-        return PCR_OK;
-    };
-    IcpPump pump;
-    PCR_TRY(pump.init(ctx, st, 1));
-    PCR_TRY(pump.run(chunk, a.max_it + 1, issue, judge));
-    if (!pump.done) { ctx->err = std::string(call) + ": the loop ended without a final state"; return PCR_EHIP; }
-    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // the launches after 'done' return at once; the arena and the pinned slots are free again
-    state_to_result(fin, out);
-    for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = std::string(call) + ": non-finite pose"; return PCR_ENUMERIC; }
-    return PCR_OK;
+    return icp_map_loop(ctx, call, a, &v, sizeof v, v.ns, validity ? 10 : 9 /* the tag of the kernel form (the ICP_MODE_* numbers end at 8) */, launch, T0, single, out, sums);
 }
 
 // ================================================================ the map: kernels
@@ -402,11 +311,7 @@ struct PmSeq { const uint64_t *keys; const uint32_t *src; int n; };
 // scratch of the context's arena for sequences of `entries` entries in all (the placed members, the sort, the passes of pm_build)
 static size_t pm_scratch(int64_t entries) { return 2 * pcr_scratch_bytes_for(entries) + pcr_sort_temp_bytes((size_t)(entries > 0 ? entries : 1)) + (size_t)entries * 192 + (4u << 20); }
 
-static int pm_check_map(pcr_context *ctx, const pcr_point_map *map, const char *call) {
-    if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
-    if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
-    return PCR_OK;
-}
+static int pm_check_map(pcr_context *ctx, const pcr_point_map *map, const char *call) { return vg_check_handle(ctx, map, call); }
 static int pm_check_max_points(pcr_context *ctx, const char *call, int max_points) {
     if (max_points < 1 || max_points > PM_MAX_POINTS) { ctx->err = std::string(call) + ": max_points_per_voxel must lie in 1 .. 64"; return PCR_EINVAL; }
     return PCR_OK;
@@ -715,7 +620,7 @@ extern "C" int pcr_point_map_remove_far(pcr_context *ctx, pcr_point_map *map, co
 int pm_check_search(pcr_context *ctx, const char *call, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, const char *T_name, int nbh,
                            double max_distance) {
     PCR_TRY(pm_check_map(ctx, map, call));
-    if (nbh != 1 && nbh != 7 && nbh != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
+    PCR_TRY(vg_check_nbh(ctx, call, nbh));
     if (n_src < 0 || (n_src > 0 && !src_xyz) || n_src > 0x7fffffff / 8) { ctx->err = std::string(call) + ": src_xyz is null or too large"; return PCR_EINVAL; }
     if (!std::isfinite(max_distance) || !(max_distance > 0.0)) { ctx->err = std::string(call) + ": max_correspondence_distance must be finite and greater than 0"; return PCR_EINVAL; }
     return vg_check_T(ctx, call, T_name, T);
@@ -744,14 +649,11 @@ static int pm_rows_at(pcr_context *ctx, const pcr_point_map *map, const float *s
     ArenaMark mark(ctx);
     int32_t *match = arena<int32_t>(ctx, (size_t)n_src);
     uint8_t *flags = arena<uint8_t>(ctx, (size_t)n_src);
-    int *pos = arena<int>(ctx, (size_t)n_src), *count = arena<int>(ctx, 1);
-    if (!match || !flags || !pos || !count) return PCR_ENOMEM;
+    if (!match || !flags) return PCR_ENOMEM;
     PmPose pose; memcpy(pose.T, T, sizeof pose.T);
     PCR_LAUNCH(ctx, k_pmap_match, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, src_xyz, (int)n_src, pose, map->view, nbh, max_d2, match, flags);
     if (valid_only) PCR_LAUNCH(ctx, k_pmap_drop_invalid, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, (const int32_t *)map->ncount, map->est_min, (int)n_src, match, flags);
-    PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)n_src, pos, count));
-    PCR_LAUNCH(ctx, k_pmap_emit, dim3(pm_blocks((size_t)n_src)), dim3(PM_BS), 0, ctx->stream, (const int32_t *)match, (const uint8_t *)flags, (const int *)pos, (int)n_src, rows2);
-    return pcr_read_count(ctx, count, n_rows);
+    return vg_emit_rows(ctx, match, flags, (size_t)n_src, 1, rows2, n_rows);      // (one candidate per source point)
 }
 
 extern "C" int pcr_point_map_correspondences(pcr_context *ctx, const pcr_point_map *map, const float *src_xyz, int64_t n_src, const double *T, double max_correspondence_distance,

@@ -52,9 +52,18 @@ struct VmapRow {
 
 // host helpers of pcr_vgicp.hip that the units of the maps that grow call too: PCR_EINVAL naming the first of up to three arrays that holds a
 // non-finite value (one read-back); the map / pose / grid_min3 argument checks; the member covariances of n points as packed cov6 (enqueues only);
-// whether both ends of the members (bounds6: minimum, maximum) lie inside the 2^21 cells per axis of the grid of grid_min3
+// whether both ends of the members (bounds6: minimum, maximum) lie inside the 2^21 cells per axis of the grid of grid_min3; and what every unit
+// that searches a map shares: the neighbourhood and source checks, and the tail of a correspondence set (flag scan, emit, count read-back)
 int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr, const size_t *count, const char *const *name, int arrays);
 int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call);
+template <class Map> static int vg_check_handle(pcr_context *ctx, const Map *map, const char *call) {      // (what vg_check_map asks, of any map's handle)
+    if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
+    if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
+    return PCR_OK;
+}
+int vg_check_nbh(pcr_context *ctx, const char *call, int neighborhood);
+int vg_check_src(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, int nbh);
+int vg_emit_rows(pcr_context *ctx, const int32_t *slot, const uint8_t *flags, size_t total, int nbh, int32_t *rows2, int64_t *n_rows);
 int vg_check_T(pcr_context *ctx, const char *call, const char *name, const double *T);
 int vg_check_grid_min(pcr_context *ctx, const char *call, const double *grid_min3);
 int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, double eps, int64_t n, float *out6);

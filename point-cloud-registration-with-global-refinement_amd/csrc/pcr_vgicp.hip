@@ -100,22 +100,8 @@ __device__ static inline void icp_row_vgicp(const IcpArgs &a, const double *Cs /
     }
 }
 __global__ void __launch_bounds__(LIN_BS) k_icp_iter_vgicp(IcpArgs a, IcpVoxelArgs v) {
-    IcpState *st = a.state;
-    if (st->done) return;
-    const int ns = v.ns;
-    int nb = (ns + LIN_BS - 1) / LIN_BS;
-    if (nb < 1) nb = 1;
-    if ((int)blockIdx.x >= nb) return;
-    const unsigned long long t_entry = wall_clock64();
-    const int launches = st->launches;
-    double T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = st->T[k];
-    double acc[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) acc[k] = 0.0;
-    const int i = blockIdx.x * LIN_BS + threadIdx.x;
-    if (i < ns) {
+    icp_iter_frame<ICP_MODE_VGICP, LIN_BS>(a, v.ns, [&](int i, bool live, const double *T, double *acc) {
+        if (!live) return;
         double qx, qy, qz;
         vg_transform(T, v.src_xyz[(size_t)i * 3], v.src_xyz[(size_t)i * 3 + 1], v.src_xyz[(size_t)i * 3 + 2], qx, qy, qz);
         const int cx = vg_cell(qx, v.map.org[0], v.map.voxel), cy = vg_cell(qy, v.map.org[1], v.map.voxel), cz = vg_cell(qz, v.map.org[2], v.map.voxel);
@@ -139,65 +125,20 @@ __global__ void __launch_bounds__(LIN_BS) k_icp_iter_vgicp(IcpArgs a, IcpVoxelAr
             any = true;
         }
         if (any) acc[27] += 1.0;
-    }
-    icp_finish<ICP_MODE_VGICP, LIN_BS>(a, st, T, acc, nb, ns, launches, t_entry, (int)blockIdx.x);
+    });
 }
-__global__ void k_vgicp_init(IcpState *st, IcpInit in) { d_icp_init(st, in); }
 
-// RegistrationICP's loop with ONE kernel per iteration and nothing to prepare -- no imported source, no tree, no certificates -- pumped in chunks
-// that replay as cached graphs like icp_loop's (pcr_gicp.hip).  Every launch of a chunk is the same launch: one graph per chunk length.
+// The map loop (icp_map_loop, pcr_icp_loop.h) with this unit's kernel and argument block.
 static int vgicp_loop(pcr_context *ctx, const float *src_xyz, const float *src_cov6, int64_t n_src, const VgicpMapView *map, int neighborhood, int min_points,
                       const double *T0, const pcr_gicp_params *p, pcr_result *out) {
     if (p->loss < PCR_LOSS_L2 || p->loss > PCR_LOSS_GM) { ctx->err = "registration_voxelized_gicp: params.loss is no robust kernel (pcr_loss_kind)"; return PCR_EINVAL; }
-    ArenaMark mark(ctx);
-    int chunk = 8; bool graph = true;
-    pcr_icp_loop_switches(&chunk, &graph);
-    const int ns = (int)n_src;
-    const int nb = ns > 0 ? (ns + LIN_BS - 1) / LIN_BS : 1;
-    IcpState *st = arena<IcpState>(ctx, 1);
-    double *partials = arena<double>(ctx, (size_t)nb * NVP);
-    if (!st || !partials) return PCR_ENOMEM;
     IcpArgs a; memset(&a, 0, sizeof a);           // (the bytes of both argument blocks are the graph key)
-    a.state = st; a.partials = partials; a.src_cap = ns > 0 ? ns : 1; a.grid.L = -1;
     a.loss = p->loss; a.loss_k = p->loss_k; a.a = 1.0 - p->epsilon;
     a.rel_fit = p->relative_fitness; a.rel_rmse = p->relative_rmse; a.max_it = p->max_iteration;
     IcpVoxelArgs v; memset(&v, 0, sizeof v);
-    v.src_xyz = src_xyz; v.src_cov6 = src_cov6; v.map = *map; v.ns = ns; v.nbh = neighborhood; v.min_points = min_points;
-    IcpInit in; memcpy(in.T, T0, sizeof in.T);
-    PCR_LAUNCH(ctx, k_vgicp_init, dim3(1), dim3(64), 0, ctx->stream, st, in);
-    auto enqueue = [&](int) { PCR_LAUNCH(ctx, k_icp_iter_vgicp, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v); };
-    auto issue = [&](int k, int c, bool ragged) -> int {
-        hipGraphExec_t ge = nullptr;
-        if (graph && !ragged) {
-            std::string key((const char *)&a, sizeof a);
-            key.append((const char *)&v, sizeof v);
-            const int extra[3] = {nb, c, ICP_MODE_VGICP};
-            key.append((const char *)extra, sizeof extra);
-            IcpGraph *hit = icp_graph_find(ctx, key);
-            if (!hit) {
-                PCR_TRY(icp_graph_capture(ctx, key, c, 0, enqueue, &hit));
-                (void)hipGraphDestroy(hit->graph); hit->graph = nullptr;      // no node of it is patched later: the instantiated graph is all that is kept
-            }
-            ge = hit->exec;
-        }
-        if (ge) PCR_HIP_CHECK(ctx, hipGraphLaunch(ge, ctx->stream));
-        else for (int i = 0; i < c; i++) enqueue(k + i);
-        return PCR_OK;
-    };
-    IcpState fin;
-    auto judge = [&](const IcpState *s, int, int *next) -> int {
-        if (s->done) { fin = *s; *next = 0; }
-        else *next = chunk;
-        return PCR_OK;
-    };
-    IcpPump pump;
-    PCR_TRY(pump.init(ctx, st, 1));
-    PCR_TRY(pump.run(chunk, a.max_it + 1, issue, judge));
-    if (!pump.done) { ctx->err = "registration_voxelized_gicp: the loop ended without a final state"; return PCR_EHIP; }
-    PCR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // the launches after 'done' return at once; the arena and the pinned slots are free again
-    state_to_result(fin, out);
-    for (int k = 0; k < 16; k++) if (!std::isfinite(fin.T[k])) { ctx->err = "registration_voxelized_gicp: non-finite pose"; return PCR_ENUMERIC; }
-    return PCR_OK;
+    v.src_xyz = src_xyz; v.src_cov6 = src_cov6; v.map = *map; v.ns = (int)n_src; v.nbh = neighborhood; v.min_points = min_points;
+    auto launch = [&](int nb) { PCR_LAUNCH(ctx, k_icp_iter_vgicp, dim3(nb), dim3(LIN_BS), 0, ctx->stream, a, v); };
+    return icp_map_loop(ctx, "registration_voxelized_gicp", a, &v, sizeof v, v.ns, ICP_MODE_VGICP, launch, T0, false, out, nullptr);
 }
 
 // ================================================================ the map
@@ -305,6 +246,7 @@ __global__ void __launch_bounds__(VG_BS) k_vmap_rows(const float *__restrict__ s
         flags[(size_t)i * nbh + k] = row >= 0 ? 1 : 0;
     }
 }
+// the emit kernel of every correspondence set (vg_emit_rows): candidate e belongs to source point e / nbh
 __global__ void __launch_bounds__(VG_BS) k_vmap_emit(const int32_t *__restrict__ slot, const uint8_t *__restrict__ flags, const int *__restrict__ pos, int total, int nbh,
                                                      int32_t *__restrict__ rows2) {
     const int e = blockIdx.x * VG_BS + threadIdx.x;
@@ -332,11 +274,18 @@ int vg_check_finite(pcr_context *ctx, const char *call, const float *const *ptr,
     return PCR_OK;
 }
 
-int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call) {
-    if (!map || !map->block) { ctx->err = std::string(call) + ": map is null"; return PCR_EINVAL; }
-    if (map->device != ctx->device) { ctx->err = std::string(call) + ": map lives on another device than the context"; return PCR_EINVAL; }
-    return PCR_OK;
+// The tail of every correspondence set (this unit's, pcr_ndt.hip's and, with nbh = 1, pcr_pmap.hip's): slot[e] is the map row of candidate e --
+// nbh candidates per source point -- and flags[e] whether it is a row; the flag scan and k_vmap_emit compact the flagged candidates in order into
+// rows2 as (source point, map row), and *n_rows is read back.  Scratch from the arena the caller has reserved and marked.
+int vg_emit_rows(pcr_context *ctx, const int32_t *slot, const uint8_t *flags, size_t total, int nbh, int32_t *rows2, int64_t *n_rows) {
+    int *pos = arena<int>(ctx, total), *count = arena<int>(ctx, 1);
+    if (!pos || !count) return PCR_ENOMEM;
+    PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)total, pos, count));
+    PCR_LAUNCH(ctx, k_vmap_emit, dim3(vg_blocks(total)), dim3(VG_BS), 0, ctx->stream, slot, flags, (const int *)pos, (int)total, nbh, rows2);
+    return pcr_read_count(ctx, count, n_rows);
 }
+
+int vg_check_map(pcr_context *ctx, const pcr_voxel_map *map, const char *call) { return vg_check_handle(ctx, map, call); }
 // the member covariances of n points (k_vmap_member_cov) for the units that grow a map: packed cov6 into out6; enqueues only
 int vg_member_cov6(pcr_context *ctx, const float *cov6, const float *normals, double eps, int64_t n, float *out6) {
     PCR_LAUNCH(ctx, k_vmap_member_cov, dim3(vg_blocks((size_t)n)), dim3(VG_BS), 0, ctx->stream, cov6, normals, eps, (int)n, (float *)nullptr, (float *)nullptr, out6);
@@ -356,8 +305,12 @@ bool vg_inside_grid(const double *bounds6, const double *grid_min3, double voxel
     }
     return true;
 }
-static int vg_check_rule(pcr_context *ctx, const char *call, int neighborhood, int min_points) {
+int vg_check_nbh(pcr_context *ctx, const char *call, int neighborhood) {
     if (neighborhood != 1 && neighborhood != 7 && neighborhood != 27) { ctx->err = std::string(call) + ": neighborhood must be 1, 7 or 27"; return PCR_EINVAL; }
+    return PCR_OK;
+}
+static int vg_check_rule(pcr_context *ctx, const char *call, int neighborhood, int min_points) {
+    PCR_TRY(vg_check_nbh(ctx, call, neighborhood));
     if (min_points < 1) { ctx->err = std::string(call) + ": min_points_per_voxel < 1"; return PCR_EINVAL; }
     return PCR_OK;
 }
@@ -450,13 +403,10 @@ static int vg_rows(pcr_context *ctx, const pcr_voxel_map *map, const float *src_
     const size_t total = (size_t)n_src * nbh;
     int32_t *slot = arena<int32_t>(ctx, total);
     uint8_t *flags = arena<uint8_t>(ctx, total);
-    int *pos = arena<int>(ctx, total), *count = arena<int>(ctx, 1);
-    if (!slot || !flags || !pos || !count) return PCR_ENOMEM;
+    if (!slot || !flags) return PCR_ENOMEM;
     VgPose pose; memcpy(pose.T, T, sizeof pose.T);
     PCR_LAUNCH(ctx, k_vmap_rows, dim3(vg_blocks((size_t)n_src)), dim3(VG_BS), 0, ctx->stream, src_xyz, (int)n_src, pose, map->view, nbh, min_points, slot, flags);
-    PCR_TRY(pcr_dev_flag_scan(ctx, flags, nullptr, (int)total, pos, count));
-    PCR_LAUNCH(ctx, k_vmap_emit, dim3(vg_blocks(total)), dim3(VG_BS), 0, ctx->stream, (const int32_t *)slot, (const uint8_t *)flags, (const int *)pos, (int)total, nbh, rows2);
-    return pcr_read_count(ctx, count, n_rows);
+    return vg_emit_rows(ctx, slot, flags, total, nbh, rows2, n_rows);
 }
 static size_t vg_rows_scratch(int64_t n_src, int nbh) { return (size_t)(n_src > 0 ? n_src : 1) * nbh * 10 + (1u << 20); }
 
@@ -465,7 +415,7 @@ int vg_check_T(pcr_context *ctx, const char *call, const char *name, const doubl
     for (int k = 0; k < 16; k++) if (!std::isfinite(T[k])) { ctx->err = std::string(call) + ": " + name + " holds a non-finite value"; return PCR_EINVAL; }
     return PCR_OK;
 }
-static int vg_check_src(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, int nbh) {
+int vg_check_src(pcr_context *ctx, const char *call, const float *src_xyz, int64_t n_src, int nbh) {
     if (n_src < 0 || (n_src > 0 && !src_xyz) || (double)n_src * nbh > (double)(0x7fffffff / 4)) { ctx->err = std::string(call) + ": src_xyz is null or too large"; return PCR_EINVAL; }
     return PCR_OK;
 }
